@@ -23,13 +23,29 @@ see is part of the workload and is built explicitly, independent of --warmup:
      of a long training run;
   --phase start: the same preparation, then every env is reset (fresh people, the
      fire kept, as EvacuationEnv.reset does): all envs at the start of an episode.
-The start-of-episode rate is also reported beside the stationary value
+With --full the start-of-episode rate is also reported beside the stationary value
 (start_phase), from a full reset after the timed steps.
 
 value = env-steps/s of the whole job (E * n_gpus * steps / time) at the headline
-schedule and precision; the JSON line also carries agent-transitions/s (x R), the
-other schedule's rate, the env-only rate, the roofline of the dominant kernel
-(env_step_kernel, HBM-bound) and the CPU baseline. Prints ONE JSON line on rank 0.
+schedule and precision, ms_per_step the milliseconds one of the --steps timed steps took;
+the JSON line also carries agent-transitions/s (x R) and the workload. Prints ONE JSON
+line on rank 0.
+
+A plain run does only that: set-up and preparation, --warmup steps, --steps timed steps,
+the line. --full adds every other reading, each in runs of its own after the timed steps:
+the instrumented pass (env_step_kernel, act and learn times; the rooflines of the dominant
+kernel, env_step_kernel, HBM-bound, and of the act and the learn), the other schedule's
+rate, the env-only rate, the start-of-episode rate, the learn step alone, the whole-job
+reading (N > 1) and the CPU baseline. The headline is measured the same way either way.
+
+--dump-outputs DIR writes, right after the timed steps, what the last timed step handed
+its caller, one DIR/<name>.npy each (rank r > 0: <name>_rank<r>.npy): actions [E*R],
+reward [E], done [E], obs (the compact observations, [E*R*8] words), loss and
+online_params (the flat online weights after the step's update); --mode env: reward,
+done, obs. float32, or float64 for float64 and integer data; 64 MB at most in all -- an
+array beyond its share is a fixed seeded sample of its elements. Every input (env seeds,
+preparation actions, weights, act and replay draws) is seeded, so two runs with the same
+arguments start the timed steps from the same state.
 """
 import argparse
 import glob
@@ -50,6 +66,10 @@ METRIC = "env steps/sec + agent-transitions/sec (whole node), 128x128 grid, 1/2/
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md chip table (spec)
 BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA (spec); f32 via bf16x3 split runs on the same pipe
 EV_EVERY = 5               # timed steps between two HIP-event-bracketed env.step launches
+# the result line's readings beside the headline: measured, and present, only with --full
+FULL_KEYS = ("total_envs_reading", "other_schedule", "env_only_steps_per_s", "start_phase", "env_step_kernel_ms",
+             "learn_ms", "learn_ms_what", "learn_alone_ms", "roofline", "roofline_hbm", "roofline_issue",
+             "roofline_binding", "roofline_act", "roofline_learn", "cpu_baseline")
 
 
 def bytes_per_env_step(P, R, G):
@@ -98,6 +118,73 @@ def counter_record(kind, phase, per_launch, L, P, R):
                     and rec.get("sq_insts_valu_per_wave") and rec.get("clock_ghz")):
                 return rec, os.path.relpath(q, ROOT)
     return None, None
+
+
+def rooflines(args, kern_ms, E, L, W, P, R):
+    """--full: (binding roof, HBM roof, issue roof or None) of env_step_kernel at the launch time kern_ms
+    the instrumented pass measured, with the PMC records of this workload under profiles/."""
+    G = (L + 2) * (W + 2)
+    bpe = bytes_per_env_step(P, R, G)
+    per_launch = E // args.groups if args.mode == "train" else E  # env.step launches of group 0 are timed
+    achieved = bpe * per_launch / (kern_ms * 1e-3) / 1e9
+    traffic, traffic_src, traffic_corr = None, None, None
+
+    def traffic_match(q):  # a PMC record of this kernel, phase, launch size and grid
+        try:
+            rec = json.load(open(q))
+        except (OSError, ValueError):
+            return False
+        return (rec.get("kernel") == "env_step_kernel" and rec.get("envs") in (None, per_launch)
+                and rec.get("grid", [L, W]) == [L, W] and rec.get("people", P) == P and rec.get("robots", R) == R)
+    tpath = args.traffic or next((q for r in ("r6", "r5", "r4", "r3", "r2")
+                                  for pat in (f"env_counters_{args.phase}*.json", f"env_traffic_{args.phase}*.json")
+                                  for q in sorted(glob.glob(os.path.join(ROOT, "profiles", r, pat)))
+                                  if traffic_match(q)), "")
+    if os.path.exists(tpath):
+        # HBM bytes per launch from rocprofv3 PMC passes of this same workload and phase
+        # (separate --pmc FETCH_SIZE / WRITE_SIZE runs; cannot be collected inside the timed run)
+        rec = json.load(open(tpath))
+        if rec.get("kernel") == "env_step_kernel" and rec.get("envs") in (None, per_launch):
+            # raw FETCH + WRITE: the x2 correction of FETCH_SIZE on gfx950 holds for 16-B/lane streaming
+            # reads, and this kernel's loads are 4-8 B per lane; the corrected figure rides along
+            traffic = rec.get("bytes_per_env_step_raw", rec["bytes_per_env_step"]) * per_launch
+            traffic_corr = rec["bytes_per_env_step"] * per_launch
+            traffic_src = os.path.relpath(tpath, ROOT)
+    # the issue roofline of the same kernel (VERDICT r5 item 6): VALU + SALU instructions per wave x waves
+    # per launch (SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_WAVES, one --pmc pass of this workload) against one
+    # instruction per SIMD per cycle (256 CUs x 4 SIMDs x the clock the GRBM pass measured) over the
+    # launch time measured here; valu_pipe_frac prices a wave64 VALU at 2 cycles of its SIMD-32
+    roof_hbm = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                "traffic_basis": "raw FETCH_SIZE + WRITE_SIZE bytes per launch (PMC)",
+                "traffic_fetch_x2": traffic_corr,
+                "frac_traffic": (traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                "frac_basis": "algorithmic bytes (bytes_per_env_step x env-steps per launch) / kernel_ms / peak; "
+                              "frac_traffic: the PMC bytes the kernel actually moved, same time",
+                "kernel": "env_step_kernel", "kernel_ms": kern_ms, "bytes_per_env_step": bpe,
+                "env_steps_per_launch": per_launch,
+                "launches_timed": len([s for s in range(args.steps) if s % EV_EVERY == 0])}
+    roof_issue = None
+    srec, ssrc = counter_record("env_counters", args.phase, per_launch, L, P, R)
+    if srec is not None:
+        waves = srec["waves"]
+        insts = (srec["sq_insts_valu_per_wave"] + srec["sq_insts_salu_per_wave"]) * waves
+        clk = min(srec["clock_ghz"], 2.4) * 1e9  # GRBM reads high on dispatches under ~0.3 ms: at most the 2.4 GHz peak
+        t = kern_ms * 1e-3
+        roof_issue = {"bound": "issue", "achieved": insts / t / 1e9, "peak": 1024 * clk / 1e9, "unit": "Ginst/s",
+                      "frac": insts / (1024 * clk * t),
+                      "valu_pipe_frac": srec["sq_insts_valu_per_wave"] * waves * 2 / (1024 * clk * t),
+                      "valu_per_wave": srec["sq_insts_valu_per_wave"], "salu_per_wave": srec["sq_insts_salu_per_wave"],
+                      "waves_per_launch": waves, "clock_ghz": min(srec["clock_ghz"], 2.4), "kernel_ms": kern_ms,
+                      "sq_active_inst_any_frac": srec.get("sq_active_inst_any_frac"),
+                      "sq_wait_any_frac": srec.get("sq_wait_any_frac"), "source": ssrc,
+                      "basis": "(VALU + SALU instructions per wave) x waves / (256 CUs x 4 SIMDs x clock x kernel_ms): "
+                               "one instruction per SIMD per cycle"}
+    # the binding roof: the larger of the measured-traffic HBM fraction and the issue fraction
+    roof = roof_hbm
+    if roof_issue is not None and roof_issue["frac"] > (roof_hbm["frac_traffic"] or 0.0):
+        roof = dict(roof_issue, traffic=traffic, traffic_source=traffic_src)
+    return roof, roof_hbm, roof_issue
 
 
 def cfg_name(args):
@@ -172,11 +259,22 @@ def parse():
     ap.add_argument("--groups", type=int, default=1,
                     help="env groups per GPU, each with its own act -> env.step -> push stream chain "
                          "(evacx.trainer._Group): one group's env.step tail overlaps the others' work")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the instrumented pass (kernel, act and "
+                         "learn times, rooflines), the other schedule, the env-only and start-of-episode rates, the "
+                         "learn step alone, the whole-job reading (N > 1) and the CPU baseline. Without it the run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (actions, reward, done, "
+                         "observations, loss, online weights) as DIR/<name>.npy (module docstring)")
     ap.add_argument("--traffic", default=None,
                     help="PMC traffic record of env_step_kernel on this workload and phase (tools/parse_prof.py); "
                          "default: the newest profiles/r*/ env_counters_<phase>*.json or env_traffic_<phase>*.json "
                          "record of this workload")
     args = ap.parse_args()
+    if not args.full:  # a plain run: none of the extra readings, no CPU baseline
+        args.other_steps = args.env_steps = args.start_steps = args.total_reading = 0
+        args.no_cpu = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.envs_total > 0:
         if args.envs_total % world:
@@ -219,6 +317,26 @@ def host_threads():
     if omp and omp.isdigit() and int(omp) > 0:
         n = min(n, int(omp))
     return max(1, n)
+
+
+DUMP_BUDGET = 64 << 20  # bytes of --dump-outputs files, all arrays (and ranks) together
+
+
+def dump_outputs(path, arrays, rank, world):
+    """Write {name: tensor} as path/<name>.npy (rank r > 0: <name>_rank<r>.npy), float32 or float64
+    (integer words as float64: exact). An array beyond its share of the budget is cut to a fixed,
+    seeded sample of its elements (sorted indices, the same for every run and build)."""
+    os.makedirs(path, exist_ok=True)
+    wide = (torch.float64, torch.int32, torch.int64)
+    total = sum(t.numel() * (8 if t.dtype in wide else 4) + 256 for t in arrays.values())  # (256: .npy header)
+    mine = DUMP_BUDGET // max(1, world)
+    share = mine // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1).cpu().numpy().astype(np.float64 if t.dtype in wide else np.float32)
+        keep = (share - 256) // a.itemsize
+        if total > mine and a.size > keep:
+            a = a[np.sort(np.random.RandomState(20240).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
 
 
 def main():
@@ -338,7 +456,9 @@ def main():
         cpu_snap = [(env.host_state(i), layout_of[i] if layout_of else 0) for i in range(min(args.cpu_envs, E))]
 
     # ----------------------------------------------------------------- warmup
-    acts_env = torch.randint(0, 5, (max(args.steps, args.warmup, 1), E * R), device="cuda", dtype=torch.int32)
+    # (a seeded generator: the same actions from run to run, so --dump-outputs of two builds compare)
+    acts_env = torch.randint(0, 5, (max(args.steps, args.warmup, 1), E * R), device="cuda", dtype=torch.int32,
+                             generator=torch.Generator(device="cuda").manual_seed(8642 + rank))
     timed_train(args.warmup)
 
     # ------------------------------------------------------------ timed steps
@@ -349,19 +469,32 @@ def main():
     env.check_err()
     loss = float(tr.last_loss.float().mean().item()) if tr.last_loss is not None else None
     value = E * world * args.steps / elapsed
+    train = args.mode == "train"
+    if args.dump_outputs:
+        # what the last timed step left for its caller (VecTrainer.step: the actions taken, the env's
+        # team reward, done flags and compact observations, the learn step's loss and the online
+        # weights after it; --mode env: the env's part), before any further step touches it
+        outs = {"reward": env.reward, "done": env.done, "obs": env.obs}
+        if train:
+            outs["actions"] = tr.actions
+            if tr.last_loss is not None:
+                outs["loss"] = tr.last_loss
+            if tr.learner is not None:
+                outs["online_params"] = tr.learner.online.flat
+        dump_outputs(args.dump_outputs, outs, rank, world)
     # the kernel / learn times: a second pass of the same length right after (same episode phase),
     # HIP events bracketing env.step and the learn step on every EV_EVERY-th step
-    ev_env, ev_learn, ev_act = ev_pairs(args.steps), ev_pairs(args.steps), ev_pairs(args.steps)
-    train = args.mode == "train"
-    timed_train(args.steps, ev_env, ev_learn if train else None, ev_act if train else None)
-    env.check_err()
-    kern_ms = ev_mean(ev_env, args.steps)
-    learn_ms = ev_mean(ev_learn, args.steps) if train else None
-    act_ms = ev_mean(ev_act, args.steps) if train else None
-    # the act's rows on the table path (fire step at the layout's last: fc1 = table + occupancy columns)
-    act_tab = None
-    if train and tr.fast is not None and getattr(tr.fast, "_static", None) is not None:
-        act_tab = float((env.obs.view(-1, 8)[:, 6] >= int(tr.lay.c.t_max)).float().mean().item())
+    kern_ms = learn_ms = act_ms = act_tab = None
+    if args.full:
+        ev_env, ev_learn, ev_act = ev_pairs(args.steps), ev_pairs(args.steps), ev_pairs(args.steps)
+        timed_train(args.steps, ev_env, ev_learn if train else None, ev_act if train else None)
+        env.check_err()
+        kern_ms = ev_mean(ev_env, args.steps)
+        learn_ms = ev_mean(ev_learn, args.steps) if train else None
+        act_ms = ev_mean(ev_act, args.steps) if train else None
+        # the act's rows on the table path (fire step at the layout's last: fc1 = table + occupancy columns)
+        if train and tr.fast is not None and getattr(tr.fast, "_static", None) is not None:
+            act_tab = float((env.obs.view(-1, 8)[:, 6] >= int(tr.lay.c.t_max)).float().mean().item())
 
     # ------------------------------- the other schedule on the same state (extra)
     other = None
@@ -399,7 +532,7 @@ def main():
     # trainer (its six extra learn steps move the weights, Adam, epsilon); without the gradient
     # all-reduce, so it is the learn chain's own time at any world size
     learn_alone_ms = None
-    if args.mode == "train" and tr.fast is not None and tr.replay.size >= args.batch:
+    if args.full and args.mode == "train" and tr.fast is not None and tr.replay.size >= args.batch:
         tr.sync()
         hook_saved, tr.learner.grad_hook = tr.learner.grad_hook, None
         ev_l = ev_pairs(6)
@@ -414,7 +547,7 @@ def main():
     # path: the online / target forwards at B >= 32768, rows at the layout's last fire step, whole
     # 64-row tiles), from the last drawn batch -- for the executed-FLOP basis of roofline_learn
     learn_tab = None
-    if args.mode == "train" and tr.fast is not None and tr.learner is not None and not tr.per_robot:
+    if args.full and args.mode == "train" and tr.fast is not None and tr.learner is not None and not tr.per_robot:
         st = getattr(tr.fast, "_static", None)
         stat_rows = int(st[1].shape[0]) if st is not None else 0
         fr = [0.0, 0.0]
@@ -445,67 +578,9 @@ def main():
                  "what": f"BASELINE.json configs[2] read as {Et * world} envs for the whole {world}-GPU job "
                          f"({Et} per GPU, learn batch {Et} per GPU), same phase preparation and schedule"}
 
-    G = (L + 2) * (W + 2)
-    bpe = bytes_per_env_step(P, R, G)
-    per_launch = E // args.groups if args.mode == "train" else E  # env.step launches of group 0 are timed
-    achieved = bpe * per_launch / (kern_ms * 1e-3) / 1e9
-    traffic, traffic_src, traffic_corr = None, None, None
-    def traffic_match(q):  # a PMC record of this kernel, phase, launch size and grid
-        try:
-            rec = json.load(open(q))
-        except (OSError, ValueError):
-            return False
-        return (rec.get("kernel") == "env_step_kernel" and rec.get("envs") in (None, per_launch)
-                and rec.get("grid", [L, W]) == [L, W] and rec.get("people", P) == P and rec.get("robots", R) == R)
-    tpath = args.traffic or next((q for r in ("r6", "r5", "r4", "r3", "r2")
-                                  for pat in (f"env_counters_{args.phase}*.json", f"env_traffic_{args.phase}*.json")
-                                  for q in sorted(glob.glob(os.path.join(ROOT, "profiles", r, pat)))
-                                  if traffic_match(q)), "")
-    if os.path.exists(tpath):
-        # HBM bytes per launch from rocprofv3 PMC passes of this same workload and phase
-        # (separate --pmc FETCH_SIZE / WRITE_SIZE runs; cannot be collected inside the timed run)
-        rec = json.load(open(tpath))
-        if rec.get("kernel") == "env_step_kernel" and rec.get("envs") in (None, per_launch):
-            # raw FETCH + WRITE: the x2 FETCH correction of MI355X_MICROARCH.md holds for 16-B/lane
-            # streaming reads, and this kernel's loads are 4-8 B per lane; the corrected figure rides along
-            traffic = rec.get("bytes_per_env_step_raw", rec["bytes_per_env_step"]) * per_launch
-            traffic_corr = rec["bytes_per_env_step"] * per_launch
-            traffic_src = os.path.relpath(tpath, ROOT)
-    # the issue roofline of the same kernel: VALU + SALU instructions per wave x waves
-    # per launch (SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_WAVES, one --pmc pass of this workload) against one
-    # instruction per SIMD per cycle (256 CUs x 4 SIMDs x the clock the GRBM pass measured) over the
-    # launch time measured here; valu_pipe_frac prices a wave64 VALU at 2 cycles of its SIMD-32
-    # (MI355X_MICROARCH.md, cycle constants)
-    roof_hbm = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                "traffic_basis": "raw FETCH_SIZE + WRITE_SIZE bytes per launch (PMC)",
-                "traffic_fetch_x2": traffic_corr,
-                "frac_traffic": (traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                "frac_basis": "algorithmic bytes (bytes_per_env_step x env-steps per launch) / kernel_ms / peak; "
-                              "frac_traffic: the PMC bytes the kernel actually moved, same time",
-                "kernel": "env_step_kernel", "kernel_ms": kern_ms, "bytes_per_env_step": bpe,
-                "env_steps_per_launch": per_launch,
-                "launches_timed": len([s for s in range(args.steps) if s % EV_EVERY == 0])}
-    roof_issue = None
-    srec, ssrc = counter_record("env_counters", args.phase, per_launch, L, P, R)
-    if srec is not None:
-        waves = srec["waves"]
-        insts = (srec["sq_insts_valu_per_wave"] + srec["sq_insts_salu_per_wave"]) * waves
-        clk = min(srec["clock_ghz"], 2.4) * 1e9  # GRBM reads high on dispatches under ~0.3 ms: at most the 2.4 GHz peak
-        t = kern_ms * 1e-3
-        roof_issue = {"bound": "issue", "achieved": insts / t / 1e9, "peak": 1024 * clk / 1e9, "unit": "Ginst/s",
-                      "frac": insts / (1024 * clk * t),
-                      "valu_pipe_frac": srec["sq_insts_valu_per_wave"] * waves * 2 / (1024 * clk * t),
-                      "valu_per_wave": srec["sq_insts_valu_per_wave"], "salu_per_wave": srec["sq_insts_salu_per_wave"],
-                      "waves_per_launch": waves, "clock_ghz": min(srec["clock_ghz"], 2.4), "kernel_ms": kern_ms,
-                      "sq_active_inst_any_frac": srec.get("sq_active_inst_any_frac"),
-                      "sq_wait_any_frac": srec.get("sq_wait_any_frac"), "source": ssrc,
-                      "basis": "(VALU + SALU instructions per wave) x waves / (256 CUs x 4 SIMDs x clock x kernel_ms): "
-                               "one instruction per SIMD per cycle"}
-    # the binding roof: the larger of the measured-traffic HBM fraction and the issue fraction
-    roof = roof_hbm
-    if roof_issue is not None and roof_issue["frac"] > (roof_hbm["frac_traffic"] or 0.0):
-        roof = dict(roof_issue, traffic=traffic, traffic_source=traffic_src)
+    roof = roof_hbm = roof_issue = None
+    if args.full:
+        roof, roof_hbm, roof_issue = rooflines(args, kern_ms, E, L, W, P, R)
     cpu = None
     if cpu_snap is not None:
         cpu = cpu_baseline(cpu_snap, env.lay.R, lay_tables, P, args, E)
@@ -617,6 +692,10 @@ def main():
                                                      "row over all 484 inputs, no rebuild. B rows, timed alone, no "
                                                      "all-reduce. The x3 arithmetic issues 2-3 bf16 MFMA products per "
                                                      "f32 product"}
+        line["full"] = args.full
+        if not args.full:  # a plain run carries the headline and its workload only
+            for k in FULL_KEYS:
+                line.pop(k, None)
         print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()

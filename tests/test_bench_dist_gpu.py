@@ -34,7 +34,7 @@ def test_bench_world2_gloo_prints_one_line(tmp_path):
     E, steps = 512, 4
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--dist-backend", "gloo",
            "--grid", "64", "--people", "569", "--robots", "8", "--envs", str(E), "--steps", str(steps),
            "--warmup", "2", "--age-steps", "40", "--stagger", "40", "--other-steps", "0", "--start-steps", "0",
            "--env-steps", "3", "--no-cpu", "--total-reading", str(E)]

@@ -56,9 +56,9 @@ def main():
     src, dst, tag = sys.argv[1], sys.argv[2], sys.argv[3]
     os.makedirs(dst, exist_ok=True)
     out = [f"# rocprofv3 summary `{tag}`", "",
-           "Commands: `tools/profile_r2.sh` -- `bench.py --steps 20 --warmup 5` (the driver's command) and, per "
+           "Commands: `tools/profile_r2.sh` -- `bench.py --full --steps 20 --warmup 5` and, per "
            "episode phase, `rocprofv3 --kernel-trace --stats` / `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` of "
-           "`bench.py --steps 20 --warmup 5 --no-cpu --other-steps 0 --env-steps 0 --start-steps 0 --phase <phase>` "
+           "`bench.py --full --steps 20 --warmup 5 --no-cpu --other-steps 0 --env-steps 0 --start-steps 0 --phase <phase>` "
            "(cfg3: 128x128, P=2276, R=16, the bench's envs per GPU (bench line), strict schedule, f32 Q-net).", ""]
     b = bench_line(os.path.join(src, "bench.json"))
     if b:

@@ -14,10 +14,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 420 python3 "$R/bench.py" --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+timeout -k 10 420 python3 "$R/bench.py" --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 echo "bench done"
 for PH in stationary start; do
-  X="--steps 20 --warmup 5 --no-cpu --other-steps 0 --env-steps 0 --start-steps 0 --phase $PH"
+  X="--full --steps 20 --warmup 5 --no-cpu --other-steps 0 --env-steps 0 --start-steps 0 --phase $PH"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/train_$PH" -o run --output-format csv -- \
       python3 "$R/bench.py" $X > "$OUT/train_$PH.log" 2>&1 || exit $?
   echo "trace $PH done"
