@@ -832,7 +832,12 @@ struct WaveLds {  // word offsets into dynamic LDS
 #endif
 __host__ __device__ inline bool big_grid(int L, int W) { return ((L + 2) * (W + 2) + 31) / 32 > EVX_BIGG_RW; }
 
-__host__ __device__ inline int cbits_words(int G) { return ((G + 1) / 2 + 31) / 32; }
+// the contested-target prefilter's resolution: one bit per 2^CB_SHIFT consecutive cells (see wave_lds)
+#ifndef EVX_CB_SHIFT
+#define EVX_CB_SHIFT 2
+#endif
+constexpr int CB_SHIFT = EVX_CB_SHIFT;
+__host__ __device__ inline int cbits_words(int G) { return (((G + (1 << CB_SHIFT) - 1) >> CB_SHIFT) + 31) / 32; }
 __host__ __device__ inline WaveLds wave_lds(int L, int W, int P, int R, bool bigg = false) {
     WaveLds s;
     const int G = (L + 2) * (W + 2);
@@ -847,9 +852,11 @@ __host__ __device__ inline WaveLds wave_lds(int L, int W, int P, int R, bool big
         s.tbits = s.cbits = s.vac = -1;  // global scratch (env_scratch_words)
     } else {
         s.tbits = o; o += RW;
-        // contested targets at half resolution (cell pairs t >> 1): a set bit marks a pair holding a
-        // contested target; the exact test happens when the candidates are grouped by target (a
-        // mover alone on its target forms a group of one, which shuffles nothing and wins)
+        // contested targets at quarter resolution (cell quads t >> CB_SHIFT): a set bit marks a quad
+        // holding a contested target; the exact test happens when the candidates are grouped by target
+        // (a mover alone on its target forms a group of one, which shuffles nothing and wins). Half
+        // resolution cost 132 words more at 128x128: 13 328 B per env, 11 workgroups per CU after
+        // the 1280-B LDS allocation granule instead of 12
         s.cbits = o; o += cbits_words(G);
         if (RW <= MT_N) {
             s.vac = s.pyring;
@@ -868,7 +875,10 @@ __host__ __device__ inline WaveLds wave_lds(int L, int W, int P, int R, bool big
     s.misc = o; o += GRP_MAX + 16;         // shuffle group; event counter; pairwise stacks
     // the near-robot block map is read only by the rows (dir_prep), before misc is first written
     // (the contested groups): it overlays misc when it fits (256x256: 16.6 -> 16.1 KB per env, 9 -> 10
-    // envs per CU by LDS; 128x128 stays at 12, its VGPR limit)
+    // envs per CU by LDS). A CU allocates LDS in 1280-B granules, 128 of them: 128x128 x P 2276 x
+    // R 16 takes 12 800 B = 10 granules per env, so 12 one-wave workgroups fit -- its VGPR limit
+    // (144 VGPRs: 3 waves per SIMD). One word more costs an 11th granule and the 12th env
+    // (measured: 13 328 B held 11.0 envs per CU); R 32 (12 864 B) is there
     if (NCW <= GRP_MAX + 16) {
         s.nearc = s.misc;
     } else {
@@ -1166,7 +1176,7 @@ __device__ __forceinline__ void rows_wide(const evx_layout& lay, const evx_state
     double* h_g = st.health + (size_t)e * P;
     double* a_g = st.acc + (size_t)e * P;
     uint32_t* scr = st.scratch + (size_t)e * env_scratch_words(lay);
-    uint32_t* cbits = smem + S.cbits;  // contested cell pairs (LDS)
+    uint32_t* cbits = smem + S.cbits;  // contested cell quads (LDS)
     uint2* plan = reinterpret_cast<uint2*>(scr);
     const uint2* ndl = reinterpret_cast<const uint2*>(scr + 2 * P);
     double* hv = reinterpret_cast<double*>(scr + wave_hv_offset(P));
@@ -1376,7 +1386,7 @@ __device__ __forceinline__ void rows_wide(const evx_layout& lay, const evx_state
                     const uint32_t bit = 1u << (t & 31);
                     const uint32_t old = atomicOr(&tbits[t >> 5], bit);
                     if (old & bit) {
-                        atomicOr(&cbits[(t >> 1) >> 5], 1u << ((t >> 1) & 31));
+                        atomicOr(&cbits[(t >> CB_SHIFT) >> 5], 1u << ((t >> CB_SHIFT) & 31));
                         anyc = true;
                     }
                 }
@@ -1511,7 +1521,7 @@ __device__ __forceinline__ void step_env(const evx_layout& lay, const evx_state&
         vac = cbits + g.RW;
     } else {
         tbits = smem + S.tbits;
-        cbits = smem + S.cbits;  // contested cell pairs (half resolution, see wave_lds)
+        cbits = smem + S.cbits;  // contested cell quads (quarter resolution, see wave_lds)
         vac = smem + S.vac;
     }
     auto tc_get = [&](const uint32_t* b, int i) -> bool {
@@ -1520,8 +1530,8 @@ __device__ __forceinline__ void step_env(const evx_layout& lay, const evx_state&
         else
             return bit_get(b, i);
     };
-    // contested target t (big grids: exact, global; others: its cell pair, LDS)
-    auto cb_idx = [&](int t) -> int { return BIGG ? t : t >> 1; };
+    // contested target t (big grids: exact, global; others: its cell quad, LDS)
+    auto cb_idx = [&](int t) -> int { return BIGG ? t : t >> CB_SHIFT; };
     auto cb_get = [&](int t) -> bool { return tc_get(cbits, cb_idx(t)); };
     uint32_t* nearc = smem + S.nearc;
     const int NCW = (((g.L + 2 + 3) >> 2) * ((GY + 3) >> 2) + 31) / 32;
@@ -2939,7 +2949,25 @@ __global__ __launch_bounds__(64 * NWB, EVX_ENV_MINW) void env_step_kernel(evx_la
     }
     if (slot < 0) return;
     const int e = st.order ? st.order[slot] : slot;
+#ifdef EVX_KARG_REREAD
+    // experiment builds (with -DEVX_ENV_MINW=4; DESIGN 4.0.1 Stage B): the light path reads the
+    // arguments from the kernarg segment where it uses them (scalar loads through a pointer the
+    // compiler cannot fold into the preloaded copies) instead of holding them parked in VGPR lanes
+    struct KArgs {  // the kernel's argument list, as the kernarg segment lays it out
+        evx_layout lay;
+        evx_state st;
+        const int32_t* actions;
+        evx_step_out out;
+        int hcap, pslots, part;
+    };
+    const __attribute__((address_space(4))) char* kp =
+        (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    const KArgs& ka = *(const KArgs*)kp;
+    step_env<false, BIGG>(lay_of<MULTI>(ka.lay, ka.st, e), ka.st, ka.actions, ka.out, e, smem + (size_t)w * words);
+#else
     step_env<false, BIGG>(lay_of<MULTI>(lay, st, e), st, actions, out, e, smem + (size_t)w * words);
+#endif
 }
 
 // ------------------------------------------------------- dispatch order
@@ -3344,11 +3372,87 @@ int check_layout(const evx_layout* l) {
     if (!l->floor || !l->cellinfo || !l->valid_bits || !l->danger_p || !l->danger_o) return fail(-22, "missing table");
     return 0;
 }
+// How a step of E envs is launched: the kernel variant, waves per workgroup, dynamic LDS per
+// workgroup and the heavy-env cap. evx_env_step_part launches it, evx_env_step_occupancy asks the
+// runtime how many such workgroups a CU holds.
+typedef void (*step_kernel_t)(evx_layout, evx_state, const int32_t*, evx_step_out, int, int, int);
+struct StepLaunch {
+    step_kernel_t fn;
+    int nwb;     // waves (64 * nwb threads) per workgroup
+    size_t lds;  // dynamic LDS bytes per workgroup
+    int hcap, hmin, pslots;
+};
+int step_select(const evx_layout& l, const evx_state& s, StepLaunch* sl) {
+    const bool bigg = evx::big_grid(l.L, l.W);
+    if (step_lds_bytes(l, bigg) > 160 * 1024) return fail(-7, "layout needs more than 160 KiB of LDS");
+    const bool multi = l.layout_set && s.layout_idx;
+    {
+        static std::atomic<uint64_t> attr_done;
+        const void* ks[10] = {(const void*)evx::env_step_kernel<1, false>, (const void*)evx::env_step_kernel<2, false>,
+                              (const void*)evx::env_step_kernel<4, false>, (const void*)evx::env_step_kernel<1, true>,
+                              (const void*)evx::env_step_kernel<2, true>, (const void*)evx::env_step_kernel<4, true>,
+                              (const void*)evx::env_step_kernel<1, false, true>,
+                              (const void*)evx::env_step_kernel<2, false, true>,
+                              (const void*)evx::env_step_kernel<1, true, true>,
+                              (const void*)evx::env_step_kernel<2, true, true>};
+        evxh::max_lds_once(attr_done, ks, 10, 160 * 1024);
+    }
+    // Default: 4-wave workgroups with the heavy-env path while a launch is short enough for
+    // its heaviest env to set its length (fewer than 64 envs per CU); one-wave workgroups
+    // beyond, where throughput rules: a wave's VGPRs and LDS free the moment its env is done
+    // instead of when the slowest of four is (32768 envs: env_step 1.50 -> 1.31 ms).
+    const int ncu = evxh::cu_count();
+    // (64 envs per CU: the 8192-env share of cfg5 keeps the heavy-env workgroups -- env_step 0.42 ->
+    // 0.37 ms; big grids, which have no heavy path, switch at 32)
+    int nwb = s.E >= (bigg ? 32 : 64) * ncu ? 1 : 4;
+    // EVX_ENV_NWB = 1 / 2 / 4 overrides (tuning, and tests of the one-wave variant at a small E)
+    if (const char* v = getenv("EVX_ENV_NWB")) {
+        const int n = atoi(v);
+        if (n == 1 || n == 2 || n == 4) nwb = n;
+    }
+    if (bigg && nwb > 2) nwb = 2;  // BIGG kernels: 1 or 2 envs per workgroup
+    while (nwb > 1 && step_launch_lds(l, nwb, bigg) > 160 * 1024) nwb >>= 1;
+    sl->nwb = nwb;
+    sl->hmin = 0;
+    sl->hcap = (nwb == evx::WNW && s.order) ? heavy_cap(l, &sl->hmin) : 0;
+    // single-wave envs at order slots < H + pslots could run at raised wave priority: 0 (a sweep
+    // of 0 / 1 / 256 / 768 / 1536 slots measured box noise in the training step)
+    sl->pslots = 0;
+    sl->lds = step_launch_lds(l, nwb, bigg);
+    if (bigg)
+        sl->fn = nwb == 2 ? (multi ? evx::env_step_kernel<2, true, true> : evx::env_step_kernel<2, false, true>)
+                          : (multi ? evx::env_step_kernel<1, true, true> : evx::env_step_kernel<1, false, true>);
+    else if (nwb == 4)
+        sl->fn = multi ? evx::env_step_kernel<4, true> : evx::env_step_kernel<4, false>;
+    else if (nwb == 2)
+        sl->fn = multi ? evx::env_step_kernel<2, true> : evx::env_step_kernel<2, false>;
+    else
+        sl->fn = multi ? evx::env_step_kernel<1, true> : evx::env_step_kernel<1, false>;
+    return 0;
+}
 }  // namespace
 
 extern "C" {
 
 const char* evx_last_error(void) { return g_err; }
+
+int evx_env_step_occupancy(const evx_layout* l, const evx_state* s, int32_t* blocks_per_cu, int32_t* lds_bytes,
+                           int32_t* block_threads) {
+    int rc = check_layout(l);
+    if (rc) return rc;
+    if (!s || !blocks_per_cu || !lds_bytes || !block_threads) return fail(-22, "NULL argument");
+    StepLaunch sl;
+    rc = step_select(*l, *s, &sl);
+    if (rc) return rc;
+    int n = 0;
+    const hipError_t e =
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)sl.fn, 64 * sl.nwb, sl.lds);
+    if (e != hipSuccess) return hip_fail(e, "env_step occupancy query");
+    *blocks_per_cu = n;
+    *lds_bytes = (int32_t)sl.lds;
+    *block_threads = 64 * sl.nwb;
+    return 0;
+}
 
 int64_t evx_step_lds_bytes(const evx_layout* l) {
     if (check_layout(l)) return -1;
@@ -3380,72 +3484,14 @@ int evx_env_step_part(const evx_layout* l, const evx_state* s, const int32_t* ac
         while ((1LL << gb) < (long long)G) gb++;
         if (pb + gb > 32) return fail(-22, "grid cells x people too large for 32-bit move keys");
     }
-    const bool bigg = evx::big_grid(l->L, l->W);
-    const size_t lds = step_lds_bytes(*l, bigg);
-    if (lds > 160 * 1024) return fail(-7, "layout needs more than 160 KiB of LDS");
-    const bool multi = l->layout_set && s->layout_idx;
-    {
-        static std::atomic<uint64_t> attr_done;
-        const void* ks[10] = {(const void*)evx::env_step_kernel<1, false>, (const void*)evx::env_step_kernel<2, false>,
-                              (const void*)evx::env_step_kernel<4, false>, (const void*)evx::env_step_kernel<1, true>,
-                              (const void*)evx::env_step_kernel<2, true>, (const void*)evx::env_step_kernel<4, true>,
-                              (const void*)evx::env_step_kernel<1, false, true>,
-                              (const void*)evx::env_step_kernel<2, false, true>,
-                              (const void*)evx::env_step_kernel<1, true, true>,
-                              (const void*)evx::env_step_kernel<2, true, true>};
-        evxh::max_lds_once(attr_done, ks, 10, 160 * 1024);
-    }
-    // Default: 4-wave workgroups with the heavy-env path while a launch is short enough for
-    // its heaviest env to set its length (fewer than 64 envs per CU); one-wave workgroups
-    // beyond, where throughput rules: a wave's VGPRs and LDS free the moment its env is done
-    // instead of when the slowest of four is (32768 envs: env_step 1.50 -> 1.31 ms).
-    const int ncu = evxh::cu_count();
-    // (64 envs per CU: the 8192-env share of cfg5 keeps the heavy-env workgroups -- env_step 0.42 ->
-    // 0.37 ms; big grids, which have no heavy path, switch at 32)
-    int nwb = s->E >= (bigg ? 32 : 64) * ncu ? 1 : 4;
-    if (bigg && nwb > 2) nwb = 2;  // BIGG kernels: 1 or 2 envs per workgroup
-    while (nwb > 1 && step_launch_lds(*l, nwb, bigg) > 160 * 1024) nwb >>= 1;
-    int hmin = 0;
-    const int hcap = (nwb == evx::WNW && s->order) ? heavy_cap(*l, &hmin) : 0;
-    // single-wave envs at order slots < H + pslots could run at raised wave priority: 0 (a sweep
-    // of 0 / 1 / 256 / 768 / 1536 slots measured box noise in the training step)
-    const int pslots = 0;
-    const size_t blds = step_launch_lds(*l, nwb, bigg);
+    StepLaunch sl;
+    rc = step_select(*l, *s, &sl);
+    if (rc) return rc;
     // heavy envs take a workgroup each; part 1: only those, part 2: only the rest
-    if (part == 1 && hcap == 0) return 0;  // no heavy workgroups for this layout: part 2 steps every env
-    const int nblk = part == 1 ? hcap : (s->E + nwb - 1) / nwb + (part == 0 ? hcap : 0);
-    hipStream_t hs = (hipStream_t)stream;
-    if (bigg) {
-        if (nwb == 2 && multi)
-            hipLaunchKernelGGL((evx::env_step_kernel<2, true, true>), dim3(nblk), dim3(128), blds, hs, *l, *s, actions,
-                               *o, 0, 0, (int)part);
-        else if (nwb == 2)
-            hipLaunchKernelGGL((evx::env_step_kernel<2, false, true>), dim3(nblk), dim3(128), blds, hs, *l, *s, actions,
-                               *o, 0, 0, (int)part);
-        else if (multi)
-            hipLaunchKernelGGL((evx::env_step_kernel<1, true, true>), dim3(nblk), dim3(64), blds, hs, *l, *s, actions,
-                               *o, 0, 0, (int)part);
-        else
-            hipLaunchKernelGGL((evx::env_step_kernel<1, false, true>), dim3(nblk), dim3(64), blds, hs, *l, *s, actions,
-                               *o, 0, 0, (int)part);
-    } else if (nwb == 4 && multi)
-        hipLaunchKernelGGL((evx::env_step_kernel<4, true>), dim3(nblk), dim3(256), blds, hs, *l, *s, actions, *o, hcap,
-                           pslots, (int)part);
-    else if (nwb == 4)
-        hipLaunchKernelGGL((evx::env_step_kernel<4, false>), dim3(nblk), dim3(256), blds, hs, *l, *s, actions, *o, hcap,
-                           pslots, (int)part);
-    else if (nwb == 2 && multi)
-        hipLaunchKernelGGL((evx::env_step_kernel<2, true>), dim3(nblk), dim3(128), blds, hs, *l, *s, actions, *o, 0, 0,
-                           (int)part);
-    else if (nwb == 2)
-        hipLaunchKernelGGL((evx::env_step_kernel<2, false>), dim3(nblk), dim3(128), blds, hs, *l, *s, actions, *o, 0, 0,
-                           (int)part);
-    else if (multi)
-        hipLaunchKernelGGL((evx::env_step_kernel<1, true>), dim3(nblk), dim3(64), blds, hs, *l, *s, actions, *o, 0, 0,
-                           (int)part);
-    else
-        hipLaunchKernelGGL((evx::env_step_kernel<1, false>), dim3(nblk), dim3(64), blds, hs, *l, *s, actions, *o, 0, 0,
-                           (int)part);
+    if (part == 1 && sl.hcap == 0) return 0;  // no heavy workgroups for this layout: part 2 steps every env
+    const int nblk = part == 1 ? sl.hcap : (s->E + sl.nwb - 1) / sl.nwb + (part == 0 ? sl.hcap : 0);
+    hipLaunchKernelGGL(sl.fn, dim3(nblk), dim3(64 * sl.nwb), sl.lds, (hipStream_t)stream, *l, *s, actions, *o, sl.hcap,
+                       sl.pslots, (int)part);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_fail(e, "env_step launch");
 }

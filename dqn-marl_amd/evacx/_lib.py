@@ -68,6 +68,10 @@ def lib():
         L.evx_env_step_part.restype = C.c_int
         L.evx_env_step_part.argtypes = [C.POINTER(evx_layout), C.POINTER(evx_state), C.c_void_p,
                                         C.POINTER(evx_step_out), C.c_int32, C.c_void_p]
+        if hasattr(L, "evx_env_step_occupancy"):  # an older build under EVX_LIB (A/B runs) lacks the query
+            L.evx_env_step_occupancy.restype = C.c_int
+            L.evx_env_step_occupancy.argtypes = [C.POINTER(evx_layout), C.POINTER(evx_state)] + \
+                [C.POINTER(C.c_int32)] * 3
         L.evx_env_reset.argtypes = [C.POINTER(evx_layout), C.POINTER(evx_state), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
         L.evx_obs_expand_f32.argtypes = [C.POINTER(evx_layout), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
@@ -98,4 +102,5 @@ def check(rc: int, what: str):
 # every C symbol include/evacx.h declares (checked by tests/test_abi.py)
 EXPORTS = ["evx_env_step", "evx_env_reset", "evx_obs_expand_f32", "evx_obs_expand_f64", "evx_seed_host",
            "evx_step_lds_bytes", "evx_step_scratch_words", "evx_last_error", "evx_perm_ws_bytes",
-           "evx_env_order", "evx_act_perm", "evx_env_orders", "evx_env_classes", "evx_env_orders_push", "evx_env_orders_push_sample"]
+           "evx_env_order", "evx_act_perm", "evx_env_orders", "evx_env_classes", "evx_env_orders_push", "evx_env_orders_push_sample",
+           "evx_env_step_occupancy"]

@@ -134,6 +134,13 @@ int evx_env_step(const evx_layout *lay, const evx_state *st, const int32_t *acti
  * state, order, actions and outputs; results are identical to the one-launch step. */
 int evx_env_step_part(const evx_layout *l, const evx_state *s, const int32_t *actions, const evx_step_out *o,
                       int32_t part, void *stream);
+/* Diagnostics, launches nothing: the workgroup evx_env_step_part would launch for this layout and
+ * st->E (only E, order and layout_idx of st are looked at, none dereferenced) -- its threads, its
+ * dynamic LDS bytes, and how many such workgroups the runtime says one CU holds
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor: registers, LDS allocation granule, wave slots).
+ * EVX_ENV_NWB = 1 / 2 / 4 in the environment overrides the waves per workgroup of both. */
+int evx_env_step_occupancy(const evx_layout *l, const evx_state *s, int32_t *blocks_per_cu, int32_t *lds_bytes,
+                           int32_t *block_threads);
 
 /* Replaces EvacuationEnv.reset / EvacuationEnvMulti.reset (envs/evacuation_env.py:61-82,
  * envs/evacuation_env_multi.py:31-42) incl. People placement (envs/people.py:183-194).
