@@ -1,0 +1,133 @@
+"""Vectorised DQN training with episode logging: evacx.trainer.VecTrainer over many envs.
+
+Reads the env and agent sections of ``configs/dqn.yaml`` (the file the single-env runner
+reads), trains ``--envs`` copies of that env for ``--steps`` vectorised steps with the
+device-resident trainer, and every ``--log-every`` steps takes one ``episode_summary()``
+of the episodes finished since the last one: a printed line, a CSV row
+(``training_log.csv``: step, episodes, reward, evac_rate, death_rate, length, loss,
+epsilon) and ``best_model.pth`` whenever the window's mean return beats the best so
+far; ``dqn_model.pth`` at the end. Checkpoints are the reference's dict (q_network,
+target_network, optimizer, epsilon, steps: agents/dqn_agent.py:174-191), so a ``--qnet
+conv`` file loads through the drop-in ``DQNAgent.load``. ``--eval-episodes N`` ends with
+a greedy evaluation (evacx.evaluate) of N episodes per env.
+
+Usage: python -m Louvre_Evacuation.runners.train_vec --envs 4096 --steps 2000   (from dqn-marl_amd/)
+"""
+import argparse
+import csv
+import os
+import sys
+from collections import OrderedDict
+
+project_root = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
+if project_root not in sys.path:
+    sys.path.insert(0, project_root)
+
+import torch  # noqa: E402
+import yaml  # noqa: E402
+
+CSV_COLUMNS = ["step", "episodes", "reward", "evac_rate", "death_rate", "length", "loss", "epsilon"]
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--config", default=os.path.join(project_root, "configs", "dqn.yaml"))
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--log-every", type=int, default=100)
+    ap.add_argument("--qnet", choices=["mlp", "conv"], default="mlp")
+    ap.add_argument("--out", default=None, help="output directory (default: the config's save_path)")
+    ap.add_argument("--eval-episodes", type=int, default=0, help="episodes per env of a final greedy evaluation")
+    ap.add_argument("--eval-envs", type=int, default=None, help="envs of that evaluation (default: --envs)")
+    ap.add_argument("--batch", type=int, default=None, help="learn batch (default: max(256, the config's batch_size))")
+    ap.add_argument("--seed", type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def checkpoint(tr) -> dict:
+    """The reference's checkpoint dict from the trainer's learner: plain tensors and scalars."""
+    from Louvre_Evacuation.agents.dqn_agent import _AdamView
+    lr = tr.learner
+    return {"q_network": OrderedDict((k, v.detach().cpu().clone()) for k, v in lr.online.state_dict().items()),
+            "target_network": OrderedDict((k, v.detach().cpu().clone()) for k, v in lr.target.state_dict().items()),
+            "optimizer": _AdamView(lr).state_dict(),
+            "epsilon": float(tr.epsilon),
+            "steps": int(tr.learn_steps)}
+
+
+def _fmt(v, spec):
+    return "n/a" if v is None else format(v, spec)
+
+
+def train_vec(args):
+    from evacx.env import DeviceLayout
+    from evacx.layout import LayoutSpec, build_tables
+    from evacx.trainer import VecTrainer
+    if not torch.cuda.is_available():
+        raise RuntimeError("train_vec needs an MI355X (HIP) device; no CPU fallback exists")
+    if args.envs < 2 or args.envs % 2 or args.steps < 1 or args.log_every < 1:
+        raise ValueError("--envs must be even and >= 2, --steps and --log-every >= 1")
+    with open(args.config, "r", encoding="utf-8") as f:
+        config = yaml.safe_load(f)
+    ec, ac = config["env"], config["agent"]
+    out_dir = args.out or os.path.join(project_root, config.get("save_path", "dqn_results"))
+    os.makedirs(out_dir, exist_ok=True)
+    # the single-robot env of EvacuationEnv (fire_zones is stored and never read, as in the reference)
+    ex = ec.get("exit_location", [36, 15])
+    spec = LayoutSpec(L=int(ec["width"]), W=int(ec["height"]), exit=(int(ex[0]), int(ex[1])))
+    device = torch.device("cuda", torch.cuda.current_device())
+    lay = DeviceLayout(build_tables(spec), int(ec["num_people"]), device=device)
+    batch = args.batch or max(256, int(ac.get("batch_size", 32)))
+    capacity = 1 << max(10, (max(int(ac.get("memory_size", 50000)), 4 * batch, 2 * args.envs * lay.R) - 1).bit_length())
+    tr = VecTrainer(lay, args.envs, kind=args.qnet, batch=batch, replay_capacity=capacity,
+                    lr=float(ac.get("learning_rate", 1e-4)), gamma=float(ac.get("gamma", 0.99)),
+                    epsilon=float(ac.get("epsilon", 1.0)), epsilon_min=float(ac.get("epsilon_min", 0.02)),
+                    epsilon_decay=float(ac.get("epsilon_decay", 0.9995)),
+                    target_every=int(ac.get("target_update_freq", 200)), learner_seed=args.seed,
+                    act_table=lay.R % 2 == 0, episode_stats=True)
+    print(f"env {spec.L}x{spec.W}, {lay.P} people, exit {tuple(spec.exit)}; {args.envs} envs, {args.qnet} Q-network "
+          f"({tr.q_arith}), batch {batch}, replay {capacity} on {device}")
+    best = float("-inf")
+    with open(os.path.join(out_dir, "training_log.csv"), "w", newline="") as f:
+        log = csv.writer(f)
+        log.writerow(CSV_COLUMNS)
+        for step in range(1, args.steps + 1):
+            tr.step()
+            if step % args.log_every and step != args.steps:
+                continue
+            s = tr.episode_summary()  # the only host sync of the loop
+            loss = None if tr.last_loss is None else float(tr.last_loss.item())
+            log.writerow([step, s["episodes"]] + ["" if v is None else repr(v) for v in
+                         (s["return_mean"], s["evac_rate"], s["death_rate"], s["length_mean"], loss)] +
+                         [repr(float(tr.epsilon))])
+            f.flush()
+            print(f"step {step:7d}: episodes={s['episodes']:6d}, reward={_fmt(s['return_mean'], '9.2f')}, "
+                  f"evac={_fmt(s['evac_rate'], '.2%')}, death={_fmt(s['death_rate'], '.2%')}, "
+                  f"len={_fmt(s['length_mean'], '.1f')}, loss={_fmt(loss, '.4f')}, eps={tr.epsilon:.4f}")
+            if s["episodes"] >= 1 and s["return_mean"] > best:
+                best = s["return_mean"]
+                torch.save(checkpoint(tr), os.path.join(out_dir, "best_model.pth"))
+    tr.sync()
+    tr.env.check_err()
+    torch.save(checkpoint(tr), os.path.join(out_dir, "dqn_model.pth"))
+    print(f"best window reward {_fmt(None if best == float('-inf') else best, '.2f')}; results in {out_dir}")
+    if args.eval_episodes > 0:
+        from evacx.evaluate import evaluate
+        torch.cuda.current_stream(device).synchronize()
+        ev = evaluate(lay, args.eval_envs or args.envs, args.eval_episodes, "greedy", learner=tr.learner,
+                      seed=args.seed)
+        print(f"greedy evaluation over {ev['episodes']} episodes: reward={ev['return_mean']:.2f} "
+              f"(std {ev['return_std']:.2f}, min {ev['return_min']:.2f}, max {ev['return_max']:.2f}), "
+              f"evac={ev['evac_rate']:.2%}, death={ev['death_rate']:.2%}, len={ev['length_mean']:.1f}")
+    return tr
+
+
+def main(argv=None):
+    try:
+        return train_vec(parse_args(argv))
+    except KeyboardInterrupt:
+        print("training interrupted")
+
+
+if __name__ == "__main__":
+    main()

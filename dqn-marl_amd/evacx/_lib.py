@@ -103,4 +103,6 @@ def check(rc: int, what: str):
 EXPORTS = ["evx_env_step", "evx_env_reset", "evx_obs_expand_f32", "evx_obs_expand_f64", "evx_seed_host",
            "evx_step_lds_bytes", "evx_step_scratch_words", "evx_last_error", "evx_perm_ws_bytes",
            "evx_env_order", "evx_act_perm", "evx_env_orders", "evx_env_classes", "evx_env_orders_push", "evx_env_orders_push_sample",
-           "evx_env_step_occupancy"]
+           "evx_env_step_occupancy",
+           "evx_episode_init", "evx_episode_update", "evx_episode_discard", "evx_episode_reduce",
+           "evx_episode_last_error"]

@@ -1,0 +1,188 @@
+"""Episode statistics on the device (csrc/episode.hip, ``evx_episode_*`` in include/evacx.h).
+
+The reference's training loop logs each episode's total reward, ``evacuation_rate`` and
+``death_rate`` on the host (runners/train_dqn.py:129-161). The vectorised envs reset inside
+the step launch and overwrite ``reward``, ``done`` and ``counts`` one step later, so
+``EpisodeStats`` folds them per env on the device, one launch per step and no host sync;
+``summary()`` reduces the window over envs (one fixed summation order) and copies a few
+hundred bytes back.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional
+
+import torch
+
+from . import _lib
+from .env import _ptr, _stream
+
+REDUCE_SPAN = 1024  # EVX_EPISODE_REDUCE_SPAN: envs one pass of a reduce workgroup covers
+ROW_WORDS = 10      # sizeof(evx_episode_row) / 8
+
+_I64 = ("w_n", "w_len", "w_evac", "w_dead", "n_total")
+_F64 = ("ret", "w_ret", "w_ret2", "w_min", "w_max", "last_ret")
+_I32 = ("len", "last_len", "last_evac", "last_dead")
+_TAB = ("tab_ret", "tab_len", "tab_evac", "tab_dead")
+
+
+class evx_episodes(C.Structure):
+    _fields_ = [("E", C.c_int32), ("tab_slots", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ["ret", "len", "w_n", "w_len", "w_evac", "w_dead", "w_ret", "w_ret2",
+                                         "w_min", "w_max", "last_ret", "last_len", "last_evac", "last_dead",
+                                         "n_total", "tab_ret", "tab_len", "tab_evac", "tab_dead"]]
+
+
+_inited = False
+
+
+def elib():
+    global _inited
+    L = _lib.lib()
+    if not _inited:
+        P = C.POINTER(evx_episodes)
+        L.evx_episode_last_error.restype = C.c_char_p
+        L.evx_episode_init.argtypes = [P, C.c_void_p]
+        L.evx_episode_update.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.evx_episode_discard.argtypes = [P, C.c_void_p, C.c_void_p]
+        L.evx_episode_reduce.argtypes = [P, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+        for name in ("evx_episode_init", "evx_episode_update", "evx_episode_discard", "evx_episode_reduce"):
+            getattr(L, name).restype = C.c_int
+        _inited = True
+    return L
+
+
+def echeck(rc, what):
+    if rc != 0:
+        raise _lib.EvacxError(f"{what} failed ({rc}): {elib().evx_episode_last_error().decode()}")
+
+
+def _need(name, t, n, dtype, device):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: a tensor is needed, not {type(t).__name__}")
+    if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name}: needs {n} contiguous {dtype} elements, got {t.numel()} of {t.dtype}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: on {t.device}, the statistics are on {device}")
+
+
+def _row_dict(irow, frow, P: int) -> dict:
+    n = int(irow[0])
+    d = dict(episodes=n, return_min=None, return_max=None, return_mean=None, return_std=None, length_mean=None,
+             evac_rate=None, death_rate=None, remaining=int(irow[8]), no_episode=int(irow[9]),
+             length_sum=int(irow[1]), evacuated=int(irow[2]), dead=int(irow[3]),
+             return_sum=float(frow[4]), return_sq_sum=float(frow[5]))
+    if n > 0:
+        mean = d["return_sum"] / n
+        d.update(return_mean=mean, return_std=math.sqrt(max(d["return_sq_sum"] / n - mean * mean, 0.0)),
+                 return_min=float(frow[6]), return_max=float(frow[7]), length_mean=d["length_sum"] / n,
+                 evac_rate=d["evacuated"] / (n * P), death_rate=d["dead"] / (n * P))
+    return d
+
+
+class _Slice:
+    """``n`` envs of an EpisodeStats from env ``lo`` (a VecEnv.split part's own envs): the same
+    buffers through offset pointers."""
+
+    def __init__(self, owner: "EpisodeStats", lo: int, n: int):
+        self.owner, self.lo, self.E = owner, lo, n
+        K = owner.record
+        self.c = evx_episodes(E=n, tab_slots=K)
+        for name in _I64 + _F64 + _I32:
+            setattr(self.c, name, _ptr(getattr(owner, name)[lo:lo + n]))
+        if K:
+            for name in _TAB:
+                setattr(self.c, name, _ptr(getattr(owner, name)[lo:lo + n]))
+
+    def update(self, reward: torch.Tensor, done: torch.Tensor, counts: torch.Tensor):
+        """Fold one step's outputs of these envs (VecEnv.reward / done / counts), one launch on
+        the current stream."""
+        dev = self.owner.device
+        _need("reward", reward, self.E, torch.float64, dev)
+        _need("done", done, self.E, torch.uint8, dev)
+        _need("counts", counts, 2 * self.E, torch.int32, dev)
+        echeck(elib().evx_episode_update(C.byref(self.c), reward.data_ptr(), done.data_ptr(), counts.data_ptr(),
+                                         self.owner.cap, _stream()), "episode_update")
+
+    def discard(self, mask: Optional[torch.Tensor] = None):
+        """Drop the episode in progress of the masked envs (None: all): for envs reset from
+        outside the step. One launch on the current stream."""
+        m = mask
+        if m is not None:
+            if isinstance(m, torch.Tensor) and m.dtype == torch.bool:
+                m = m.to(torch.uint8)
+            _need("mask", m, self.E, torch.uint8, self.owner.device)
+        echeck(elib().evx_episode_discard(C.byref(self.c), _ptr(m), _stream()), "episode_discard")
+
+
+class EpisodeStats(_Slice):
+    """Per-env episode statistics of E envs of P people each.
+
+    layout_idx / n_layouts: each env's layout (VecEnv.layout_idx of a LayoutSet) for the
+    per-layout rows of ``summary``. cap > 0: only the first ``cap`` episodes of every env
+    enter the window (an evaluation over exactly E * cap episodes). record = K > 0: the
+    first K episodes of every env are also kept one by one (``tab_ret`` ... [E, K]).
+
+    Public per-env tensors: the episode in progress ``ret``, ``len``; the window ``w_n``,
+    ``w_len``, ``w_evac``, ``w_dead``, ``w_ret``, ``w_ret2``, ``w_min``, ``w_max``; the last
+    finished episode ``last_return`` (= ``last_ret``), ``last_len``, ``last_evac``,
+    ``last_dead``; the lifetime count ``n_total``."""
+
+    def __init__(self, E: int, device, P: int, layout_idx: Optional[torch.Tensor] = None, n_layouts: int = 1,
+                 cap: int = 0, record: int = 0):
+        E, P, n_layouts, cap, record = int(E), int(P), int(n_layouts), int(cap), int(record)
+        if E < 1 or P < 1:
+            raise ValueError(f"EpisodeStats: E and P must be >= 1, not {E}, {P}")
+        if cap < 0 or record < 0:
+            raise ValueError("EpisodeStats: cap and record must be >= 0")
+        if not 1 <= n_layouts <= 65535:
+            raise ValueError(f"EpisodeStats: n_layouts must be 1..65535, not {n_layouts}")
+        if n_layouts > 1 and layout_idx is None:
+            raise ValueError("EpisodeStats: several layouts need layout_idx")
+        device = torch.device(device)
+        if layout_idx is not None:
+            _need("layout_idx", layout_idx, E, torch.int32, None)
+            if layout_idx.device.type != device.type:
+                raise ValueError(f"layout_idx: on {layout_idx.device}, the statistics are on {device}")
+        self.P, self.n_layouts, self.cap, self.record, self.device = P, n_layouts, cap, record, device
+        self.layout_idx = layout_idx
+        for name in _I64:
+            setattr(self, name, torch.zeros(E, dtype=torch.int64, device=device))
+        for name in _F64:
+            setattr(self, name, torch.zeros(E, dtype=torch.float64, device=device))
+        for name in _I32:
+            setattr(self, name, torch.zeros(E, dtype=torch.int32, device=device))
+        if record:
+            self.tab_ret = torch.zeros(E, record, dtype=torch.float64, device=device)
+            for name in _TAB[1:]:
+                setattr(self, name, torch.zeros(E, record, dtype=torch.int32, device=device))
+        self.device = self.ret.device  # with its index
+        self.last_return = self.last_ret
+        self.rows = torch.zeros((n_layouts + 1) * ROW_WORDS, dtype=torch.int64, device=device)
+        super().__init__(self, 0, E)
+        echeck(elib().evx_episode_init(C.byref(self.c), _stream()), "episode_init")
+
+    def view(self, lo: int, n: int) -> _Slice:
+        """The slice object of envs [lo, lo + n): its update / discard touch only those."""
+        lo, n = int(lo), int(n)
+        if lo < 0 or n < 1 or lo + n > self.E:
+            raise ValueError(f"view: envs [{lo}, {lo + n}) are not within 0..{self.E}")
+        return _Slice(self, lo, n)
+
+    def summary(self, clear: bool = True) -> dict:
+        """Reduce the window over envs (one launch, plus one that empties the window when
+        ``clear``), copy the rows to the host (this waits for the current stream) and return
+        the "all" row as a dict, with ``per_layout`` a list of the same dicts. With no episode
+        in the window the means and rates are None."""
+        echeck(elib().evx_episode_reduce(C.byref(self.c), _ptr(self.layout_idx), self.n_layouts, self.cap,
+                                         self.rows.data_ptr(), int(bool(clear)), _stream()), "episode_reduce")
+        host = self.rows.cpu()
+        irows = host.view(self.n_layouts + 1, ROW_WORDS).tolist()
+        frows = host.view(torch.float64).view(self.n_layouts + 1, ROW_WORDS).tolist()
+        out = _row_dict(irows[-1], frows[-1], self.P)
+        out["per_layout"] = [_row_dict(irows[l], frows[l], self.P) for l in range(self.n_layouts)]
+        return out
+
+
+__all__ = ["EpisodeStats", "evx_episodes", "REDUCE_SPAN"]

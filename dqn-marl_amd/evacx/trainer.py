@@ -127,6 +127,7 @@ class _Group:
         self.ev_order.record(cur)
         self.perm = None  # the act's env order over this group's envs (x3 table path), or None
         self.act_ws = None  # the x3 act's workspace (evx_qmlp_fwd_out.act_ws), made at the first act
+        self.ep = None  # this group's envs of the trainer's EpisodeStats (episode_stats=True), or None
 
 
 class VecTrainer:
@@ -137,7 +138,7 @@ class VecTrainer:
                  grad_hook=None, learn_every: int = 1, lagged_learn: bool = False, replay: str = "uniform",
                  prio_alpha: float = 0.6, prio_beta0: float = 0.4, prio_beta_steps: int = 100000,
                  prio_eps: float = 1e-6, groups: int = 1, layout_of=None, world_envs: Optional[int] = None,
-                 nets: str = "shared", act_table: Optional[bool] = None):
+                 nets: str = "shared", act_table: Optional[bool] = None, episode_stats: bool = False):
         """groups: the envs are split into this many parts, each stepping on its own
         stream chain (see _Group), group g's act after group g - 1's (it overlaps that
         group's env.step); neither the env results nor the act's dropout masks (one stream
@@ -152,7 +153,11 @@ class VecTrainer:
         its own network, memory and optimizer, as runners/train_double_dqn.py:35-56 gives each
         robot its own DQNAgent: evacx.qgroup.GroupedLearner, batch / R transitions per net per
         learn step, strict schedule, one GPU) or "qmix" (per-robot nets under a QMIX mixer,
-        runners/train_qmix.py: batch / R joint env-steps per learn step, evacx.qgroup.GroupedQMix)."""
+        runners/train_qmix.py: batch / R joint env-steps per learn step, evacx.qgroup.GroupedQMix).
+        episode_stats: keep every env's episode returns, lengths and evacuated / dead counts on
+        the device (evacx.episodes.EpisodeStats: one more launch per group and step on the
+        group's stream, between env.step and the push; no host sync) for episode_summary().
+        Off: nothing is allocated or launched for it."""
         if precision not in ("f32", "bf16", "exact"):
             raise ValueError(f"precision must be 'f32', 'bf16' or 'exact', not {precision!r}")
         self.lay, self.E, self.R = layout, E, layout.R
@@ -222,6 +227,15 @@ class VecTrainer:
         self.groups: List[_Group] = [_Group(p, g, g * ng, self.actions[g * ng:(g + 1) * ng], self.device)
                                      for g, p in enumerate(parts)]
         self.main = self.groups[0].main
+        # episode statistics (the reference's per-episode log, runners/train_dqn.py:129-161), or None
+        self.episodes = None
+        if episode_stats:
+            from .env import LayoutSet
+            from .episodes import EpisodeStats
+            self.episodes = EpisodeStats(E, self.device, layout.P, layout_idx=self.env.layout_idx,
+                                         n_layouts=len(layout) if isinstance(layout, LayoutSet) else 1)
+            for grp in self.groups:
+                grp.ep = self.episodes.view(grp.g * grp.env.E, grp.env.E) if len(parts) > 1 else self.episodes
         self.samp = dict(s=torch.zeros(batch * OBS_WORDS, dtype=torch.int32, device=self.device),
                          s2=torch.zeros(batch * OBS_WORDS, dtype=torch.int32, device=self.device),
                          a=torch.zeros(batch, dtype=torch.int32, device=self.device),
@@ -479,6 +493,8 @@ class VecTrainer:
                 grp.env.step(grp.actions, order=False, auto_reset=True)
                 if ev_env is not None and grp.g == 0:
                     ev_env[1].record(grp.main)
+                if grp.ep is not None:  # before this stream's next step overwrites reward / done / counts
+                    grp.ep.update(grp.env.reward, grp.env.done, grp.env.counts)
                 if fused:
                     # the strict schedule's learn batch drawn in the same launch (the ring after this push)
                     smp = None
@@ -503,7 +519,10 @@ class VecTrainer:
                 side.wait_stream(caller)
                 for grp in G:
                     side.wait_event(grp.ev_push)
-                self.env.reset(mask=extra_reset & ~self.env.done.bool())
+                mask = extra_reset & ~self.env.done.bool()
+                self.env.reset(mask=mask)
+                if self.episodes is not None:  # after every group's update (ev_push): their partial episodes end here
+                    self.episodes.discard(mask)
                 if len(G) > 1:
                     for grp in G:  # the orders again, with the reset envs' new classes
                         grp.env.compute_orders(perm=grp.perm)
@@ -537,6 +556,15 @@ class VecTrainer:
                     self.ev_learned.record(m)
         self._presampled = False
         self.t += 1
+
+    def episode_summary(self, clear: bool = True) -> dict:
+        """sync(), then the statistics of the episodes finished since the last clearing call
+        (EpisodeStats.summary: episodes, return_mean / _std / _min / _max, length_mean, evac_rate,
+        death_rate, per_layout rows for a LayoutSet). Waits for the device; not part of a step."""
+        if self.episodes is None:
+            raise RuntimeError("episode_summary: the trainer was made with episode_stats=False")
+        self.sync()
+        return self.episodes.summary(clear=clear)
 
     def sync(self):
         """Make the current stream wait for all work of the steps so far. step() runs on

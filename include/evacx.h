@@ -611,6 +611,71 @@ int evx_qmix_loss(const float *Q, const float *Qt, int32_t A, const int32_t *act
                   float *dQ, float *mix_grad, float *loss, float *part, float *zero, int64_t nzero, void *stream);
 const char *evx_qmix_last_error(void);
 
+/* ---- Episode statistics (csrc/episode.hip). The reference's training loop adds each step's
+ * reward into total_reward on the host and logs the episode's return, evacuation_rate and
+ * death_rate when done comes back (runners/train_dqn.py:129-161; evaluate_strategies.py:47-77
+ * does the same per strategy). The vectorised envs reset inside the step launch, so the same
+ * bookkeeping runs on the device from the step's outputs. Every array is per env ([E] unless
+ * noted): an env's numbers depend on its own step sequence only, never on the order in which
+ * envs, groups or streams run, and nothing is added with float atomics. A part of the envs
+ * (VecEnv.split) is a descriptor whose pointers are offset to its first env and whose E is
+ * its env count. */
+typedef struct {
+    int32_t E;
+    int32_t tab_slots;     /* K: episodes per env the episode table holds (0 = no table) */
+    /* the episode in progress */
+    double *ret;           /* sum of its rewards so far, f64 adds in step order */
+    int32_t *len;          /* its steps so far */
+    /* the window: episodes folded since the last clear */
+    int64_t *w_n, *w_len, *w_evac, *w_dead; /* count, sum of lengths, of evacuated, of dead */
+    double *w_ret, *w_ret2;                 /* sum of returns, of squared returns (episode order) */
+    double *w_min, *w_max;                  /* smallest / largest return (+inf / -inf when empty) */
+    /* the last finished episode */
+    double *last_ret;
+    int32_t *last_len, *last_evac, *last_dead;
+    int64_t *n_total;      /* episodes finished since evx_episode_init (never cleared) */
+    /* optional episode table [E][K]: the env's episode with lifetime index k < K in slot k */
+    double *tab_ret;
+    int32_t *tab_len, *tab_evac, *tab_dead;
+} evx_episodes;
+
+/* One row of evx_episode_reduce: the window summed over a set of envs. */
+typedef struct {
+    int64_t episodes, len_sum, evac_sum, dead_sum;
+    double ret_sum, ret2_sum, ret_min, ret_max;
+    int64_t remaining;     /* envs of the row whose lifetime count is < cap (0 when cap <= 0) */
+    int64_t no_episode;    /* envs of the row that have not finished an episode yet */
+} evx_episode_row;
+
+/* envs one pass of a reduce workgroup covers (its thread count) */
+#define EVX_EPISODE_REDUCE_SPAN 1024
+
+/* Everything zeroed: no episode in progress, empty window (min +inf, max -inf), lifetime 0. */
+int evx_episode_init(const evx_episodes *ep, void *stream);
+/* One step of every env of ep, one launch: ret += reward[e] (the reference's total_reward +=
+ * reward), len += 1; where done[e], the episode is folded into the window (w_ret2 += ret * ret,
+ * not contracted), the last-episode slots and the table, with counts[2e], counts[2e + 1] its
+ * terminal evacuated and dead (evx_step_out.counts), the lifetime count is bumped and ret, len
+ * start again from 0. cap > 0: an episode whose lifetime index (n_total before the bump) is >= cap
+ * stays out of the window, so the window holds exactly the first cap episodes of every env. */
+int evx_episode_update(const evx_episodes *ep, const double *reward, const uint8_t *done, const int32_t *counts,
+                       int64_t cap, void *stream);
+/* Drops the episode in progress (ret = 0, len = 0) of the envs with mask[e] != 0 (NULL: all):
+ * for envs reset from outside the step (evx_env_reset). */
+int evx_episode_discard(const evx_episodes *ep, const uint8_t *mask, void *stream);
+/* The window summed over envs into out[0 .. n_layouts]: row l < n_layouts over the envs with
+ * layout_idx[e] == l (NULL: every env is of layout 0), row n_layouts over all envs. Integer
+ * fields are exact. The f64 sums of a row are added in one fixed order -- the same bits on every
+ * run and however the updates were sliced: thread t of the row's workgroup (EVX_EPISODE_REDUCE_SPAN
+ * threads) adds the row's envs t, t + SPAN, t + 2 SPAN, ... in ascending order onto 0.0 (envs of
+ * other layouts are skipped), then the thread sums are added pairwise, s[t] = s[t] + s[t + h] for
+ * h = SPAN/2, SPAN/4, ..., 1; the row's sum is s[0]. clear != 0: the per-env window arrays are
+ * emptied by a second launch of the same call; the episode in progress, the last-episode slots,
+ * the table and the lifetime count stay. Any E >= 1. */
+int evx_episode_reduce(const evx_episodes *ep, const int32_t *layout_idx, int32_t n_layouts, int64_t cap,
+                       evx_episode_row *out, int32_t clear, void *stream);
+const char *evx_episode_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,565 @@
+"""Episode statistics on the device (csrc/episode.hip, evacx.episodes), the vector evaluator
+(evacx.evaluate), VecTrainer(episode_stats=True) and the train_vec runner.
+
+The reference everywhere is the numpy fold below (sequential f64 adds per env in step order,
+then per-env window sums in episode order) or the C oracle -- never EpisodeStats itself.
+Per-env numbers must match the fold exactly (f64 fields bit for bit); the summary's f64 sums
+are compared with math.fsum under |got - fsum| <= 64 * 2^-52 * sum|x|, which covers any fixed
+summation tree at these sizes (at most 3 sequential + 10 pairwise adds per sum here)."""
+import csv
+import dataclasses
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from golden_util import ROOT
+
+pytestmark = pytest.mark.gpu
+
+SPAN = 1024  # envs one pass of a reduce workgroup covers (EVX_EPISODE_REDUCE_SPAN)
+# boundary sizes; SPAN + 1 = 1025 is the first E at which a reduce thread adds a second env
+SIZES = [1, 63, 65, SPAN + 1, 2 * SPAN + 5]
+assert 1025 in SIZES
+
+I_FIELDS = ["len", "w_n", "w_len", "w_evac", "w_dead", "last_len", "last_evac", "last_dead", "n_total"]
+F_FIELDS = ["ret", "w_ret", "w_ret2", "w_min", "w_max", "last_ret"]
+
+
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+
+
+class Fold:
+    """The reference: what the reference's loop keeps per episode (total_reward += reward,
+    runners/train_dqn.py:109), for E envs at once; numpy's elementwise f64 add / multiply are
+    the IEEE operations, one per env and step, in step order."""
+
+    def __init__(self, E, cap=0, table=0):
+        self.E, self.cap = E, cap
+        self.ret = np.zeros(E)
+        self.len = np.zeros(E, np.int64)
+        self.last_ret = np.zeros(E)
+        self.last_len, self.last_evac, self.last_dead = (np.zeros(E, np.int64) for _ in range(3))
+        self.n_total = np.zeros(E, np.int64)
+        self.tab = [[] for _ in range(E)] if table else None
+        self.table = table
+        self.clear()
+
+    def clear(self):
+        E = self.E
+        self.w_n, self.w_len, self.w_evac, self.w_dead = (np.zeros(E, np.int64) for _ in range(4))
+        self.w_ret, self.w_ret2 = np.zeros(E), np.zeros(E)
+        self.w_min, self.w_max = np.full(E, np.inf), np.full(E, -np.inf)
+
+    def step(self, reward, done, counts):
+        reward = np.asarray(reward, np.float64)
+        done = np.asarray(done).astype(bool)
+        counts = np.asarray(counts, np.int64).reshape(self.E, 2)
+        self.ret = self.ret + reward
+        self.len = self.len + 1
+        for e in np.nonzero(done)[0]:
+            r, n = self.ret[e], self.len[e]
+            if self.cap <= 0 or self.n_total[e] < self.cap:
+                self.w_n[e] += 1
+                self.w_len[e] += n
+                self.w_evac[e] += counts[e, 0]
+                self.w_dead[e] += counts[e, 1]
+                self.w_ret[e] = self.w_ret[e] + r
+                self.w_ret2[e] = self.w_ret2[e] + r * r
+                self.w_min[e] = min(self.w_min[e], r)
+                self.w_max[e] = max(self.w_max[e], r)
+            self.last_ret[e], self.last_len[e] = r, n
+            self.last_evac[e], self.last_dead[e] = counts[e]
+            if self.tab is not None and self.n_total[e] < self.table:
+                self.tab[e].append((r, int(n), int(counts[e, 0]), int(counts[e, 1])))
+            self.n_total[e] += 1
+            self.ret[e], self.len[e] = 0.0, 0
+
+    def discard(self, mask):
+        m = np.asarray(mask).astype(bool)
+        self.ret[m], self.len[m] = 0.0, 0
+
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, np.float64)).view(np.int64)
+
+
+def _check_per_env(st, fold, lo=0, what=""):
+    torch.cuda.synchronize()
+    n = fold.E
+    for k in I_FIELDS:
+        got = getattr(st, k)[lo:lo + n].cpu().numpy()
+        assert np.array_equal(got, getattr(fold, k)), (what, k)
+    for k in F_FIELDS:
+        got = getattr(st, k)[lo:lo + n].cpu().numpy()
+        assert np.array_equal(_bits(got), _bits(getattr(fold, k))), (what, k)
+
+
+def _check_row(row, fold, envs, P, cap=0, what=""):
+    """One summary row against the fold over `envs` (indices)."""
+    e = np.asarray(envs, np.int64)
+    n = int(fold.w_n[e].sum())
+    assert row["episodes"] == n, what
+    assert row["length_sum"] == int(fold.w_len[e].sum()), what
+    assert row["evacuated"] == int(fold.w_evac[e].sum()), what
+    assert row["dead"] == int(fold.w_dead[e].sum()), what
+    assert row["remaining"] == (int((fold.n_total[e] < cap).sum()) if cap > 0 else 0), what
+    assert row["no_episode"] == int((fold.n_total[e] == 0).sum()), what
+    for key, arr in (("return_sum", fold.w_ret[e]), ("return_sq_sum", fold.w_ret2[e])):
+        ref, mass = math.fsum(arr.tolist()), math.fsum(np.abs(arr).tolist())
+        print(f"{what} {key}: got {row[key]!r} fsum {ref!r} |diff| {abs(row[key] - ref):.3e} "
+              f"bound {64 * 2.0 ** -52 * mass:.3e}")
+        assert abs(row[key] - ref) <= 64 * 2.0 ** -52 * mass, (what, key, row[key], ref)
+    if n == 0:
+        for k in ("return_mean", "return_std", "return_min", "return_max", "length_mean", "evac_rate", "death_rate"):
+            assert row[k] is None, (what, k)
+        return
+    assert row["return_min"] == fold.w_min[e].min() and row["return_max"] == fold.w_max[e].max(), what
+    assert row["return_mean"] == row["return_sum"] / n and row["length_mean"] == row["length_sum"] / n, what
+    assert row["evac_rate"] == row["evacuated"] / (n * P) and row["death_rate"] == row["dead"] / (n * P), what
+    var = row["return_sq_sum"] / n - row["return_mean"] * row["return_mean"]
+    assert row["return_std"] == math.sqrt(max(var, 0.0)), what
+
+
+def _synthetic(E, steps, seed, p_done=0.1, P=150):
+    rng = np.random.RandomState(seed)
+    rew = rng.standard_normal((steps, E)) * np.exp(rng.uniform(-3, 6, size=(steps, E)))
+    done = (rng.rand(steps, E) < p_done).astype(np.uint8)
+    evac = rng.randint(0, P + 1, size=(steps, E))
+    dead = rng.randint(0, P + 1, size=(steps, E)) % (P + 1 - evac)
+    counts = np.stack([evac, dead], -1).astype(np.int32)
+    return rew, done, counts
+
+
+def _dev(rew, done, counts):
+    return (torch.from_numpy(rew).cuda(), torch.from_numpy(done).cuda(),
+            torch.from_numpy(np.ascontiguousarray(counts)).cuda())
+
+
+def _snapshot(st):
+    torch.cuda.synchronize()
+    return {k: getattr(st, k).clone() for k in I_FIELDS + F_FIELDS}
+
+
+# ------------------------------------------------------------------ 1. boundary sizes
+@pytest.mark.parametrize("E", SIZES)
+def test_boundary_sizes_match_the_fold(E):
+    _need_gpu()
+    from evacx.episodes import REDUCE_SPAN, EpisodeStats
+    assert REDUCE_SPAN == SPAN
+    P, steps = 150, 50
+    rew, done, counts = _synthetic(E, steps, seed=100 + E)
+    fold = Fold(E)
+    for t in range(steps):
+        fold.step(rew[t], done[t], counts[t])
+    assert E < 63 or fold.w_n.sum() > 0
+    R, D, Cn = _dev(rew, done, counts)
+    cut = E // 3  # the sliced run: envs [0, cut) and [cut, E) updated by two calls
+
+    def run(sliced):
+        st = EpisodeStats(E, "cuda", P)
+        parts = [st] if not sliced or cut == 0 else [st.view(0, cut), st.view(cut, E - cut)]
+        for t in range(steps):
+            lo = 0
+            for p in parts:
+                p.update(R[t, lo:lo + p.E], D[t, lo:lo + p.E], Cn[t, lo:lo + p.E].reshape(-1))
+                lo += p.E
+        snap = _snapshot(st)
+        s = st.summary(clear=False)
+        return st, snap, s, st.rows.cpu().clone()
+
+    st, snap, s, rows = run(False)
+    _check_per_env(st, fold, what=f"E={E}")
+    _check_row(s, fold, range(E), P, what=f"E={E} all")
+    assert len(s["per_layout"]) == 1
+    _check_row(s["per_layout"][0], fold, range(E), P, what=f"E={E} layout 0")
+    for sliced in (False, True):  # a second run, and a run updated in two slices: identical bits
+        st2, snap2, s2, rows2 = run(sliced)
+        for k in snap:
+            assert torch.equal(snap[k].view(torch.int64) if snap[k].dtype == torch.float64 else snap[k],
+                               snap2[k].view(torch.int64) if snap2[k].dtype == torch.float64 else snap2[k]), k
+        assert torch.equal(rows, rows2), ("summary bits", sliced)
+
+
+# ------------------------------------------------------------------ 2. clear
+def test_clear_splits_windows_and_keeps_spanning_episodes_whole():
+    _need_gpu()
+    from evacx.episodes import EpisodeStats
+    E, P = 65, 150
+    rew, done, counts = _synthetic(E, 50, seed=7)
+    R, D, Cn = _dev(rew, done, counts)
+    st = EpisodeStats(E, "cuda", P)
+    fold, whole = Fold(E), Fold(E)
+    partial, first_finish = None, {}
+    for t in range(50):
+        st.update(R[t], D[t], Cn[t].reshape(-1))
+        fold.step(rew[t], done[t], counts[t])
+        whole.step(rew[t], done[t], counts[t])
+        if t >= 25:
+            for e in np.nonzero(done[t])[0]:
+                first_finish.setdefault(int(e), t)
+        if t == 24:
+            s1 = st.summary(clear=True)
+            _check_row(s1, fold, range(E), P, what="window 1")
+            assert s1["episodes"] > 0
+            partial = fold.len.copy()  # episodes in progress at the boundary
+            fold.clear()
+            _check_per_env(st, fold, what="after clear")  # in progress, last and lifetime untouched
+    _check_per_env(st, fold, what="window 2")
+    s2 = st.summary(clear=True)
+    _check_row(s2, fold, range(E), P, what="window 2")
+    assert np.array_equal(st.n_total.cpu().numpy(), whole.n_total)
+    assert s1["episodes"] + s2["episodes"] == int(whole.n_total.sum())
+    # an episode that spans the boundary lands whole in the second window
+    span = [e for e, t in first_finish.items() if partial[e] > 0 and fold.w_n[e] == 1]
+    assert span
+    w_len = st.w_len.cpu().numpy()  # (already cleared on the device: compare the fold's)
+    for e in span:
+        assert fold.w_len[e] == partial[e] + (first_finish[e] - 24)
+    assert (w_len == 0).all() and st.summary(clear=False)["episodes"] == 0
+
+
+# ------------------------------------------------------------------ 3. cap and discard
+def test_cap_counts_the_first_episodes_only_and_discard_drops_partials():
+    _need_gpu()
+    from evacx.episodes import EpisodeStats
+    E, P, cap, steps = 65, 150, 2, 80
+    rew, done, counts = _synthetic(E, steps, seed=11, p_done=0.2)
+    R, D, Cn = _dev(rew, done, counts)
+    st = EpisodeStats(E, "cuda", P, cap=cap, record=cap)
+    fold = Fold(E, cap=cap, table=cap)
+    remaining = []
+    for t in range(steps):
+        st.update(R[t], D[t], Cn[t].reshape(-1))
+        fold.step(rew[t], done[t], counts[t])
+        if t % 10 == 9:
+            s = st.summary(clear=False)
+            assert s["remaining"] == int((fold.n_total < cap).sum())
+            remaining.append(s["remaining"])
+    assert remaining[0] > 0 and remaining[-1] == 0 and remaining == sorted(remaining, reverse=True)
+    assert (fold.n_total > cap).any()  # later episodes happened and stayed out
+    _check_per_env(st, fold, what="cap")
+    assert (st.w_n.cpu().numpy() == cap).all()
+    s = st.summary(clear=False)
+    _check_row(s, fold, range(E), P, cap=cap, what="cap")
+    assert s["episodes"] == cap * E
+    # the sums are those of each env's first two episodes, from the episode list itself
+    for e in range(E):
+        r0, r1 = fold.tab[e][0][0], fold.tab[e][1][0]
+        assert _bits(st.w_ret[e].item()) == _bits((0.0 + r0) + r1)
+        assert st.w_len[e].item() == fold.tab[e][0][1] + fold.tab[e][1][1]
+        assert np.array_equal(_bits(st.tab_ret[e].cpu().numpy()), _bits([r0, r1]))
+        assert st.tab_len[e].tolist() == [fold.tab[e][0][1], fold.tab[e][1][1]]
+        assert st.tab_evac[e].tolist() == [fold.tab[e][0][2], fold.tab[e][1][2]]
+        assert st.tab_dead[e].tolist() == [fold.tab[e][0][3], fold.tab[e][1][3]]
+    # discard: masked envs lose their partial episode, everything else keeps its bits
+    assert (fold.len > 0).sum() > 10
+    mask = np.random.RandomState(5).rand(E) < 0.5
+    assert (mask & (fold.len > 0)).any() and (~mask & (fold.len > 0)).any()
+    st.discard(torch.from_numpy(mask).cuda())
+    fold.discard(mask)
+    _check_per_env(st, fold, what="discard")
+    st.discard()  # no mask: all
+    fold.discard(np.ones(E, bool))
+    _check_per_env(st, fold, what="discard all")
+
+
+def test_update_rejects_wrong_buffers_before_launching():
+    _need_gpu()
+    from evacx.episodes import EpisodeStats
+    st = EpisodeStats(8, "cuda", 150)
+    r = torch.zeros(8, dtype=torch.float64, device="cuda")
+    d = torch.zeros(8, dtype=torch.uint8, device="cuda")
+    c = torch.zeros(16, dtype=torch.int32, device="cuda")
+    for bad in [(r.float(), d, c), (r, d.bool(), c), (r, d, c.long()), (r[:7], d, c), (r, d, c[:8]),
+                (r.cpu(), d, c)]:
+        with pytest.raises(ValueError):
+            st.update(*bad)
+    with pytest.raises(ValueError):
+        st.discard(torch.zeros(7, dtype=torch.uint8, device="cuda"))
+    with pytest.raises(ValueError):
+        st.view(4, 5)
+    st.update(r, d, c)
+    assert st.summary()["episodes"] == 0 and st.len.tolist() == [1] * 8
+
+
+# ------------------------------------------------------------------ 4. real env
+def _small_layout(P=150):
+    from evacx.env import DeviceLayout
+    from evacx.layout import build_tables, synthetic
+    tables = build_tables(synthetic(36, 30, 1))
+    return tables, DeviceLayout(tables, P)
+
+
+def test_real_env_random_actions_match_the_fold():
+    _need_gpu()
+    from evacx.env import VecEnv
+    from evacx.episodes import EpisodeStats
+    P, E, steps = 150, 8, 400
+    tables, lay = _small_layout(P)
+    env = VecEnv(lay, E)
+    env.seed([1234 + i for i in range(E)])
+    env.reset()
+    st = EpisodeStats(E, lay.device, P)
+    fold = Fold(E)
+    acts = torch.from_numpy(np.random.RandomState(3).randint(0, 5, size=(steps, E * lay.R)).astype(np.int32)).cuda()
+    for t in range(steps):
+        env.step(acts[t], auto_reset=True)
+        st.update(env.reward, env.done, env.counts)
+        fold.step(env.reward.cpu().numpy(), env.done.cpu().numpy(), env.counts.cpu().numpy())
+    env.check_err()
+    assert fold.n_total.sum() >= 30 and fold.n_total.min() >= 2, fold.n_total
+    _check_per_env(st, fold, what="real env")
+    _check_row(st.summary(clear=False), fold, range(E), P, what="real env")
+
+
+# ------------------------------------------------------------------ 5. per layout
+def test_per_layout_rows_match_the_fold_over_each_layouts_envs():
+    _need_gpu()
+    from evacx.env import DeviceLayout, LayoutSet, VecEnv
+    from evacx.episodes import EpisodeStats
+    from evacx.layout import build_tables, synthetic
+    s0 = synthetic(24, 20, 4)
+    s1 = dataclasses.replace(s0, barriers=(((5, 5), (8, 9)),), exit=(24, 3))
+    P, E, steps = 380, 8, 240
+    ls = LayoutSet([DeviceLayout(build_tables(s), P) for s in (s0, s1)])
+    layout_of = [i % 2 for i in range(E)]
+    env = VecEnv(ls, E, layout_of=layout_of)
+    env.seed([500 + i for i in range(E)])
+    env.reset()
+    st = EpisodeStats(E, ls.device, P, layout_idx=env.layout_idx, n_layouts=2)
+    fold = Fold(E)
+    acts = torch.from_numpy(np.random.RandomState(4).randint(0, 5, size=(steps, E * ls.R)).astype(np.int32)).cuda()
+    for t in range(steps):
+        env.step(acts[t], auto_reset=True)
+        st.update(env.reward, env.done, env.counts)
+        fold.step(env.reward.cpu().numpy(), env.done.cpu().numpy(), env.counts.cpu().numpy())
+    env.check_err()
+    s = st.summary(clear=False)
+    assert len(s["per_layout"]) == 2
+    for l in range(2):
+        envs = [e for e in range(E) if layout_of[e] == l]
+        _check_row(s["per_layout"][l], fold, envs, P, what=f"layout {l}")
+        assert s["per_layout"][l]["episodes"] >= 1
+    _check_row(s, fold, range(E), P, what="all")
+    assert s["per_layout"][0]["episodes"] + s["per_layout"][1]["episodes"] == s["episodes"]
+
+
+# ------------------------------------------------------------------ 6. evaluator
+def test_evaluate_constant_action_matches_the_oracle_episode_by_episode():
+    _need_gpu()
+    from evacx.evaluate import evaluate
+    from oracle import oracle as orc
+    P, E, K, action = 150, 8, 2, 1
+    tables, lay = _small_layout(P)
+    ev = evaluate(lay, E, K, action, seed_base=1234)
+    assert ev["episodes"] == E * K == 16 and ev["remaining"] == 0
+    olay = orc.Layout.from_tables(tables, P)
+    tab = {k: ev["per_env"][k].cpu().numpy() for k in ("tab_ret", "tab_len", "tab_evac", "tab_dead")}
+    fold = Fold(E, cap=K, table=K)
+    for i in range(E):
+        oe = orc.Env(olay, thmap=False)
+        oe.seed(1234 + i)
+        oe.reset()
+        for k in range(K):
+            total, n, done = 0.0, 0, False
+            while not done:
+                _, r, done = oe.step([action] * lay.R)
+                total += r  # the reference's total_reward += reward
+                n += 1
+                assert n <= 1200
+            assert _bits(tab["tab_ret"][i, k]) == _bits(total), (i, k, tab["tab_ret"][i, k], total)
+            assert tab["tab_len"][i, k] == n, (i, k)
+            assert tab["tab_evac"][i, k] == oe.scal[2] and tab["tab_dead"][i, k] == oe.scal[3], (i, k)
+            fold.w_n[i] += 1
+            fold.w_len[i] += n
+            fold.w_evac[i] += oe.scal[2]
+            fold.w_dead[i] += oe.scal[3]
+            fold.w_ret[i] = fold.w_ret[i] + total
+            fold.w_ret2[i] = fold.w_ret2[i] + total * total
+            fold.w_min[i], fold.w_max[i] = min(fold.w_min[i], total), max(fold.w_max[i], total)
+            fold.n_total[i] += 1
+            oe.reset()
+    fold.n_total = ev["per_env"]["n_total"].cpu().numpy()  # lifetime counts run past the cap
+    assert (fold.n_total >= K).all()
+    _check_row(ev, fold, range(E), P, cap=K, what="evaluate")
+    assert np.array_equal(_bits(ev["per_env"]["w_ret"].cpu().numpy()), _bits(fold.w_ret))
+
+
+def test_evaluate_greedy_is_reproducible_and_matches_a_hand_loop():
+    _need_gpu()
+    from evacx.env import VecEnv
+    from evacx.evaluate import evaluate
+    from evacx.qnet import Learner
+    P, E, K = 150, 8, 2
+    tables, lay = _small_layout(P)
+    lr = Learner(kind="mlp", precision="f32", seed=5)
+    ev1 = evaluate(lay, E, K, "greedy", learner=lr)
+    ev2 = evaluate(lay, E, K, "greedy", learner=lr)
+    keys = [k for k in ev1 if k not in ("per_env", "per_layout")]
+    assert {k: ev1[k] for k in keys} == {k: ev2[k] for k in keys} and ev1["episodes"] == E * K
+    for k in ev1["per_env"]:
+        assert torch.equal(ev1["per_env"][k], ev2["per_env"][k]), k
+    # by hand: eval-mode act (no dropout, epsilon 0) + auto-reset step, folded on the host
+    env = VecEnv(lay, E)
+    env.seed([1234 + i for i in range(E)])
+    env.reset()
+    n = E * lay.R
+    a = torch.zeros(n, dtype=torch.int32, device="cuda")
+    fold = Fold(E, cap=K, table=K)
+    for t in range(ev1["steps"]):
+        lr.fast.act(lay.c, env.obs, n, drop=None, actions=a, epsilon=0.0)
+        env.step(a, auto_reset=True)
+        fold.step(env.reward.cpu().numpy(), env.done.cpu().numpy(), env.counts.cpu().numpy())
+    assert (fold.n_total >= K).all()
+    assert np.array_equal(ev1["per_env"]["n_total"].cpu().numpy(), fold.n_total)
+    for j, name in enumerate(("tab_ret", "tab_len", "tab_evac", "tab_dead")):
+        ref = np.array([[fold.tab[e][k][j] for k in range(K)] for e in range(E)])
+        got = ev1["per_env"][name].cpu().numpy()
+        assert np.array_equal(_bits(got), _bits(ref)) if j == 0 else np.array_equal(got, ref), name
+    _check_row(ev1, fold, range(E), P, cap=K, what="greedy")
+
+
+def test_evaluate_random_policy_and_step_guard():
+    _need_gpu()
+    from evacx.evaluate import evaluate
+    P, E = 150, 8
+    tables, lay = _small_layout(P)
+    ev = evaluate(lay, E, 1, "random", seed=9)
+    assert ev["episodes"] == E and ev["remaining"] == 0 and ev["no_episode"] == 0
+    ev2 = evaluate(lay, E, 1, "random", seed=9)
+    assert torch.equal(ev["per_env"]["tab_ret"], ev2["per_env"]["tab_ret"])
+    with pytest.raises(RuntimeError):
+        evaluate(lay, E, 1, "random", seed=9, max_steps=5)  # no episode is that short
+
+
+# ------------------------------------------------------------------ 7. trainer
+def _trainer(**kw):
+    from evacx.env import DeviceLayout
+    from evacx.layout import build_tables, synthetic
+    from evacx.trainer import VecTrainer
+    lay = DeviceLayout(build_tables(synthetic(64, 64, 4)), 300)
+    args = dict(batch=256, replay_capacity=4096, epsilon=1.0, epsilon_decay=1.0, target_every=50)
+    args.update(kw)
+    return VecTrainer(lay, 64, **args)
+
+
+_RUN = {}
+
+
+def _trainer_run():
+    """200 steps of a stats-on trainer (one group) with the host fold of env.reward / done / counts
+    read after sync() each step: shared by the trainer tests."""
+    if not _RUN:
+        tr = _trainer(episode_stats=True)
+        fold = Fold(64)
+        for _ in range(200):
+            tr.step()
+            tr.sync()
+            torch.cuda.current_stream().synchronize()
+            fold.step(tr.env.reward.cpu().numpy(), tr.env.done.cpu().numpy(), tr.env.counts.cpu().numpy())
+        tr.env.check_err()
+        _RUN.update(tr=tr, fold=fold, snap=_snapshot(tr.episodes), summary=tr.episode_summary(clear=False),
+                    rows=tr.episodes.rows.cpu().clone())
+    return _RUN
+
+
+def test_trainer_episode_summary_matches_the_fold():
+    _need_gpu()
+    run = _trainer_run()
+    tr, fold = run["tr"], run["fold"]
+    assert fold.n_total.min() >= 1, fold.n_total  # episodes are 78-152 steps here: every env finished one
+    _check_per_env(tr.episodes, fold, what="trainer")
+    _check_row(run["summary"], fold, range(64), 300, what="trainer")
+    assert run["summary"]["episodes"] == int(fold.n_total.sum())
+    s = tr.episode_summary()  # clears
+    assert s["episodes"] == run["summary"]["episodes"] and tr.episode_summary()["episodes"] == 0
+
+
+def test_trainer_two_groups_give_the_same_bits():
+    _need_gpu()
+    run = _trainer_run()
+    tr2 = _trainer(episode_stats=True, groups=2)
+    for _ in range(200):
+        tr2.step()
+    s2 = tr2.episode_summary(clear=False)
+    tr2.env.check_err()
+    snap2 = _snapshot(tr2.episodes)
+    for k, v in run["snap"].items():
+        same = torch.equal(v.view(torch.int64), snap2[k].view(torch.int64)) if v.dtype == torch.float64 else \
+            torch.equal(v, snap2[k])
+        assert same, k
+    assert torch.equal(run["rows"], tr2.episodes.rows.cpu())
+    assert {k: v for k, v in s2.items() if k != "per_layout"} == \
+        {k: v for k, v in run["summary"].items() if k != "per_layout"}
+
+
+def test_trainer_stats_do_not_change_the_trajectory_and_off_raises():
+    _need_gpu()
+    on, off = _trainer(episode_stats=True, epsilon=0.5), _trainer(epsilon=0.5)
+    assert off.episodes is None and all(g.ep is None for g in off.groups)
+    for _ in range(20):
+        on.step()
+        off.step()
+    on.sync()
+    off.sync()
+    torch.cuda.synchronize()
+    assert torch.equal(on.actions, off.actions)
+    assert torch.equal(on.learner.online.flat.view(torch.int32), off.learner.online.flat.view(torch.int32))
+    assert torch.equal(on.env.reward.view(torch.int64), off.env.reward.view(torch.int64))
+    with pytest.raises(RuntimeError):
+        off.episode_summary()
+    assert on.episode_summary()["no_episode"] == 64  # 20 steps: nothing finished yet
+
+
+def test_trainer_extra_reset_discards_the_masked_partial_episodes():
+    _need_gpu()
+    tr = _trainer(episode_stats=True)
+    for _ in range(10):
+        tr.step()
+    tr.sync()
+    torch.cuda.synchronize()
+    before = _snapshot(tr.episodes)
+    assert (before["len"] == 10).all()
+    mask = torch.zeros(64, dtype=torch.bool, device="cuda")
+    mask[::3] = True
+    tr.step(extra_reset=mask)
+    tr.sync()
+    torch.cuda.synchronize()
+    assert not tr.env.done.any()
+    ret, ln = tr.episodes.ret.cpu().numpy(), tr.episodes.len.cpu().numpy()
+    m = mask.cpu().numpy()
+    assert (ln[m] == 0).all() and (ret[m] == 0.0).all()
+    want = before["ret"].cpu().numpy() + tr.env.reward.cpu().numpy()
+    assert (ln[~m] == 11).all() and np.array_equal(_bits(ret[~m]), _bits(want[~m]))
+    assert tr.episode_summary()["episodes"] == 0
+
+
+# ------------------------------------------------------------------ 8. runner
+def test_train_vec_runner_logs_and_saves(tmp_path):
+    _need_gpu()
+    cfg = tmp_path / "small.yaml"
+    cfg.write_text("env:\n  width: 36\n  height: 30\n  fire_zones: [[18, 14]]\n  exit_location: [36, 15]\n"
+                   "  num_people: 40\nagent:\n  gamma: 0.99\n  epsilon: 1.0\n  epsilon_min: 0.02\n"
+                   "  epsilon_decay: 0.9995\n  learning_rate: 0.0001\n  batch_size: 32\n  target_update_freq: 20\n"
+                   "  memory_size: 4096\nsave_path: \"unused\"\n")
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, "-m", "Louvre_Evacuation.runners.train_vec", "--config", str(cfg),
+                        "--envs", "64", "--steps", "60", "--log-every", "20", "--qnet", "mlp", "--out", str(out)],
+                       cwd=os.path.join(ROOT, "dqn-marl_amd"), capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rows = list(csv.reader(open(out / "training_log.csv")))
+    assert rows[0] == ["step", "episodes", "reward", "evac_rate", "death_rate", "length", "loss", "epsilon"]
+    assert len(rows) == 4 and [row[0] for row in rows[1:]] == ["20", "40", "60"]
+    assert all(len(row) == 8 for row in rows)
+    ck = torch.load(out / "dqn_model.pth", map_location="cpu", weights_only=True)
+    assert set(ck) == {"q_network", "target_network", "optimizer", "epsilon", "steps"}
+    assert list(ck["q_network"]) == ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias"]
+    assert ck["steps"] > 0 and 0.0 < ck["epsilon"] <= 1.0
+    assert r.stdout.count("step ") >= 3
