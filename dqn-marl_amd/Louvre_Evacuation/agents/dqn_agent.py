@@ -151,8 +151,12 @@ class DQNAgent:
         # draws torch's generator, which a counter-based Philox cannot follow draw for draw)
         seed = (int(torch.initial_seed()) * 1000003 + _AGENTS) & 0x7FFFFFFF if config.get("seed") is None \
             else int(config["seed"])
+        # optional keys beyond the reference's: Double-Q targets and the Huber loss (absent: the
+        # reference's max target and MSE); the target copy stays with the runners
         self._learner = Learner(kind="conv", device=self.device, lr=self.learning_rate, gamma=self.gamma,
-                                max_norm=1.0, precision="f32", hidden=hidden, actions=action_size, seed=seed)
+                                max_norm=1.0, precision="f32", hidden=hidden, actions=action_size, seed=seed,
+                                double_q=bool(config.get("double_dqn", False)), loss=config.get("loss", "mse"),
+                                huber_delta=float(config.get("huber_delta", 1.0)))
         # initial weights as the reference draws them: q_network then target_network
         # (agents/dqn_agent.py:83-84), each from torch's global generator in module order; the
         # target's draw is consumed and then overwritten by update_target_network (:95)

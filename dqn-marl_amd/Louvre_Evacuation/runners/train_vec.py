@@ -11,6 +11,10 @@ target_network, optimizer, epsilon, steps: agents/dqn_agent.py:174-191), so a ``
 conv`` file loads through the drop-in ``DQNAgent.load``. ``--eval-episodes N`` ends with
 a greedy evaluation (evacx.evaluate) of N episodes per env.
 
+``--double-q``, ``--loss huber`` (``--huber-delta``) and ``--target-tau`` turn on the
+learner's Double-Q targets, Huber loss and soft target updates (defaults from the optional
+``agent:`` keys ``double_dqn``, ``loss``, ``huber_delta``, ``target_tau`` of the config).
+
 Usage: python -m Louvre_Evacuation.runners.train_vec --envs 4096 --steps 2000   (from dqn-marl_amd/)
 """
 import argparse
@@ -41,7 +45,28 @@ def parse_args(argv=None):
     ap.add_argument("--eval-envs", type=int, default=None, help="envs of that evaluation (default: --envs)")
     ap.add_argument("--batch", type=int, default=None, help="learn batch (default: max(256, the config's batch_size))")
     ap.add_argument("--seed", type=int, default=0)
+    # defaults of the next four: the config's optional agent keys (td_options), else off
+    ap.add_argument("--double-q", action=argparse.BooleanOptionalAction, default=None,
+                    help="Double-Q targets (config: agent.double_dqn)")
+    ap.add_argument("--loss", choices=["mse", "huber"], default=None, help="TD loss (config: agent.loss; mse)")
+    ap.add_argument("--huber-delta", type=float, default=None, help="config: agent.huber_delta; 1.0")
+    ap.add_argument("--target-tau", type=float, default=None,
+                    help="soft target update rate per learn step; 0: the periodic hard copy (config: agent.target_tau)")
     return ap.parse_args(argv)
+
+
+def td_options(args, agent_cfg) -> dict:
+    """The learner's options: a flag given on the command line, else the config's optional
+    agent key, else off. Validated here (no device needed)."""
+    from evacx.qnet import validate_td_options
+
+    def pick(flag, key, default):
+        return flag if flag is not None else agent_cfg.get(key, default)
+    o = dict(double_q=bool(pick(args.double_q, "double_dqn", False)), loss=str(pick(args.loss, "loss", "mse")),
+             huber_delta=float(pick(args.huber_delta, "huber_delta", 1.0)),
+             target_tau=float(pick(args.target_tau, "target_tau", 0.0)))
+    validate_td_options(o["loss"], o["huber_delta"], o["target_tau"])
+    return o
 
 
 def checkpoint(tr) -> dict:
@@ -78,15 +103,19 @@ def train_vec(args):
     device = torch.device("cuda", torch.cuda.current_device())
     lay = DeviceLayout(build_tables(spec), int(ec["num_people"]), device=device)
     batch = args.batch or max(256, int(ac.get("batch_size", 32)))
+    opts = td_options(args, ac)
     capacity = 1 << max(10, (max(int(ac.get("memory_size", 50000)), 4 * batch, 2 * args.envs * lay.R) - 1).bit_length())
     tr = VecTrainer(lay, args.envs, kind=args.qnet, batch=batch, replay_capacity=capacity,
                     lr=float(ac.get("learning_rate", 1e-4)), gamma=float(ac.get("gamma", 0.99)),
                     epsilon=float(ac.get("epsilon", 1.0)), epsilon_min=float(ac.get("epsilon_min", 0.02)),
                     epsilon_decay=float(ac.get("epsilon_decay", 0.9995)),
                     target_every=int(ac.get("target_update_freq", 200)), learner_seed=args.seed,
-                    act_table=lay.R % 2 == 0, episode_stats=True)
+                    act_table=lay.R % 2 == 0, episode_stats=True, **opts)
+    tgt = f"soft tau {opts['target_tau']:g}" if opts["target_tau"] > 0 else f"hard copy every {tr.target_every}"
     print(f"env {spec.L}x{spec.W}, {lay.P} people, exit {tuple(spec.exit)}; {args.envs} envs, {args.qnet} Q-network "
-          f"({tr.q_arith}), batch {batch}, replay {capacity} on {device}")
+          f"({tr.q_arith}), batch {batch}, replay {capacity} on {device}; "
+          f"{'double-Q' if opts['double_q'] else 'max'} target, "
+          f"{'huber(%g)' % opts['huber_delta'] if opts['loss'] == 'huber' else 'mse'} loss, target {tgt}")
     best = float("-inf")
     with open(os.path.join(out_dir, "training_log.csv"), "w", newline="") as f:
         log = csv.writer(f)

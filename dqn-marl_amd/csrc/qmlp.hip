@@ -1951,6 +1951,10 @@ struct Bwd {
     const uint8_t* done;
     float gamma;
     float* td_abs;
+    // TD options (evx_td_opts): the bootstrap action per row (NULL: the target's maximum), the
+    // Huber delta (0: the squared error)
+    const int32_t* sel;
+    float delta;
 };
 // net g's view of a blocked grouped backward (see fwd_net; x3: two planes per activation)
 __device__ __forceinline__ Bwd bwd_net(const Bwd& a0, int g) {
@@ -2005,15 +2009,26 @@ __global__ __launch_bounds__(256) void qbwd3_kernel(Bwd a0, int rb) {
 #pragma unroll
             for (int t = 0; t < NACT; t++) dq[t] = 0.f;
             if (i < a.B) {
-                float mx = a.Qt[(size_t)i * NACT];
+                float mx;
+                if (a.sel) {  // Double-Q: the target's value of the given action (clamped into the row)
+                    mx = a.Qt[(size_t)i * NACT + min(max(a.sel[i], 0), NACT - 1)];
+                } else {
+                    mx = a.Qt[(size_t)i * NACT];
 #pragma unroll
-                for (int j = 1; j < NACT; j++) mx = fmaxf(mx, a.Qt[(size_t)i * NACT + j]);
+                    for (int j = 1; j < NACT; j++) mx = fmaxf(mx, a.Qt[(size_t)i * NACT + j]);
+                }
                 const float y = a.rew[i] + a.gamma * mx * (a.done[i] ? 0.f : 1.f);
                 const int ai = a.act[i];
                 const float d = a.Q[(size_t)i * NACT + ai] - y;
                 const float wi = a.w ? a.w[i] : 1.f;
-                part = a.w ? wi * (d * d) : d * d;
-                const float gd = a.w ? wi * (2.f * d) : 2.f * d;
+                float l = d * d, g1 = 2.f * d;
+                if (a.delta > 0.f) {  // Huber: quadratic within delta, linear beyond; the gradient clamped
+                    const float ad = fabsf(d);
+                    l = ad <= a.delta ? 0.5f * (d * d) : a.delta * (ad - 0.5f * a.delta);
+                    g1 = fminf(fmaxf(d, -a.delta), a.delta);
+                }
+                part = a.w ? wi * l : l;
+                const float gd = a.w ? wi * g1 : g1;
 #pragma unroll
                 for (int t = 0; t < NACT; t++) dq[t] = t == ai ? gd / (float)a.B : 0.f;
                 if (a.td_abs) a.td_abs[i] = fabsf(d);
@@ -2667,6 +2682,62 @@ __global__ __launch_bounds__(256) void adam_pack3_kernel(AdamPack a0) {
     }
 }
 
+// Polyak target update t = tau p + (1 - tau) t on the flat target parameters with the target's
+// x3 operand repack in the same launch (evx_qmlp_polyak_pack3): adam_pack3_kernel's thread ->
+// parameter -> operand-tile map with the blend in place of the Adam step (a.p: the target,
+// a.g: the online parameters; m / v / ss unused).
+__device__ __forceinline__ float polyak_one(const AdamPack& a, int i, float tau, float omt) {
+    const float tn = tau * a.g[i] + omt * a.p[i];
+    a.p[i] = tn;
+    return tn;
+}
+__global__ __launch_bounds__(256) void polyak_pack3_kernel(AdamPack a, float tau, float omt) {
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= NPAR) return;
+    if (i < OB1) {
+        const int n = i / K1, rc = i - n * K1;
+        if (rc == CENTRE_COL) return;  // blended by the b1[n] thread
+        const float pn = polyak_one(a, i, tau, omt);
+        const int c = rc / 6, ch = rc - c * 6;
+        if (ch >= 1 && ch <= 4) {
+            const int kk = 4 * c + ch - 1;
+            __bf16 hi, lo;
+            split2(pn, hi, lo);
+            a.w1b[opnd_off(w1_tile(n >> 5, kk >> 5, (kk >> 4) & 1, NKC1X), n, kk)] = hi;
+            a.w1l[opnd_off(w1_tile(n >> 5, kk >> 5, (kk >> 4) & 1, NKC1), n, kk)] = lo;
+            if (ch == 2) {
+                const int kr = K1P + c;
+                a.w1b[opnd_off(w1_tile(n >> 5, kr >> 5, (kr >> 4) & 1, NKC1X), n, kr)] = hi;
+            }
+            if (ch == 1 && a.w1o) {
+                const size_t oo = opnd_off(w1o_tile(n >> 5, c >> 5, (c >> 4) & 1), n, c);
+                a.w1o[oo] = hi;
+                a.w1ol[oo] = lo;
+            }
+        }
+    } else if (i < OW2) {
+        const int n = i - OB1;
+        const float bn = polyak_one(a, i, tau, omt);
+        const float wc = polyak_one(a, n * K1 + CENTRE_COL, tau, omt);
+        a.b1c[n] = bn + wc;
+    } else if (i < OB2) {
+        const float pn = polyak_one(a, i, tau, omt);
+        const int j = i - OW2, n = j / HID, kk = j - n * HID;
+        __bf16 hi, lo;
+        split2(pn, hi, lo);
+        const size_t o2 = opnd_off(w2_tile(n >> 5, kk >> 5, (kk >> 4) & 1), n, kk);
+        a.w2b[o2] = hi;
+        a.w2l[o2] = lo;
+        if (a.w2t) {
+            const size_t ot = opnd_off(w2t_tile(kk >> 5, n >> 5, (n >> 4) & 1), kk, n);
+            a.w2t[ot] = hi;
+            a.w2tl[ot] = lo;
+        }
+    } else {
+        polyak_one(a, i, tau, omt);
+    }
+}
+
 // squared-norm partials of the flat gradient buffer (one per workgroup) for adam_pack3_kernel
 // when the gradients changed after the backward (the multi-GPU all-reduce)
 __global__ __launch_bounds__(256) void sumsq_parts_kernel(const float* __restrict__ g, float* __restrict__ ss) {
@@ -3222,6 +3293,8 @@ struct TdIn {
     const uint8_t* done;
     float gamma;
     float *loss, *td_abs;
+    const int32_t* sel = nullptr;  // evx_td_opts
+    float delta = 0.f;
 };
 static int qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, const uint16_t* x, const uint16_t* h1,
                          const float* h2, float drop_p, uint16_t* dz2, uint16_t* dz1, const evx_qmlp_grads* g,
@@ -3272,6 +3345,8 @@ static int qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, c
     a.done = td ? td->done : nullptr;
     a.gamma = td ? td->gamma : 0.f;
     a.td_abs = td ? td->td_abs : nullptr;
+    a.sel = td ? td->sel : nullptr;
+    a.delta = td ? td->delta : 0.f;
     float* loss = td ? td->loss : nullptr;
     if (p->x3) {
         if (!p->w2tl) return mfail(-22, "qmlp_backward: x3 needs w2tl (evx_qmlp_pack3)");
@@ -3302,6 +3377,42 @@ int evx_qmlp_td_backward_ss(const evx_qmlp_params* p, int32_t B, const float* Q,
                             uint16_t* dz2, uint16_t* dz1, const evx_qmlp_grads* g, float* ss, void* stream) {
     const TdIn td{Q, Qt, rew, w, act, done, gamma, loss, td_abs};
     return qmlp_backward(p, B, nullptr, x, h1, h2, drop_p, dz2, dz1, g, 1, ss, stream, 1, &td);
+}
+
+int evx_qmlp_td_backward_opt(const evx_qmlp_params* p, int32_t B, const float* Q, const float* Qt, const int32_t* act,
+                             const float* rew, const uint8_t* done, float gamma, const float* w, float* loss,
+                             float* td_abs, const uint16_t* x, const uint16_t* h1, const float* h2, float drop_p,
+                             uint16_t* dz2, uint16_t* dz1, const evx_qmlp_grads* g, float* ss, const evx_td_opts* opt,
+                             void* stream) {
+    TdIn td{Q, Qt, rew, w, act, done, gamma, loss, td_abs};
+    if (opt) {
+        if (!(opt->huber_delta >= 0.f) || !std::isfinite(opt->huber_delta))
+            return mfail(-22, "qmlp_td_backward: huber_delta must be finite and >= 0");
+        td.sel = opt->sel;
+        td.delta = opt->huber_delta;
+    }
+    return qmlp_backward(p, B, nullptr, x, h1, h2, drop_p, dz2, dz1, g, 1, ss, stream, 1, &td);
+}
+
+int evx_qmlp_polyak_pack3(const float* p, float* t, float tau, float one_minus_tau, uint16_t* w1b, uint16_t* w1l,
+                          float* b1c, uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl, uint16_t* w1o,
+                          uint16_t* w1ol, void* stream) {
+    if (!(tau >= 0.f && tau <= 1.f)) return mfail(-22, "qmlp_polyak_pack3: tau must lie in [0, 1]");
+    if (!std::isfinite(one_minus_tau)) return mfail(-22, "qmlp_polyak_pack3: one_minus_tau must be finite");
+    if (!p || !t || !w1b || !w1l || !b1c || !w2b || !w2l) return mfail(-22, "qmlp_polyak_pack3: NULL argument");
+    if ((w1o == nullptr) != (w1ol == nullptr)) return mfail(-22, "qmlp_polyak_pack3: w1o and w1ol go together");
+    if ((w2t == nullptr) != (w2tl == nullptr)) return mfail(-22, "qmlp_polyak_pack3: w2t and w2tl go together");
+    evxm::AdamPack a = {};
+    a.p = t;
+    a.g = const_cast<float*>(p);  // read only (polyak_one)
+    a.w1b = reinterpret_cast<__bf16*>(w1b); a.w1l = reinterpret_cast<__bf16*>(w1l);
+    a.w2b = reinterpret_cast<__bf16*>(w2b); a.w2l = reinterpret_cast<__bf16*>(w2l);
+    a.w2t = reinterpret_cast<__bf16*>(w2t); a.w2tl = reinterpret_cast<__bf16*>(w2tl);
+    a.w1o = reinterpret_cast<__bf16*>(w1o); a.w1ol = reinterpret_cast<__bf16*>(w1ol);
+    a.b1c = b1c;
+    hipLaunchKernelGGL(evxm::polyak_pack3_kernel, dim3((unsigned)((evxm::NPAR + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, a, tau, one_minus_tau);
+    return mlaunch("qmlp_polyak_pack3");
 }
 
 int evx_qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, const uint16_t* x, const uint16_t* h1,

@@ -850,13 +850,16 @@ __global__ __launch_bounds__(256) void colsum_finish(const float* __restrict__ p
 // One row per thread over many blocks, each block's partial into the caller's workspace; a
 // one-block launch per net then sums them in block order (deterministic; no module state, so
 // launches on different streams with their own workspaces never meet).
+// sel / delta (evx_td_opts; not the reference's): the bootstrap action given instead of the
+// target's maximum, the Huber loss instead of the squared error.
 __global__ __launch_bounds__(256) void td_loss_kernel(const float* __restrict__ Q, const float* __restrict__ Qt,
                                                       int A, const int32_t* __restrict__ act,
                                                       const float* __restrict__ rew, const uint8_t* __restrict__ done,
                                                       float gamma, int B, const float* __restrict__ w,
                                                       float* __restrict__ dQ, float* __restrict__ part,
                                                       float* __restrict__ td_abs, int ntd = 0,
-                                                      float* __restrict__ zero = nullptr, int64_t nzero = 0) {
+                                                      float* __restrict__ zero = nullptr, int64_t nzero = 0,
+                                                      const int32_t* __restrict__ sel = nullptr, float delta = 0.f) {
     __shared__ float red[256];
     if (zero && (int)blockIdx.x >= ntd) {  // the extra workgroups clear the gradient buffer for the backward
         if (blockIdx.y) return;
@@ -877,20 +880,32 @@ __global__ __launch_bounds__(256) void td_loss_kernel(const float* __restrict__ 
         if (w) w += o;
         dQ += o * A;
         if (td_abs) td_abs += o;
+        if (sel) sel += o;
     }
     const float nrm = (float)B;
     const int i = blockIdx.x * 256 + threadIdx.x;
     float pt = 0.f;
     if (i < B) {
-        float mx = Qt[(int64_t)i * A];
-        for (int j = 1; j < A; j++) mx = fmaxf(mx, Qt[(int64_t)i * A + j]);
+        float mx;
+        if (sel) {  // Double-Q: the target's value of the given action (clamped: never out of the row)
+            mx = Qt[(int64_t)i * A + min(max(sel[i], 0), A - 1)];
+        } else {
+            mx = Qt[(int64_t)i * A];
+            for (int j = 1; j < A; j++) mx = fmaxf(mx, Qt[(int64_t)i * A + j]);
+        }
         const float y = rew[i] + gamma * mx * (done[i] ? 0.f : 1.f);
         const int a = act[i];
         const float d = Q[(int64_t)i * A + a] - y;
         // prioritized replay: importance weights scale each squared error and its gradient
         const float wi = w ? w[i] : 1.f;
-        pt = w ? wi * (d * d) : d * d;
-        const float g = w ? wi * (2.f * d) : 2.f * d;
+        float l = d * d, gd = 2.f * d;
+        if (delta > 0.f) {  // Huber: quadratic within delta, linear beyond; the gradient clamped
+            const float ad = fabsf(d);
+            l = ad <= delta ? 0.5f * (d * d) : delta * (ad - 0.5f * delta);
+            gd = fminf(fmaxf(d, -delta), delta);
+        }
+        pt = w ? wi * l : l;
+        const float g = w ? wi * gd : gd;
         for (int j = 0; j < A; j++) dQ[(int64_t)i * A + j] = (j == a) ? g / nrm : 0.f;
         if (td_abs) td_abs[i] = fabsf(d);
     }
@@ -916,6 +931,13 @@ __global__ __launch_bounds__(256) void td_finish_kernel(const float* __restrict_
         __syncthreads();
     }
     if (threadIdx.x == 0) loss_out[blockIdx.x] = red[0] / (float)B;
+}
+
+// Polyak target update t = tau p + (1 - tau) t (evx_polyak), one element per thread per trip
+__global__ __launch_bounds__(256) void polyak_kernel(const float* __restrict__ p, float* __restrict__ t, int64_t n,
+                                                     float tau, float omt) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        t[i] = tau * p[i] + omt * t[i];
 }
 
 // ------------------------------------------------- clip_grad_norm_ + Adam
@@ -1844,7 +1866,10 @@ int64_t evx_td_loss_ws_floats(int32_t B, int32_t nets) {
 static int td_launch(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew,
                      const uint8_t* done, float gamma, int32_t B, int32_t nets, const float* w, float* dQ, float* loss,
                      float* td_abs, float* zero, int64_t nzero, float* ws, int64_t ws_floats, void* stream,
-                     const char* what) {
+                     const char* what, const evx_td_opts* opt = nullptr) {
+    const int32_t* sel = opt ? opt->sel : nullptr;
+    const float delta = opt ? opt->huber_delta : 0.f;
+    if (!(delta >= 0.f) || !std::isfinite(delta)) return qfail(-22, "td_loss: huber_delta must be finite and >= 0");
     if (B <= 0) return 0;
     if (nets < 1 || nets > 65535) return qfail(-22, "td_loss: nets must be 1..65535");
     if (!Q || !Qt || !act || !rew || !done || !dQ || !loss) return qfail(-22, "td_loss: NULL argument");
@@ -1853,7 +1878,7 @@ static int td_launch(const float* Q, const float* Qt, int32_t A, const int32_t* 
     const int nz = zero && nzero > 0 ? (int)std::min<int64_t>((nzero + 256 * 16 - 1) / (256 * 16), 512) : 0;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(evxq::td_loss_kernel, dim3(ntd + nz, nets), dim3(256), 0, st, Q, Qt, A, act, rew, done, gamma, B,
-                       w, dQ, ws, td_abs, ntd, nz ? zero : nullptr, nzero);
+                       w, dQ, ws, td_abs, ntd, nz ? zero : nullptr, nzero, sel, delta);
     hipLaunchKernelGGL(evxq::td_finish_kernel, dim3(nets), dim3(256), 0, st, (const float*)ws, ntd, B, loss);
     return qlaunch(what);
 }
@@ -1877,6 +1902,24 @@ int evx_td_loss_zero_g(const float* Q, const float* Qt, int32_t A, const int32_t
                        float* td_abs, float* zero, int64_t nzero, float* ws, int64_t ws_floats, void* stream) {
     return td_launch(Q, Qt, A, act, rew, done, gamma, B, nets, w, dQ, loss, td_abs, zero, nzero, ws, ws_floats, stream,
                      "td_loss_zero_g");
+}
+
+int evx_td_loss_opt(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew,
+                    const uint8_t* done, float gamma, int32_t B, int32_t nets, const float* w, float* dQ, float* loss,
+                    float* td_abs, float* zero, int64_t nzero, float* ws, int64_t ws_floats, const evx_td_opts* opt,
+                    void* stream) {
+    return td_launch(Q, Qt, A, act, rew, done, gamma, B, nets, w, dQ, loss, td_abs, zero, nzero, ws, ws_floats, stream,
+                     "td_loss_opt", opt);
+}
+
+int evx_polyak(const float* p, float* t, int64_t n, float tau, float one_minus_tau, void* stream) {
+    if (!(tau >= 0.f && tau <= 1.f)) return qfail(-22, "polyak: tau must lie in [0, 1]");
+    if (!std::isfinite(one_minus_tau)) return qfail(-22, "polyak: one_minus_tau must be finite");
+    if (!p || !t) return qfail(-22, "polyak: NULL argument");
+    if (n <= 0) return 0;
+    const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(evxq::polyak_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, p, t, n, tau, one_minus_tau);
+    return qlaunch("polyak");
 }
 
 int evx_td_loss(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew, const uint8_t* done,

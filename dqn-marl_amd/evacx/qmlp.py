@@ -11,6 +11,8 @@ operands, f32 accumulation).
 from __future__ import annotations
 
 import ctypes as C
+import math
+from typing import Optional
 
 import numpy as np
 import torch
@@ -43,6 +45,33 @@ class evx_qmlp_dropout(C.Structure):
 
 class evx_qmlp_grads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ["w1", "b1", "w2", "b2", "w3", "b3", "part"]]
+
+
+class evx_td_opts(C.Structure):
+    """TD options (include/evacx.h): sel = the bootstrap action per row (Double-Q; NULL: the
+    target's maximum), huber_delta (0: squared error)."""
+    _fields_ = [("sel", C.c_void_p), ("huber_delta", C.c_float)]
+
+
+def validate_td_options(loss: str = "mse", huber_delta: float = 1.0, target_tau: float = 0.0) -> None:
+    """ValueError for a loss other than "mse" / "huber", a Huber delta that is not a finite
+    positive number, or a soft-update rate outside [0, 1). Needs no device."""
+    if loss not in ("mse", "huber"):
+        raise ValueError(f"loss must be 'mse' or 'huber', not {loss!r}")
+    if not (isinstance(huber_delta, (int, float)) and math.isfinite(huber_delta) and huber_delta > 0):
+        raise ValueError(f"huber_delta must be a finite number > 0, not {huber_delta!r}")
+    if not (isinstance(target_tau, (int, float)) and 0.0 <= target_tau < 1.0):
+        raise ValueError(f"target_tau must lie in [0, 1), not {target_tau!r}")
+
+
+def td_opts(sel=None, huber_delta: float = 0.0) -> evx_td_opts:
+    return evx_td_opts(sel=_p(sel), huber_delta=float(huber_delta))
+
+
+def polyak_coeffs(tau: float):
+    """(tau, 1 - tau) as the kernels take them: f32 tau, and (float)(1.0 - (double)tau) of it."""
+    t = float(np.float32(tau))
+    return t, float(np.float32(1.0 - t))
 
 
 class evx_qmlp_fwd_out(C.Structure):
@@ -83,6 +112,9 @@ def mlib():
         L.evx_qmlp_td_backward_ss.argtypes = [C.POINTER(evx_qmlp_params), C.c_int32] + [C.c_void_p] * 5 + \
             [C.c_float] + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_void_p, C.POINTER(evx_qmlp_grads),
                                               C.c_void_p, C.c_void_p]
+        L.evx_qmlp_td_backward_opt.argtypes = L.evx_qmlp_td_backward_ss.argtypes[:-1] + \
+            [C.POINTER(evx_td_opts), C.c_void_p]
+        L.evx_qmlp_polyak_pack3.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 10
         L.evx_qmlp_norm_parts.restype = C.c_int32
         L.evx_qmlp_nparams.restype = C.c_int64
         if hasattr(L, "evx_qmlp_act_ws_ints"):  # (absent from older builds loaded through EVX_LIB for A/Bs)
@@ -231,6 +263,22 @@ class MLPFast:
         if self._static is not None:  # the act table follows the weights
             self._rebuild_static()
 
+    def polyak_step(self, online_flat, target_flat, tau: float):
+        """target = tau * online + (1 - tau) * target on the flat buffers and this (target)
+        network's x3 operand repack, one launch (evx_qmlp_polyak_pack3); then the act table."""
+        if not self.x3:
+            raise ValueError("polyak_step: the fused repack writes the x3 operand layout")
+        if online_flat.numel() != target_flat.numel() or target_flat.numel() != int(mlib().evx_qmlp_nparams()):
+            raise ValueError("polyak_step: flat buffers of evx_qmlp_nparams() floats")
+        t, omt = polyak_coeffs(tau)
+        mcheck(mlib().evx_qmlp_polyak_pack3(online_flat.data_ptr(), target_flat.data_ptr(), t, omt,
+                                            self.w1b.data_ptr(), self.w1l.data_ptr(), self.b1c.data_ptr(),
+                                            self.w2b.data_ptr(), self.w2l.data_ptr(), self.w2t.data_ptr(),
+                                            self.w2tl.data_ptr(), self.w1o.data_ptr(), self.w1ol.data_ptr(),
+                                            _stream()), "qmlp_polyak_pack3")
+        if self._static is not None:  # the act table follows the weights
+            self._rebuild_static()
+
     @staticmethod
     def sumsq_parts(g, ss):
         """The squared-norm partials of a flat gradient buffer (evx_qmlp_sumsq_parts)."""
@@ -363,9 +411,10 @@ class MLPFast:
         return g
 
     def td_backward(self, B: int, Q, Qt, act, rew, done, gamma: float, loss, x, h1, h2, drop_p: float, dz2, dz1, grads,
-                    weights=None, td_abs=None, ss: Optional[torch.Tensor] = None):
+                    weights=None, td_abs=None, ss: Optional[torch.Tensor] = None, sel=None, huber_delta: float = 0.0):
         """DQNAgent.learn's TD step + loss.backward() in one (evx_qmlp_td_backward_ss): loss[0] = the
-        mean squared TD error, the gradients overwritten; ss (or None) as backward's."""
+        mean squared TD error, the gradients overwritten; ss (or None) as backward's. sel (int32 [B]:
+        the bootstrap action, Double-Q) / huber_delta > 0: evx_qmlp_td_backward_opt."""
         pl = self.planes
         for name, t, n in [("x", x, B * self.kx), ("h1", h1, pl * B * HID), ("dz1", dz1, pl * B * HID),
                            ("dz2", dz2, pl * B * HID2), ("h2", h2, B * HID2), ("Q", Q, B * NACT), ("Qt", Qt, B * NACT),
@@ -375,6 +424,16 @@ class MLPFast:
         if ss is not None:
             _need("td_backward ss", ss, 1, int(mlib().evx_qmlp_norm_parts()))
         g = self._grads(B, grads)
+        if sel is not None or huber_delta:
+            _need("td_backward sel", sel, B, 1)
+            o = td_opts(sel, huber_delta)
+            mcheck(mlib().evx_qmlp_td_backward_opt(C.byref(self.c), B, Q.data_ptr(), Qt.data_ptr(), act.data_ptr(),
+                                                   rew.data_ptr(), done.data_ptr(), float(gamma), _p(weights),
+                                                   loss.data_ptr(), _p(td_abs), x.data_ptr(), h1.data_ptr(),
+                                                   h2.data_ptr(), float(drop_p), dz2.data_ptr(), dz1.data_ptr(),
+                                                   C.byref(g), _p(ss), C.byref(o), _stream()),
+                   "qmlp_td_backward_opt")
+            return
         mcheck(mlib().evx_qmlp_td_backward_ss(C.byref(self.c), B, Q.data_ptr(), Qt.data_ptr(), act.data_ptr(),
                                               rew.data_ptr(), done.data_ptr(), float(gamma), _p(weights),
                                               loss.data_ptr(), _p(td_abs), x.data_ptr(), h1.data_ptr(), h2.data_ptr(),

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from .env import _stream
+from .qmlp import evx_td_opts, polyak_coeffs, td_opts, validate_td_options  # noqa: F401 (re-exported)
 
 PREC = {"f32": 0, "bf16": 1, "x3": 2}
 RELU, ACCUM, SPLIT_AB, OUT_SPLIT = 1, 2, 4, 8
@@ -72,6 +73,8 @@ def qlib():
         L.evx_td_loss_zero_g.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        L.evx_td_loss_opt.argtypes = L.evx_td_loss_zero_g.argtypes[:-1] + [C.POINTER(evx_td_opts), C.c_void_p]
+        L.evx_polyak.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]
         L.evx_sumsq_norm.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.evx_clip_adam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_float, C.POINTER(evx_adam), C.c_void_p]
@@ -410,7 +413,17 @@ class Learner:
     """Online + target networks, fused clip+Adam, TD loss: DQNAgent.learn on the device."""
 
     def __init__(self, kind="mlp", device="cuda", lr=1e-4, gamma=0.99, max_norm=1.0, precision="f32",
-                 hidden=512, actions=5, seed=0, betas=(0.9, 0.999), eps=1e-8):
+                 hidden=512, actions=5, seed=0, betas=(0.9, 0.999), eps=1e-8, double_q=False, loss="mse",
+                 huber_delta=1.0, target_tau=0.0):
+        """double_q: the target bootstraps from the target net's value of the online net's greedy
+        action at s' (one more online forward per learn step); loss: "mse" or "huber" (with
+        huber_delta); target_tau > 0: soft_update() blends the target towards the online net.
+        None of them is the reference's; all off is DQNAgent.learn."""
+        validate_td_options(loss, huber_delta, target_tau)
+        self.double_q, self.loss_kind = bool(double_q), loss
+        self.huber_delta, self.target_tau = float(huber_delta), float(target_tau)
+        self.last_sel = None  # double_q: the last learn step's bootstrap actions (int32 [B], device)
+        self._sel_ws = {}     # the selection act's workspaces by batch size
         if precision not in ("f32", "bf16", "x3", "exact"):
             raise ValueError(f"precision must be 'f32', 'bf16', 'x3' or 'exact', not {precision!r}")
         # "exact": every product on the exact-f32 MFMA GEMMs (evx_gemm f32), no fused MLP kernels
@@ -472,21 +485,44 @@ class Learner:
         net = self.tnet if target else self.net
         return net.forward(x, mask if train else None, save=False, tag=tag + "_")
 
-    def learn(self, s, a, r, done, s2, mask_online=None, mask_target=None, weights=None, td_abs=None):
+    @property
+    def _delta(self) -> float:
+        """The kernels' huber_delta: 0 selects the squared error."""
+        return self.huber_delta if self.loss_kind == "huber" else 0.0
+
+    def _td_loss(self, Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel):
+        """The TD launch of the separate chain: today's entry with the options off."""
+        L = qlib()
+        if sel is None and not self._delta:
+            qcheck(L.evx_td_loss_w(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, _p(weights),
+                                   _p(dQ), _p(self.loss), _p(td_abs), _p(tw), tw.numel(), _stream()), "td_loss")
+            return
+        o = td_opts(sel, self._delta)
+        qcheck(L.evx_td_loss_opt(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, 1, _p(weights),
+                                 _p(dQ), _p(self.loss), _p(td_abs), None, 0, _p(tw), tw.numel(), C.byref(o),
+                                 _stream()), "td_loss_opt")
+
+    def learn(self, s, a, r, done, s2, mask_online=None, mask_target=None, weights=None, td_abs=None,
+              mask_select=None):
         """One DQNAgent.learn step on device tensors; returns the loss tensor (no host sync).
-        weights / td_abs: prioritized replay's importance weights in, |TD error| out."""
+        weights / td_abs: prioritized replay's importance weights in, |TD error| out.
+        mask_select: double_q's selection forward's keep mask (as mask_online / mask_target)."""
         B = s.shape[0]
         if mask_online is None:
             mask_online = self.dropout_mask(B, "on")
         if mask_target is None:
             mask_target = self.dropout_mask(B, "tg")
+        sel = None
+        if self.double_q:  # the online net's greedy action at s' (train mode, as every forward of learn)
+            Qs = self.q_values(s2, train=True, mask=mask_select, target=False, tag="sel")
+            sel = self.net.ws.get("sel", (B,), torch.int32, self.device)
+            qcheck(qlib().evx_act(_p(Qs), B, self.actions, 0.0, 0, 0, _p(sel), _stream()), "act (selection)")
+            self.last_sel = sel
         Q = self.net.forward(s, mask_online, save=True)
         Qt = self.tnet.forward(s2, mask_target, save=False, tag="t_")
         dQ = self.net.ws.get("dq", (B, self.actions), torch.float32, self.device)
-        L = qlib()
         tw = td_workspace(self.net.ws, B, 1, self.device)
-        qcheck(L.evx_td_loss_w(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, _p(weights),
-                               _p(dQ), _p(self.loss), _p(td_abs), _p(tw), tw.numel(), _stream()), "td_loss")
+        self._td_loss(Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel)
         self.net.backward(dQ, self.grads)
         if self.grad_hook is not None:
             self.grad_hook(self.grads.flat)
@@ -494,13 +530,15 @@ class Learner:
         return self.loss
 
     def learn_obs(self, lay_c, s_obs, a, r, done, s2_obs, B, update: bool = True, weights=None, td_abs=None,
-                  mask_online=None, mask_target=None, drop_row0: int = 0):
+                  mask_online=None, mask_target=None, drop_row0: int = 0, mask_select=None):
         """DQNAgent.learn on compact observations with the fused kernels (x3 = f32-accurate,
         or bf16): online forward (saves X, H1, H2), target forward, TD loss, backward,
         clip+Adam. update=False stops after the gradients (the caller runs step_optimizer
         later). mask_online / mask_target: explicit uint8 [B][512] dropout keep masks (tests:
-        the reference's captured torch masks) in place of the hash."""
-        from .qmlp import HID, HID2
+        the reference's captured torch masks) in place of the hash. double_q: one more forward of
+        the online net on s2 (the fused act kernel, actions only) on dropout stream drop_stream + 2
+        (mask_select: its explicit mask) leaves the bootstrap actions in last_sel."""
+        from .qmlp import HID, HID2, act_ws_ints
         for name, t in (("s_obs", s_obs), ("s2_obs", s2_obs)):  # evx_obs rows are 8 words
             if t.numel() < B * 8:
                 raise ValueError(f"learn_obs: {name} holds {t.numel() // 8} observations, B = {B}")
@@ -518,24 +556,33 @@ class Learner:
         dQ = buf("fdq", self.actions, torch.float32).view(B, self.actions)
         dz2 = buf("fdz2", pl * HID2, torch.int16)
         dz1 = buf("fdz1", pl * HID, torch.int16)
-        self.drop_stream += 2
+        self.drop_stream += 3 if self.double_q else 2
         # drop_row0 (even): the dropout hash rows start there (evacx.qgroup keys net g's batch rows g * B + i)
         d_on = (self.seed, self.drop_stream, DROPOUT_P, mask_online, drop_row0)
         d_tg = (self.seed, self.drop_stream + 1, DROPOUT_P, mask_target, drop_row0)
+        sel = None
+        if self.double_q:
+            # the learner's own buffers: in the lagged schedule this runs on the learn stream beside the
+            # trainer's act on the main stream (the act's workspace is zeroed once; every act resets it)
+            sel = buf("fsel", 1, torch.int32)
+            sws = self._sel_ws.get(B)
+            if sws is None:
+                sws = self._sel_ws[B] = torch.zeros(act_ws_ints(B), dtype=torch.int32, device=dev)
+            self.fast.act(lay_c, s2_obs, B, drop=(self.seed, self.drop_stream + 2, DROPOUT_P, mask_select, drop_row0),
+                          actions=sel, epsilon=0.0, ws=sws)
+            self.last_sel = sel
         type(self.fast).forward_pair(lay_c, B, self.fast, s_obs, d_on, dict(h1=H1, x=X, h2=H2, q=Q), self.fast_t,
                                      s2_obs, d_tg, dict(h1=H1t, q=Qt))
-        L = qlib()
         if self.fused_opt:
             # the TD step inside the backward's first kernel, the gradients overwritten by its ordered
             # reductions, which also leave the norm partials unless an all-reduce will change the gradients
             self.fast.td_backward(B, Q, Qt, a, r, done, self.gamma, self.loss, X, H1, H2, DROPOUT_P, dz2, dz1,
                                   self.grads, weights=weights, td_abs=td_abs,
-                                  ss=self._ss if self.grad_hook is None else None)
+                                  ss=self._ss if self.grad_hook is None else None, sel=sel, huber_delta=self._delta)
             self._ss_fresh = self.grad_hook is None
         else:
             tw = td_workspace(ws, B, 1, dev)
-            qcheck(L.evx_td_loss_w(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, _p(weights),
-                                   _p(dQ), _p(self.loss), _p(td_abs), _p(tw), tw.numel(), _stream()), "td_loss")
+            self._td_loss(Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel)
             self.fast.backward(B, dQ, X, H1, H2, DROPOUT_P, dz2, dz1, self.grads)
         if self.grad_hook is not None:
             self.grad_hook(self.grads.flat)
@@ -578,6 +625,19 @@ class Learner:
     def sync_target(self):
         """DQNAgent.update_target_network (agents/dqn_agent.py:170-172)."""
         self.target.flat.copy_(self.online.flat)
+        if self.fast_t is not None:
+            self.fast_t.repack()
+
+    def soft_update(self):
+        """Polyak target update: target = target_tau * online + (1 - target_tau) * target. x3 MLP:
+        the blend and the target's operand repack in one launch (then its act table, if attached);
+        otherwise the blend on the flat buffers (bf16 MLP: then the repack)."""
+        if self.fast_t is not None and self.fast_t.x3:
+            self.fast_t.polyak_step(self.online.flat, self.target.flat, self.target_tau)
+            return
+        t, omt = polyak_coeffs(self.target_tau)
+        qcheck(qlib().evx_polyak(_p(self.online.flat), _p(self.target.flat), self.target.numel, t, omt, _stream()),
+               "polyak")
         if self.fast_t is not None:
             self.fast_t.repack()
 

@@ -30,7 +30,7 @@ from . import _lib
 from ._lib import evx_replay
 from .env import OBS_WORDS, DeviceLayout, VecEnv, _ptr, _stream
 from .qmlp import act_ws_ints
-from .qnet import DROPOUT_P, Learner, qcheck, qlib
+from .qnet import DROPOUT_P, Learner, qcheck, qlib, validate_td_options
 
 
 class Replay:
@@ -138,7 +138,8 @@ class VecTrainer:
                  grad_hook=None, learn_every: int = 1, lagged_learn: bool = False, replay: str = "uniform",
                  prio_alpha: float = 0.6, prio_beta0: float = 0.4, prio_beta_steps: int = 100000,
                  prio_eps: float = 1e-6, groups: int = 1, layout_of=None, world_envs: Optional[int] = None,
-                 nets: str = "shared", act_table: Optional[bool] = None, episode_stats: bool = False):
+                 nets: str = "shared", act_table: Optional[bool] = None, episode_stats: bool = False,
+                 double_q: bool = False, loss: str = "mse", huber_delta: float = 1.0, target_tau: float = 0.0):
         """groups: the envs are split into this many parts, each stepping on its own
         stream chain (see _Group), group g's act after group g - 1's (it overlaps that
         group's env.step); neither the env results nor the act's dropout masks (one stream
@@ -157,7 +158,12 @@ class VecTrainer:
         episode_stats: keep every env's episode returns, lengths and evacuated / dead counts on
         the device (evacx.episodes.EpisodeStats: one more launch per group and step on the
         group's stream, between env.step and the push; no host sync) for episode_summary().
-        Off: nothing is allocated or launched for it."""
+        Off: nothing is allocated or launched for it.
+        double_q / loss ("mse", "huber") / huber_delta / target_tau: the learner's TD options
+        (evacx.qnet.Learner); target_tau > 0 replaces the hard copy every target_every learn steps
+        by Learner.soft_update() after every learn step. nets="shared" only."""
+        validate_td_options(loss, huber_delta, target_tau)
+        self.target_tau = float(target_tau)
         if precision not in ("f32", "bf16", "exact"):
             raise ValueError(f"precision must be 'f32', 'bf16' or 'exact', not {precision!r}")
         self.lay, self.E, self.R = layout, E, layout.R
@@ -170,6 +176,9 @@ class VecTrainer:
         self.per_robot = nets in ("per_robot", "qmix")
         if nets not in ("shared", "per_robot", "qmix"):
             raise ValueError(f"nets must be 'shared', 'per_robot' or 'qmix', not {nets!r}")
+        if self.per_robot and (double_q or loss != "mse" or huber_delta != 1.0 or target_tau != 0.0):
+            raise ValueError("double_q / loss / huber_delta / target_tau need nets='shared': the grouped learner has "
+                             "no grouped selection forward and the QMIX loss has its own kernel")
         if self.per_robot:
             if kind != "mlp" or precision != "f32" or groups != 1 or lagged_learn or replay != "uniform" or \
                     layout_of is not None or grad_hook is not None:
@@ -187,7 +196,8 @@ class VecTrainer:
         # MFMA GEMMs (evx_gemm f32, no fused kernels: the golden-test path, either kind)
         lprec = "x3" if (kind == "conv" and precision == "f32") else precision
         self.learner = Learner(kind=kind, device=self.device, lr=lr, gamma=gamma, precision=lprec,
-                               seed=learner_seed) if not self.per_robot else None
+                               seed=learner_seed, double_q=double_q, loss=loss, huber_delta=huber_delta,
+                               target_tau=target_tau) if not self.per_robot else None
         # the arithmetic the Q-network actually runs: "x3" (f32 operands as bf16 hi + lo pairs on the
         # bf16 MFMA, f32 accumulation: f32 within the tests' stated tolerances), "f32" (exact f32
         # MFMA) or "bf16" -- read from what the learner built
@@ -411,7 +421,9 @@ class VecTrainer:
         self.learn_steps += 1
         if self.epsilon > self.epsilon_min:  # DQNAgent.learn epsilon schedule (agents/dqn_agent.py:163-164)
             self.epsilon *= self.epsilon_decay
-        if self.learn_steps % self.target_every == 0:
+        if self.target_tau > 0:  # Polyak target after every learn step, no periodic hard copy
+            self.learner.soft_update()
+        elif self.learn_steps % self.target_every == 0:
             self.learner.sync_target()
         return loss
 

@@ -586,6 +586,42 @@ int evx_td_loss_zero_g(const float *Q, const float *Qt, int32_t A, const int32_t
                        const uint8_t *done, float gamma, int32_t B, int32_t nets, const float *w, float *dQ,
                        float *loss, float *td_abs, float *zero, int64_t nzero, float *ws, int64_t ws_floats,
                        void *stream);
+
+/* ---- TD options: Double-Q targets, Huber loss, soft target updates. None of them has a
+ * counterpart in the reference (agents/dqn_agent.py:143-151 is the max target with the MSE and
+ * a hard copy); all off gives the entries above bit for bit. Per row, all f32:
+ *   j* = sel ? clamp(sel[i], 0, A - 1) : argmax_j Qt[i][j]
+ *   y  = rew[i] + (gamma * Qt[i][j*]) * (done[i] ? 0 : 1);  d = Q[i][act[i]] - y;  td_abs[i] = |d|
+ *   huber_delta = 0:  l = d * d,  g = 2 d
+ *   huber_delta > 0:  l = |d| <= delta ? 0.5 (d * d) : delta (|d| - 0.5 delta),  g = min(max(d, -delta), delta)
+ *   (l and g times w[i] with weights);  dQ[i][act[i]] = g / B;  loss = mean(l). */
+typedef struct {
+    const int32_t *sel;   /* [B] (grouped: [nets][B]) action whose target value bootstraps:
+                             y uses Qt[i][sel[i]]; NULL: max_j Qt[i][j] */
+    float huber_delta;    /* 0: squared error; > 0: Huber loss with this delta */
+} evx_td_opts;
+/* evx_td_loss_zero_g with options (nets = 1: evx_td_loss_zero; zero = NULL: evx_td_loss_w);
+ * opt = NULL: no options */
+int evx_td_loss_opt(const float *Q, const float *Qt, int32_t A, const int32_t *act, const float *rew,
+                    const uint8_t *done, float gamma, int32_t B, int32_t nets, const float *w, float *dQ,
+                    float *loss, float *td_abs, float *zero, int64_t nzero, float *ws, int64_t ws_floats,
+                    const evx_td_opts *opt, void *stream);
+/* evx_qmlp_td_backward_ss with options (opt = NULL: none) */
+int evx_qmlp_td_backward_opt(const evx_qmlp_params *p, int32_t B, const float *Q, const float *Qt, const int32_t *act,
+                             const float *rew, const uint8_t *done, float gamma, const float *w, float *loss,
+                             float *td_abs, const uint16_t *x, const uint16_t *h1, const float *h2, float drop_p,
+                             uint16_t *dz2, uint16_t *dz1, const evx_qmlp_grads *g, float *ss,
+                             const evx_td_opts *opt, void *stream);
+/* Polyak target update: t = tau * p + one_minus_tau * t, elementwise over n floats; tau in [0, 1],
+ * one_minus_tau = (float)(1.0 - (double)tau) from the caller */
+int evx_polyak(const float *p, float *t, int64_t n, float tau, float one_minus_tau, void *stream);
+/* the same blend on the MLP's flat target parameters t (evx_qmlp_nparams() floats) with the
+ * target's x3 operand repack (evx_qmlp_pack3's outputs; w1o / w1ol: evx_qmlp_pack_occ3's, or both
+ * NULL) in the same launch, as evx_qmlp_adam_pack3 does for the online net */
+int evx_qmlp_polyak_pack3(const float *p, float *t, float tau, float one_minus_tau, uint16_t *w1b, uint16_t *w1l,
+                          float *b1c, uint16_t *w2b, uint16_t *w2l, uint16_t *w2t, uint16_t *w2tl,
+                          uint16_t *w1o, uint16_t *w1ol, void *stream);
+
 /* evx_qmlp_backward_ss for the blocked forward of evx_qmlp_forward2_g (gradients cleared by the
  * caller); g->part: [nets][evx_qmlp_backward_part_floats(B)], ss [nets][evx_qmlp_norm_parts()]. */
 int evx_qmlp_backward_ss_g(const evx_qmlp_params *p, int32_t B, int32_t nets, const float *dq, const uint16_t *x,
