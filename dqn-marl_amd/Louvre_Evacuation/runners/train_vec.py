@@ -14,6 +14,8 @@ a greedy evaluation (evacx.evaluate) of N episodes per env.
 ``--double-q``, ``--loss huber`` (``--huber-delta``) and ``--target-tau`` turn on the
 learner's Double-Q targets, Huber loss and soft target updates (defaults from the optional
 ``agent:`` keys ``double_dqn``, ``loss``, ``huber_delta``, ``target_tau`` of the config).
+``--n-step N`` (default: the optional ``agent:`` key ``n_step``, else 1) trains on n-step
+returns gathered from the replay ring.
 
 Usage: python -m Louvre_Evacuation.runners.train_vec --envs 4096 --steps 2000   (from dqn-marl_amd/)
 """
@@ -52,6 +54,8 @@ def parse_args(argv=None):
     ap.add_argument("--huber-delta", type=float, default=None, help="config: agent.huber_delta; 1.0")
     ap.add_argument("--target-tau", type=float, default=None,
                     help="soft target update rate per learn step; 0: the periodic hard copy (config: agent.target_tau)")
+    ap.add_argument("--n-step", type=int, default=None,
+                    help="n-step returns from the replay ring, 1..32 (config: agent.n_step; 1: one-step targets)")
     return ap.parse_args(argv)
 
 
@@ -67,6 +71,15 @@ def td_options(args, agent_cfg) -> dict:
              target_tau=float(pick(args.target_tau, "target_tau", 0.0)))
     validate_td_options(o["loss"], o["huber_delta"], o["target_tau"])
     return o
+
+
+def n_step_option(args, agent_cfg) -> int:
+    """--n-step, else the config's optional agent key n_step, else 1 (no device needed)."""
+    from evacx._lib import NSTEP_MAX
+    n = args.n_step if args.n_step is not None else agent_cfg.get("n_step", 1)
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= NSTEP_MAX:
+        raise ValueError(f"n_step must be an integer in [1, {NSTEP_MAX}], not {n!r}")
+    return n
 
 
 def checkpoint(tr) -> dict:
@@ -104,18 +117,22 @@ def train_vec(args):
     lay = DeviceLayout(build_tables(spec), int(ec["num_people"]), device=device)
     batch = args.batch or max(256, int(ac.get("batch_size", 32)))
     opts = td_options(args, ac)
-    capacity = 1 << max(10, (max(int(ac.get("memory_size", 50000)), 4 * batch, 2 * args.envs * lay.R) - 1).bit_length())
+    n_step = n_step_option(args, ac)
+    # at least two pushes in the ring, and a whole chain of n_step of them
+    capacity = 1 << max(10, (max(int(ac.get("memory_size", 50000)), 4 * batch,
+                                 max(2, n_step) * args.envs * lay.R) - 1).bit_length())
     tr = VecTrainer(lay, args.envs, kind=args.qnet, batch=batch, replay_capacity=capacity,
                     lr=float(ac.get("learning_rate", 1e-4)), gamma=float(ac.get("gamma", 0.99)),
                     epsilon=float(ac.get("epsilon", 1.0)), epsilon_min=float(ac.get("epsilon_min", 0.02)),
                     epsilon_decay=float(ac.get("epsilon_decay", 0.9995)),
                     target_every=int(ac.get("target_update_freq", 200)), learner_seed=args.seed,
-                    act_table=lay.R % 2 == 0, episode_stats=True, **opts)
+                    act_table=lay.R % 2 == 0, episode_stats=True, n_step=n_step, **opts)
     tgt = f"soft tau {opts['target_tau']:g}" if opts["target_tau"] > 0 else f"hard copy every {tr.target_every}"
     print(f"env {spec.L}x{spec.W}, {lay.P} people, exit {tuple(spec.exit)}; {args.envs} envs, {args.qnet} Q-network "
           f"({tr.q_arith}), batch {batch}, replay {capacity} on {device}; "
           f"{'double-Q' if opts['double_q'] else 'max'} target, "
-          f"{'huber(%g)' % opts['huber_delta'] if opts['loss'] == 'huber' else 'mse'} loss, target {tgt}")
+          f"{'huber(%g)' % opts['huber_delta'] if opts['loss'] == 'huber' else 'mse'} loss, target {tgt}, "
+          f"n_step {n_step}")
     best = float("-inf")
     with open(os.path.join(out_dir, "training_log.csv"), "w", newline="") as f:
         log = csv.writer(f)

@@ -1955,6 +1955,7 @@ struct Bwd {
     // Huber delta (0: the squared error)
     const int32_t* sel;
     float delta;
+    const float* gamma_row;  // the discount per row (n-step rows; NULL: gamma)
 };
 // net g's view of a blocked grouped backward (see fwd_net; x3: two planes per activation)
 __device__ __forceinline__ Bwd bwd_net(const Bwd& a0, int g) {
@@ -2017,7 +2018,8 @@ __global__ __launch_bounds__(256) void qbwd3_kernel(Bwd a0, int rb) {
 #pragma unroll
                     for (int j = 1; j < NACT; j++) mx = fmaxf(mx, a.Qt[(size_t)i * NACT + j]);
                 }
-                const float y = a.rew[i] + a.gamma * mx * (a.done[i] ? 0.f : 1.f);
+                const float gm = a.gamma_row ? a.gamma_row[i] : a.gamma;  // n-step rows: the row's own discount
+                const float y = a.rew[i] + gm * mx * (a.done[i] ? 0.f : 1.f);
                 const int ai = a.act[i];
                 const float d = a.Q[(size_t)i * NACT + ai] - y;
                 const float wi = a.w ? a.w[i] : 1.f;
@@ -3295,6 +3297,7 @@ struct TdIn {
     float *loss, *td_abs;
     const int32_t* sel = nullptr;  // evx_td_opts
     float delta = 0.f;
+    const float* gamma_row = nullptr;
 };
 static int qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, const uint16_t* x, const uint16_t* h1,
                          const float* h2, float drop_p, uint16_t* dz2, uint16_t* dz1, const evx_qmlp_grads* g,
@@ -3347,6 +3350,7 @@ static int qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, c
     a.td_abs = td ? td->td_abs : nullptr;
     a.sel = td ? td->sel : nullptr;
     a.delta = td ? td->delta : 0.f;
+    a.gamma_row = td ? td->gamma_row : nullptr;
     float* loss = td ? td->loss : nullptr;
     if (p->x3) {
         if (!p->w2tl) return mfail(-22, "qmlp_backward: x3 needs w2tl (evx_qmlp_pack3)");
@@ -3390,6 +3394,7 @@ int evx_qmlp_td_backward_opt(const evx_qmlp_params* p, int32_t B, const float* Q
             return mfail(-22, "qmlp_td_backward: huber_delta must be finite and >= 0");
         td.sel = opt->sel;
         td.delta = opt->huber_delta;
+        td.gamma_row = opt->gamma_row;
     }
     return qmlp_backward(p, B, nullptr, x, h1, h2, drop_p, dz2, dz1, g, 1, ss, stream, 1, &td);
 }

@@ -850,8 +850,8 @@ __global__ __launch_bounds__(256) void colsum_finish(const float* __restrict__ p
 // One row per thread over many blocks, each block's partial into the caller's workspace; a
 // one-block launch per net then sums them in block order (deterministic; no module state, so
 // launches on different streams with their own workspaces never meet).
-// sel / delta (evx_td_opts; not the reference's): the bootstrap action given instead of the
-// target's maximum, the Huber loss instead of the squared error.
+// sel / delta / gamma_row (evx_td_opts; not the reference's): the bootstrap action given instead
+// of the target's maximum, the Huber loss instead of the squared error, a discount per row.
 __global__ __launch_bounds__(256) void td_loss_kernel(const float* __restrict__ Q, const float* __restrict__ Qt,
                                                       int A, const int32_t* __restrict__ act,
                                                       const float* __restrict__ rew, const uint8_t* __restrict__ done,
@@ -859,7 +859,8 @@ __global__ __launch_bounds__(256) void td_loss_kernel(const float* __restrict__ 
                                                       float* __restrict__ dQ, float* __restrict__ part,
                                                       float* __restrict__ td_abs, int ntd = 0,
                                                       float* __restrict__ zero = nullptr, int64_t nzero = 0,
-                                                      const int32_t* __restrict__ sel = nullptr, float delta = 0.f) {
+                                                      const int32_t* __restrict__ sel = nullptr, float delta = 0.f,
+                                                      const float* __restrict__ gamma_row = nullptr) {
     __shared__ float red[256];
     if (zero && (int)blockIdx.x >= ntd) {  // the extra workgroups clear the gradient buffer for the backward
         if (blockIdx.y) return;
@@ -881,6 +882,7 @@ __global__ __launch_bounds__(256) void td_loss_kernel(const float* __restrict__ 
         dQ += o * A;
         if (td_abs) td_abs += o;
         if (sel) sel += o;
+        if (gamma_row) gamma_row += o;
     }
     const float nrm = (float)B;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -893,7 +895,8 @@ __global__ __launch_bounds__(256) void td_loss_kernel(const float* __restrict__ 
             mx = Qt[(int64_t)i * A];
             for (int j = 1; j < A; j++) mx = fmaxf(mx, Qt[(int64_t)i * A + j]);
         }
-        const float y = rew[i] + gamma * mx * (done[i] ? 0.f : 1.f);
+        // gamma_row (n-step rows, evx_replay_nstep): the row's own discount gamma^L
+        const float y = rew[i] + (gamma_row ? gamma_row[i] : gamma) * mx * (done[i] ? 0.f : 1.f);
         const int a = act[i];
         const float d = Q[(int64_t)i * A + a] - y;
         // prioritized replay: importance weights scale each squared error and its gradient
@@ -1083,6 +1086,43 @@ __global__ __launch_bounds__(256) void replay_sample_kernel(evx_replay rp, int64
     r[i] = rp.r[j];
     done[i] = rp.done[j];
     if (idx_out) idx_out[i] = j;
+}
+
+// n-step rows of sampled slots (evx_replay_nstep; not the reference's, whose target is one step
+// deep). Every training step pushes `stride` rows in the same order, so the successor of slot j
+// (same env, same robot, next env step) is slot (j + stride) mod capacity while that slot lies in
+// the live range [base, base + count) mod capacity (push order, oldest first): no link array.
+// One row per thread; the chain stops at n_step links, at a terminal slot (so never across an
+// auto-reset: that slot's s2 is the terminal observation) or at the end of the range. All f32;
+// R + g * r stays a multiply and an add (-ffp-contract=off). A slot index outside the ring is
+// clamped into it (never read out of bounds); one outside the range keeps its own row (L = 1).
+__global__ __launch_bounds__(256) void replay_nstep_kernel(evx_replay rp, const int64_t* __restrict__ idx, int B,
+                                                           int64_t base, int64_t count, int64_t stride, int n_step,
+                                                           float gamma, evx_obs* __restrict__ s2,
+                                                           float* __restrict__ r, uint8_t* __restrict__ done,
+                                                           float* __restrict__ gamma_row, int32_t* __restrict__ len) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    const int64_t C = rp.capacity;
+    const int64_t j0 = min(max(idx[i], (int64_t)0), C - 1);
+    int64_t d0 = j0 - base;
+    if (d0 < 0) d0 += C;
+    int64_t j = j0;
+    float R = rp.r[j0], g = gamma;
+    uint8_t dn = rp.done[j0];
+    int L = 1;
+    while (L < n_step && !dn && d0 + (int64_t)L * stride < count) {
+        j = (j0 + (int64_t)L * stride) % C;
+        R = R + g * rp.r[j];
+        g = g * gamma;
+        dn = rp.done[j];
+        L++;
+    }
+    r[i] = R;
+    gamma_row[i] = g;
+    done[i] = dn;
+    s2[i] = rp.s2[j];
+    if (len) len[i] = L;
 }
 
 __global__ __launch_bounds__(256) void gather_rows_kernel(const evx_obs* __restrict__ src,
@@ -1869,6 +1909,7 @@ static int td_launch(const float* Q, const float* Qt, int32_t A, const int32_t* 
                      const char* what, const evx_td_opts* opt = nullptr) {
     const int32_t* sel = opt ? opt->sel : nullptr;
     const float delta = opt ? opt->huber_delta : 0.f;
+    const float* gamma_row = opt ? opt->gamma_row : nullptr;
     if (!(delta >= 0.f) || !std::isfinite(delta)) return qfail(-22, "td_loss: huber_delta must be finite and >= 0");
     if (B <= 0) return 0;
     if (nets < 1 || nets > 65535) return qfail(-22, "td_loss: nets must be 1..65535");
@@ -1878,7 +1919,7 @@ static int td_launch(const float* Q, const float* Qt, int32_t A, const int32_t* 
     const int nz = zero && nzero > 0 ? (int)std::min<int64_t>((nzero + 256 * 16 - 1) / (256 * 16), 512) : 0;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(evxq::td_loss_kernel, dim3(ntd + nz, nets), dim3(256), 0, st, Q, Qt, A, act, rew, done, gamma, B,
-                       w, dQ, ws, td_abs, ntd, nz ? zero : nullptr, nzero, sel, delta);
+                       w, dQ, ws, td_abs, ntd, nz ? zero : nullptr, nzero, sel, delta, gamma_row);
     hipLaunchKernelGGL(evxq::td_finish_kernel, dim3(nets), dim3(256), 0, st, (const float*)ws, ntd, B, loss);
     return qlaunch(what);
 }
@@ -2037,6 +2078,26 @@ int evx_replay_sample_window(const evx_replay* rp, int64_t base, int64_t count, 
     hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, base, count,
                        B, seed, offset, s, s2, a, r, done, idx_out);
     return qlaunch("replay_sample_window");
+}
+
+int evx_replay_nstep(const evx_replay* rp, const int64_t* idx, int32_t B, int64_t base, int64_t count, int64_t stride,
+                     int32_t n_step, float gamma, evx_obs* s2, float* r, uint8_t* done, float* gamma_row, int32_t* len,
+                     void* stream) {
+    if (!rp || rp->capacity <= 0) return qfail(-22, "replay_nstep: bad ring");
+    if (!idx || !s2 || !r || !done || !gamma_row) return qfail(-22, "replay_nstep: NULL argument");
+    if (n_step < 1 || n_step > EVX_NSTEP_MAX) return qfail(-22, "replay_nstep: n_step must be 1..EVX_NSTEP_MAX (32)");
+    if (stride < 1) return qfail(-22, "replay_nstep: stride must be >= 1");
+    if (count < 0 || count > rp->capacity) return qfail(-22, "replay_nstep: count must lie in [0, capacity]");
+    if (base < 0 || base >= rp->capacity) return qfail(-22, "replay_nstep: base must lie in [0, capacity)");
+    if (!std::isfinite(gamma)) return qfail(-22, "replay_nstep: gamma must be finite");
+    if (B <= 0) return 0;
+    if (!rp->s2 || !rp->r || !rp->done) return qfail(-22, "replay_nstep: ring without s2 / r / done");
+    // a stride beyond the ring never finds a successor inside the range (count <= capacity): the
+    // capacity stands for it, so L * stride cannot overflow
+    hipLaunchKernelGGL(evxq::replay_nstep_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, idx, (int)B,
+                       base, count, std::min<int64_t>(stride, rp->capacity), (int)n_step, gamma, s2, r, done,
+                       gamma_row, len);
+    return qlaunch("replay_nstep");
 }
 
 int evx_gather_obs(const evx_obs* src, const int64_t* idx, int32_t n, evx_obs* dst, void* stream) {

@@ -29,6 +29,7 @@ class evx_layout(C.Structure):
                                          "layout_set", "obs_feats", "obs_feat_lo", "obs_feats_lo"]]
 
 FEAT_PAD = 6  # EVX_FEAT_PAD
+NSTEP_MAX = 32  # EVX_NSTEP_MAX
 
 
 class evx_state(C.Structure):
@@ -90,6 +91,10 @@ def lib():
         L.evx_env_classes.argtypes = [C.POINTER(evx_layout), C.POINTER(evx_state), C.c_void_p]
         L.evx_perm_ws_bytes.restype = C.c_int64
         L.evx_perm_ws_bytes.argtypes = [C.c_int32]
+        if hasattr(L, "evx_replay_nstep"):  # (absent from older builds loaded through EVX_LIB for A/Bs)
+            L.evx_replay_nstep.restype = C.c_int
+            L.evx_replay_nstep.argtypes = [C.POINTER(evx_replay), C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                           C.c_int64, C.c_int32, C.c_float] + [C.c_void_p] * 6
         _lib = L
     return _lib
 
@@ -103,6 +108,6 @@ def check(rc: int, what: str):
 EXPORTS = ["evx_env_step", "evx_env_reset", "evx_obs_expand_f32", "evx_obs_expand_f64", "evx_seed_host",
            "evx_step_lds_bytes", "evx_step_scratch_words", "evx_last_error", "evx_perm_ws_bytes",
            "evx_env_order", "evx_act_perm", "evx_env_orders", "evx_env_classes", "evx_env_orders_push", "evx_env_orders_push_sample",
-           "evx_env_step_occupancy",
+           "evx_env_step_occupancy", "evx_replay_nstep",
            "evx_episode_init", "evx_episode_update", "evx_episode_discard", "evx_episode_reduce",
            "evx_episode_last_error"]

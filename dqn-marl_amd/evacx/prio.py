@@ -13,6 +13,10 @@ The reference's replay is a uniform ``deque`` (Louvre_Evacuation/agents/dqn_agen
 
 Slots a concurrently running push is about to overwrite are *hidden* (priority 0) so
 the lagged schedule's learn step never samples them (``expose(n_hide=...)``).
+
+``sample_prio``'s ``idx`` is also what the inherited ``Replay.nstep`` takes (n-step rows of the
+sampled slots, ``VecTrainer(n_step=)``); ``update`` then sets the priorities of those slots from
+the n-step |TD error|.
 """
 from __future__ import annotations
 

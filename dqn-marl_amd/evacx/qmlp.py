@@ -49,8 +49,9 @@ class evx_qmlp_grads(C.Structure):
 
 class evx_td_opts(C.Structure):
     """TD options (include/evacx.h): sel = the bootstrap action per row (Double-Q; NULL: the
-    target's maximum), huber_delta (0: squared error)."""
-    _fields_ = [("sel", C.c_void_p), ("huber_delta", C.c_float)]
+    target's maximum), huber_delta (0: squared error), gamma_row = the discount per row (n-step
+    rows; NULL: the scalar gamma)."""
+    _fields_ = [("sel", C.c_void_p), ("huber_delta", C.c_float), ("gamma_row", C.c_void_p)]
 
 
 def validate_td_options(loss: str = "mse", huber_delta: float = 1.0, target_tau: float = 0.0) -> None:
@@ -64,8 +65,8 @@ def validate_td_options(loss: str = "mse", huber_delta: float = 1.0, target_tau:
         raise ValueError(f"target_tau must lie in [0, 1), not {target_tau!r}")
 
 
-def td_opts(sel=None, huber_delta: float = 0.0) -> evx_td_opts:
-    return evx_td_opts(sel=_p(sel), huber_delta=float(huber_delta))
+def td_opts(sel=None, huber_delta: float = 0.0, gamma_row=None) -> evx_td_opts:
+    return evx_td_opts(sel=_p(sel), huber_delta=float(huber_delta), gamma_row=_p(gamma_row))
 
 
 def polyak_coeffs(tau: float):
@@ -411,10 +412,12 @@ class MLPFast:
         return g
 
     def td_backward(self, B: int, Q, Qt, act, rew, done, gamma: float, loss, x, h1, h2, drop_p: float, dz2, dz1, grads,
-                    weights=None, td_abs=None, ss: Optional[torch.Tensor] = None, sel=None, huber_delta: float = 0.0):
+                    weights=None, td_abs=None, ss: Optional[torch.Tensor] = None, sel=None, huber_delta: float = 0.0,
+                    gamma_row=None):
         """DQNAgent.learn's TD step + loss.backward() in one (evx_qmlp_td_backward_ss): loss[0] = the
         mean squared TD error, the gradients overwritten; ss (or None) as backward's. sel (int32 [B]:
-        the bootstrap action, Double-Q) / huber_delta > 0: evx_qmlp_td_backward_opt."""
+        the bootstrap action, Double-Q) / huber_delta > 0 / gamma_row (f32 [B]: the discount per row,
+        n-step rows): evx_qmlp_td_backward_opt."""
         pl = self.planes
         for name, t, n in [("x", x, B * self.kx), ("h1", h1, pl * B * HID), ("dz1", dz1, pl * B * HID),
                            ("dz2", dz2, pl * B * HID2), ("h2", h2, B * HID2), ("Q", Q, B * NACT), ("Qt", Qt, B * NACT),
@@ -424,9 +427,10 @@ class MLPFast:
         if ss is not None:
             _need("td_backward ss", ss, 1, int(mlib().evx_qmlp_norm_parts()))
         g = self._grads(B, grads)
-        if sel is not None or huber_delta:
+        if sel is not None or huber_delta or gamma_row is not None:
             _need("td_backward sel", sel, B, 1)
-            o = td_opts(sel, huber_delta)
+            _need("td_backward gamma_row", gamma_row, B, 1)
+            o = td_opts(sel, huber_delta, gamma_row)
             mcheck(mlib().evx_qmlp_td_backward_opt(C.byref(self.c), B, Q.data_ptr(), Qt.data_ptr(), act.data_ptr(),
                                                    rew.data_ptr(), done.data_ptr(), float(gamma), _p(weights),
                                                    loss.data_ptr(), _p(td_abs), x.data_ptr(), h1.data_ptr(),

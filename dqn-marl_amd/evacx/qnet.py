@@ -490,23 +490,27 @@ class Learner:
         """The kernels' huber_delta: 0 selects the squared error."""
         return self.huber_delta if self.loss_kind == "huber" else 0.0
 
-    def _td_loss(self, Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel):
+    def _td_loss(self, Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel, gamma_row=None):
         """The TD launch of the separate chain: today's entry with the options off."""
         L = qlib()
-        if sel is None and not self._delta:
+        if gamma_row is not None and (gamma_row.dtype != torch.float32 or gamma_row.numel() < B):
+            raise ValueError(f"gamma_row must be a float32 tensor of at least B = {B} elements")
+        if sel is None and not self._delta and gamma_row is None:
             qcheck(L.evx_td_loss_w(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, _p(weights),
                                    _p(dQ), _p(self.loss), _p(td_abs), _p(tw), tw.numel(), _stream()), "td_loss")
             return
-        o = td_opts(sel, self._delta)
+        o = td_opts(sel, self._delta, gamma_row)
         qcheck(L.evx_td_loss_opt(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, 1, _p(weights),
                                  _p(dQ), _p(self.loss), _p(td_abs), None, 0, _p(tw), tw.numel(), C.byref(o),
                                  _stream()), "td_loss_opt")
 
     def learn(self, s, a, r, done, s2, mask_online=None, mask_target=None, weights=None, td_abs=None,
-              mask_select=None):
+              mask_select=None, gamma_row=None):
         """One DQNAgent.learn step on device tensors; returns the loss tensor (no host sync).
         weights / td_abs: prioritized replay's importance weights in, |TD error| out.
-        mask_select: double_q's selection forward's keep mask (as mask_online / mask_target)."""
+        mask_select: double_q's selection forward's keep mask (as mask_online / mask_target).
+        gamma_row: device f32 [B], the discount per row in place of gamma (n-step rows from
+        Replay.nstep: r the n-step return, s2 / done the chain's last slot's)."""
         B = s.shape[0]
         if mask_online is None:
             mask_online = self.dropout_mask(B, "on")
@@ -522,7 +526,7 @@ class Learner:
         Qt = self.tnet.forward(s2, mask_target, save=False, tag="t_")
         dQ = self.net.ws.get("dq", (B, self.actions), torch.float32, self.device)
         tw = td_workspace(self.net.ws, B, 1, self.device)
-        self._td_loss(Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel)
+        self._td_loss(Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel, gamma_row)
         self.net.backward(dQ, self.grads)
         if self.grad_hook is not None:
             self.grad_hook(self.grads.flat)
@@ -530,15 +534,18 @@ class Learner:
         return self.loss
 
     def learn_obs(self, lay_c, s_obs, a, r, done, s2_obs, B, update: bool = True, weights=None, td_abs=None,
-                  mask_online=None, mask_target=None, drop_row0: int = 0, mask_select=None):
+                  mask_online=None, mask_target=None, drop_row0: int = 0, mask_select=None, gamma_row=None):
         """DQNAgent.learn on compact observations with the fused kernels (x3 = f32-accurate,
         or bf16): online forward (saves X, H1, H2), target forward, TD loss, backward,
         clip+Adam. update=False stops after the gradients (the caller runs step_optimizer
         later). mask_online / mask_target: explicit uint8 [B][512] dropout keep masks (tests:
         the reference's captured torch masks) in place of the hash. double_q: one more forward of
         the online net on s2 (the fused act kernel, actions only) on dropout stream drop_stream + 2
-        (mask_select: its explicit mask) leaves the bootstrap actions in last_sel."""
+        (mask_select: its explicit mask) leaves the bootstrap actions in last_sel. gamma_row: as
+        learn's."""
         from .qmlp import HID, HID2, act_ws_ints
+        if gamma_row is not None and (gamma_row.dtype != torch.float32 or gamma_row.numel() < B):
+            raise ValueError(f"gamma_row must be a float32 tensor of at least B = {B} elements")
         for name, t in (("s_obs", s_obs), ("s2_obs", s2_obs)):  # evx_obs rows are 8 words
             if t.numel() < B * 8:
                 raise ValueError(f"learn_obs: {name} holds {t.numel() // 8} observations, B = {B}")
@@ -578,11 +585,12 @@ class Learner:
             # reductions, which also leave the norm partials unless an all-reduce will change the gradients
             self.fast.td_backward(B, Q, Qt, a, r, done, self.gamma, self.loss, X, H1, H2, DROPOUT_P, dz2, dz1,
                                   self.grads, weights=weights, td_abs=td_abs,
-                                  ss=self._ss if self.grad_hook is None else None, sel=sel, huber_delta=self._delta)
+                                  ss=self._ss if self.grad_hook is None else None, sel=sel, huber_delta=self._delta,
+                                  gamma_row=gamma_row)
             self._ss_fresh = self.grad_hook is None
         else:
             tw = td_workspace(ws, B, 1, dev)
-            self._td_loss(Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel)
+            self._td_loss(Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel, gamma_row)
             self.fast.backward(B, dQ, X, H1, H2, DROPOUT_P, dz2, dz1, self.grads)
         if self.grad_hook is not None:
             self.grad_hook(self.grads.flat)

@@ -93,7 +93,8 @@ class Replay:
                                                C.c_void_p, C.c_void_p, C.c_void_p]
         qcheck(L.evx_replay_sample_window(C.byref(self.c), base, count, B, seed, offset, out["s"].data_ptr(),
                                           out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
-                                          out["done"].data_ptr(), None, _stream()), "replay_sample_window")
+                                          out["done"].data_ptr(), _ptr(out.get("idx")), _stream()),
+               "replay_sample_window")
 
     def sample(self, B, seed, offset, out):
         L = _lib.lib()
@@ -102,7 +103,31 @@ class Replay:
                                         C.c_void_p]
         qcheck(L.evx_replay_sample(C.byref(self.c), self.size, B, seed, offset, out["s"].data_ptr(),
                                    out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
-                                   out["done"].data_ptr(), None, _stream()), "replay_sample")
+                                   out["done"].data_ptr(), _ptr(out.get("idx")), _stream()), "replay_sample")
+
+    def live_range(self):
+        """(base, count) of the whole ring in push order, oldest first."""
+        return (self.pos - self.size) % self.capacity, self.size
+
+    def nstep(self, idx, B, base, count, stride, n_step, gamma, out):
+        """n-step rows of the sampled slots idx (int64 [B], the samplers' idx_out) over the live
+        range [base, base + count) mod capacity, stride rows pushed per env step
+        (evx_replay_nstep): out["r"] = the discounted return of up to n_step rewards, out["s2"] /
+        out["done"] = the chain's last slot's, out["gamma_row"] = gamma^L (f32 products),
+        out["nlen"] (optional, int32) = L. The chain stops at a terminal slot and at the end of
+        the range."""
+        for k, per in (("r", 1), ("done", 1), ("gamma_row", 1), ("s2", OBS_WORDS)):
+            if out[k].numel() < B * per:
+                raise ValueError(f"nstep: out[{k!r}] holds {out[k].numel() // per} rows, B = {B}")
+        if idx.dtype != torch.int64 or idx.numel() < B:
+            raise ValueError(f"nstep: idx must be an int64 tensor of at least B = {B} elements")
+        nlen = out.get("nlen")
+        if nlen is not None and nlen.numel() < B:
+            raise ValueError(f"nstep: out['nlen'] holds {nlen.numel()} rows, B = {B}")
+        qcheck(_lib.lib().evx_replay_nstep(C.byref(self.c), idx.data_ptr(), B, base, count, stride, n_step,
+                                           float(gamma), out["s2"].data_ptr(), out["r"].data_ptr(),
+                                           out["done"].data_ptr(), out["gamma_row"].data_ptr(), _ptr(nlen),
+                                           _stream()), "replay_nstep")
 
 
 class _Group:
@@ -139,7 +164,8 @@ class VecTrainer:
                  prio_alpha: float = 0.6, prio_beta0: float = 0.4, prio_beta_steps: int = 100000,
                  prio_eps: float = 1e-6, groups: int = 1, layout_of=None, world_envs: Optional[int] = None,
                  nets: str = "shared", act_table: Optional[bool] = None, episode_stats: bool = False,
-                 double_q: bool = False, loss: str = "mse", huber_delta: float = 1.0, target_tau: float = 0.0):
+                 double_q: bool = False, loss: str = "mse", huber_delta: float = 1.0, target_tau: float = 0.0,
+                 n_step: int = 1):
         """groups: the envs are split into this many parts, each stepping on its own
         stream chain (see _Group), group g's act after group g - 1's (it overlaps that
         group's env.step); neither the env results nor the act's dropout masks (one stream
@@ -161,9 +187,28 @@ class VecTrainer:
         Off: nothing is allocated or launched for it.
         double_q / loss ("mse", "huber") / huber_delta / target_tau: the learner's TD options
         (evacx.qnet.Learner); target_tau > 0 replaces the hard copy every target_every learn steps
-        by Learner.soft_update() after every learn step. nets="shared" only."""
+        by Learner.soft_update() after every learn step. nets="shared" only.
+        n_step > 1: the learn step turns its sampled slots into n-step rows (Replay.nstep, one more
+        launch after the sampler's, on its stream: r = the discounted return of up to n_step
+        rewards of the same env and robot, s2 / done the chain's last slot's, the discount per row
+        in samp["gamma_row"], the chain lengths in samp["nlen"]); under every sampler and both
+        schedules. nets="shared", groups=1 and no step(extra_reset=...). 1: nothing of it runs."""
         validate_td_options(loss, huber_delta, target_tau)
         self.target_tau = float(target_tau)
+        if not (isinstance(n_step, int) and 1 <= n_step <= _lib.NSTEP_MAX):
+            raise ValueError(f"n_step must be an integer in [1, {_lib.NSTEP_MAX}], not {n_step!r}")
+        if n_step > 1:
+            if nets != "shared":
+                raise ValueError(f"n_step > 1 needs nets='shared': the samplers of nets={nets!r} return no slot "
+                                 "indices")
+            if groups != 1:
+                raise ValueError("n_step > 1 needs groups=1: the successor rule rests on one push of E * R rows "
+                                 "per step")
+            if n_step * E * layout.R > replay_capacity:
+                raise ValueError(f"n_step * E * R = {n_step * E * layout.R} exceeds replay_capacity = "
+                                 f"{replay_capacity}: no n_step chain could ever complete")
+        self.n_step = n_step
+        self.last_range = None  # n_step > 1: the (base, count) the last learn step's chains ran over
         if precision not in ("f32", "bf16", "exact"):
             raise ValueError(f"precision must be 'f32', 'bf16' or 'exact', not {precision!r}")
         self.lay, self.E, self.R = layout, E, layout.R
@@ -255,6 +300,11 @@ class VecTrainer:
             self.samp.update(idx=torch.zeros(batch, dtype=torch.int64, device=self.device),
                              w=torch.zeros(batch, dtype=torch.float32, device=self.device),
                              td=torch.zeros(batch, dtype=torch.float32, device=self.device))
+        if self.n_step > 1:  # the samplers' slot indices, the rows' discounts and chain lengths
+            if not self.prio:
+                self.samp["idx"] = torch.zeros(batch, dtype=torch.int64, device=self.device)
+            self.samp.update(gamma_row=torch.zeros(batch, dtype=torch.float32, device=self.device),
+                             nlen=torch.zeros(batch, dtype=torch.int32, device=self.device))
         # replay sampling: per rank (each rank samples its own shard); act draws: one key for
         # all ranks (counters are global agent ids)
         self.seed = learner_seed * 7919 + env_offset + 17
@@ -392,17 +442,26 @@ class VecTrainer:
             else:
                 self.replay.sample_window(window[0], window[1], self.batch, self.seed + 1,
                                           self.learn_steps * self.batch, self.samp)
+            grow = None
+            if self.n_step > 1:
+                # the sampled slots' n-step rows over the range the batch was drawn from (lagged: the
+                # window, which the concurrent push does not write), in place of their r / done / s2
+                self.last_range = window if window is not None else self.replay.live_range()
+                self.replay.nstep(self.samp["idx"], self.batch, self.last_range[0], self.last_range[1],
+                                  self.n_agents, self.n_step, self.learner.gamma, self.samp)
+                grow = self.samp["gamma_row"]
             side_prio = self.prio and phase == "all" and self.fast is not None and not self.lagged
             if self.fast is not None:
                 loss = self.learner.learn_obs(self.lay.c, self.samp["s"], self.samp["a"], self.samp["r"],
                                               self.samp["done"], self.samp["s2"], self.batch,
-                                              update=phase == "all" and not side_prio, weights=w, td_abs=td)
+                                              update=phase == "all" and not side_prio, weights=w, td_abs=td,
+                                              gamma_row=grow)
             else:
                 assert phase == "all", "a two-phase learn needs the fused MLP path"
                 s = self.env.expand_obs(torch.float32, self.samp["s"]).view(self.batch, 11, 11, 6)
                 s2 = self.env.expand_obs(torch.float32, self.samp["s2"]).view(self.batch, 11, 11, 6)
                 loss = self.learner.learn(s, self.samp["a"], self.samp["r"], self.samp["done"], s2, weights=w,
-                                          td_abs=td)
+                                          td_abs=td, gamma_row=grow)
             if side_prio:  # |TD| is ready: the trees' update on the priority stream, then clip+Adam here
                 cur = torch.cuda.current_stream(self.device)
                 self.ev_td.record(cur)
@@ -444,6 +503,8 @@ class VecTrainer:
         before this step's push (minus the slots the push overwrites): its gradients
         overlap act and env.step, its weight update waits for every group's act to have
         read the weights, and the next acts wait for the update."""
+        if extra_reset is not None and self.n_step > 1:
+            raise ValueError("extra_reset with n_step > 1: a forced reset breaks a transition chain without a done")
         caller = torch.cuda.current_stream(self.device)
         join = self.join_caller
         if self.join_caller or extra_reset is not None:  # inputs made on the caller's stream
@@ -508,9 +569,11 @@ class VecTrainer:
                 if grp.ep is not None:  # before this stream's next step overwrites reward / done / counts
                     grp.ep.update(grp.env.reward, grp.env.done, grp.env.counts)
                 if fused:
-                    # the strict schedule's learn batch drawn in the same launch (the ring after this push)
+                    # the strict schedule's learn batch drawn in the same launch (the ring after this push;
+                    # not with n_step > 1: that draw leaves no slot indices)
                     smp = None
-                    if (not self.lagged and not self.prio and not self.per_robot and self.t % self.learn_every == 0
+                    if (self.n_step == 1 and not self.lagged and not self.prio and not self.per_robot
+                            and self.t % self.learn_every == 0
                             and min(self.replay.capacity, self.replay.size + grp.n) >= self.batch):
                         smp = (self.batch, self.seed + 1, self.learn_steps * self.batch, self.samp)
                     self.replay.push_orders(grp.env, grp.perm, grp.env.obs_prev, grp.env.obs, grp.actions,

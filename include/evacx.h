@@ -336,6 +336,26 @@ int evx_replay_sample_agents(const evx_replay *rp, int64_t size, int32_t B, int3
 int evx_replay_sample_joint(const evx_replay *rp, int64_t size, int32_t B, int32_t nets, uint64_t seed,
                             uint64_t offset, evx_obs *s, evx_obs *s2, int32_t *a, float *r, uint8_t *done,
                             void *stream);
+/* n-step rows of sampled slots (no counterpart in the reference, whose target is one step deep).
+ * Every training step pushes `stride` rows in the same order (env * R + robot), so the successor
+ * of slot j -- same env, same robot, next env step -- is slot (j + stride) mod capacity while that
+ * slot is inside the live range [base, base + count) mod capacity (push order, oldest first: the
+ * whole ring is ((pos - size) mod capacity, size), the lagged schedule's window is the pair given
+ * to evx_replay_sample_window). idx [B]: the samplers' idx_out. Per row, all f32, a multiply and
+ * an add (no fma):
+ *   j0 = idx[i];  d0 = (j0 - base) mod C;  j = j0;  R = r[j0];  g = gamma;  dn = done[j0];  L = 1
+ *   while L < n_step and !dn and d0 + L stride < count:
+ *       j = (j0 + L stride) mod C;  R = R + g r[j];  g = g gamma;  dn = done[j];  L = L + 1
+ *   r[i] = R;  gamma_row[i] = g;  done[i] = dn;  s2[i] = rp.s2[j];  len[i] = L   (len may be NULL)
+ * so y = R + gamma_row * Q_target(s2, .) * !done (evx_td_opts.gamma_row). The chain stops at a
+ * terminal slot (never across an auto-reset) and at the end of the range; a row with d0 >= count
+ * keeps its own slot (L = 1); n_step = 1 copies the slot's r, done, s2 and gamma_row = gamma.
+ * -22 before any launch: a NULL required pointer, n_step outside [1, EVX_NSTEP_MAX], stride < 1,
+ * count outside [0, capacity], base outside [0, capacity), gamma not finite (evx_q_last_error). */
+#define EVX_NSTEP_MAX 32
+int evx_replay_nstep(const evx_replay *rp, const int64_t *idx, int32_t B, int64_t base, int64_t count,
+                     int64_t stride, int32_t n_step, float gamma, evx_obs *s2, float *r, uint8_t *done,
+                     float *gamma_row, int32_t *len, void *stream);
 /* ------------------------------------------- prioritized replay
  * Proportional prioritized replay (Schaul et al. 2016) over the slots of an evx_replay
  * ring; the reference samples uniformly (random.sample, agents/dqn_agent.py:132), so
@@ -592,6 +612,7 @@ int evx_td_loss_zero_g(const float *Q, const float *Qt, int32_t A, const int32_t
  * a hard copy); all off gives the entries above bit for bit. Per row, all f32:
  *   j* = sel ? clamp(sel[i], 0, A - 1) : argmax_j Qt[i][j]
  *   y  = rew[i] + (gamma * Qt[i][j*]) * (done[i] ? 0 : 1);  d = Q[i][act[i]] - y;  td_abs[i] = |d|
+ *        (gamma_row given: gamma_row[i] in place of gamma)
  *   huber_delta = 0:  l = d * d,  g = 2 d
  *   huber_delta > 0:  l = |d| <= delta ? 0.5 (d * d) : delta (|d| - 0.5 delta),  g = min(max(d, -delta), delta)
  *   (l and g times w[i] with weights);  dQ[i][act[i]] = g / B;  loss = mean(l). */
@@ -599,6 +620,8 @@ typedef struct {
     const int32_t *sel;   /* [B] (grouped: [nets][B]) action whose target value bootstraps:
                              y uses Qt[i][sel[i]]; NULL: max_j Qt[i][j] */
     float huber_delta;    /* 0: squared error; > 0: Huber loss with this delta */
+    const float *gamma_row; /* [B] (grouped: [nets][B]) the row's discount in place of gamma in y
+                               (n-step rows: evx_replay_nstep's gamma^L); NULL: the scalar gamma */
 } evx_td_opts;
 /* evx_td_loss_zero_g with options (nets = 1: evx_td_loss_zero; zero = NULL: evx_td_loss_w);
  * opt = NULL: no options */
