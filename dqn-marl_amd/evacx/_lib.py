@@ -110,4 +110,5 @@ EXPORTS = ["evx_env_step", "evx_env_reset", "evx_obs_expand_f32", "evx_obs_expan
            "evx_env_order", "evx_act_perm", "evx_env_orders", "evx_env_classes", "evx_env_orders_push", "evx_env_orders_push_sample",
            "evx_env_step_occupancy", "evx_replay_nstep",
            "evx_episode_init", "evx_episode_update", "evx_episode_discard", "evx_episode_reduce",
-           "evx_episode_last_error"]
+           "evx_episode_last_error",
+           "evx_health_init", "evx_health_update", "evx_health_reduce", "evx_health_last_error"]

@@ -1,0 +1,164 @@
+"""Terminal health on the device (csrc/health.hip, ``evx_health_*`` in include/evacx.h).
+
+The reference's strategy comparison prints ``EvacuationEnv.get_performance_metrics()`` per
+episode (envs/evacuation_env.py:290-309): ``avg_health`` = np.mean of the healths of the
+persons that are not dead, ``min_health`` = their min (100 with none). ``HealthStats`` takes
+the same numbers from a VecEnv's ``pk`` / ``health`` where ``done`` is set -- after the step and
+before the reset, so the envs are stepped with ``auto_reset=False`` and reset with the device
+mask afterwards -- one launch per step and no host sync. ``avg_health`` equals np.mean bit for
+bit (numpy's summation order is stated in include/evacx.h).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from . import _lib
+from .env import _ptr, _stream
+from .episodes import _need
+
+MAX_P = 16383   # EVX_HEALTH_MAX_P
+ROW_WORDS = 6   # sizeof(evx_health_row) / 8
+
+_I64 = ("n_total", "w_n", "w_has", "w_alive")
+_F64 = ("w_avg", "w_min", "w_lo", "last_avg", "last_min")
+_I32 = ("last_alive",)
+_TAB = ("tab_avg", "tab_min", "tab_alive")
+
+
+class evx_health(C.Structure):
+    _fields_ = [("E", C.c_int32), ("tab_slots", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ["n_total", "w_n", "w_has", "w_alive", "w_avg", "w_min", "w_lo", "last_avg",
+                                         "last_min", "last_alive", "tab_avg", "tab_min", "tab_alive"]]
+
+
+_inited = False
+
+
+def hlib():
+    global _inited
+    L = _lib.lib()
+    if not _inited:
+        P = C.POINTER(evx_health)
+        L.evx_health_last_error.restype = C.c_char_p
+        L.evx_health_init.argtypes = [P, C.c_void_p]
+        L.evx_health_update.argtypes = [P, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        L.evx_health_reduce.argtypes = [P, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        for name in ("evx_health_init", "evx_health_update", "evx_health_reduce"):
+            getattr(L, name).restype = C.c_int
+        _inited = True
+    return L
+
+
+def hcheck(rc, what):
+    if rc != 0:
+        raise _lib.EvacxError(f"{what} failed ({rc}): {hlib().evx_health_last_error().decode()}")
+
+
+def _row_dict(irow, frow) -> dict:
+    n, has = int(irow[0]), int(irow[1])
+    d = dict(episodes=n, health_episodes=has, avg_health=None, min_health_mean=None, min_health=None,
+             alive_mean=None, alive_sum=int(irow[2]), avg_health_sum=float(frow[3]), min_health_sum=float(frow[4]))
+    if has > 0:
+        d["avg_health"] = d["avg_health_sum"] / has
+    if n > 0:
+        d.update(min_health_mean=d["min_health_sum"] / n, min_health=float(frow[5]), alive_mean=d["alive_sum"] / n)
+    return d
+
+
+class _Slice:
+    """``n`` envs of a HealthStats from env ``lo``: the same buffers through offset pointers."""
+
+    def __init__(self, owner: "HealthStats", lo: int, n: int):
+        self.owner, self.lo, self.E = owner, lo, n
+        K = owner.record
+        self.c = evx_health(E=n, tab_slots=K)
+        for name in _I64 + _F64 + _I32:
+            setattr(self.c, name, _ptr(getattr(owner, name)[lo:lo + n]))
+        if K:
+            for name in _TAB:
+                setattr(self.c, name, _ptr(getattr(owner, name)[lo:lo + n]))
+
+    def update(self, env_or_tensors, done: torch.Tensor):
+        """Fold the finished episodes of these envs: ``env_or_tensors`` is a VecEnv (its ``pk`` and
+        ``health``) or a pair (pk int32 [E, P], health float64 [E, P]) as the step left them, ``done``
+        the step's uint8 flags. One launch on the current stream; envs with done == 0 are untouched."""
+        if isinstance(env_or_tensors, (tuple, list)):
+            pk, health = env_or_tensors
+        else:
+            pk, health = env_or_tensors.pk, env_or_tensors.health
+        dev, P = self.owner.device, self.owner.P
+        _need("pk", pk, self.E * P, torch.int32, dev)
+        _need("health", health, self.E * P, torch.float64, dev)
+        _need("done", done, self.E, torch.uint8, dev)
+        hcheck(hlib().evx_health_update(C.byref(self.c), pk.data_ptr(), health.data_ptr(), P, done.data_ptr(),
+                                        self.owner.cap, _stream()), "health_update")
+
+
+class HealthStats(_Slice):
+    """Per-env terminal health of E envs of P people each; the arguments are EpisodeStats's.
+
+    Public per-env tensors: the window ``w_n``, ``w_has`` (episodes with somebody alive),
+    ``w_alive``, ``w_avg``, ``w_min`` (sums), ``w_lo`` (smallest min_health); the last finished
+    episode ``last_avg``, ``last_min``, ``last_alive``; the lifetime count ``n_total``; with
+    record = K the table ``tab_avg``, ``tab_min``, ``tab_alive`` [E, K]."""
+
+    def __init__(self, E: int, device, P: int, layout_idx: Optional[torch.Tensor] = None, n_layouts: int = 1,
+                 cap: int = 0, record: int = 0):
+        E, P, n_layouts, cap, record = int(E), int(P), int(n_layouts), int(cap), int(record)
+        if E < 1 or not 1 <= P <= MAX_P:
+            raise ValueError(f"HealthStats: E must be >= 1 and P 1..{MAX_P}, not {E}, {P}")
+        if cap < 0 or record < 0:
+            raise ValueError("HealthStats: cap and record must be >= 0")
+        if not 1 <= n_layouts <= 65535:
+            raise ValueError(f"HealthStats: n_layouts must be 1..65535, not {n_layouts}")
+        if n_layouts > 1 and layout_idx is None:
+            raise ValueError("HealthStats: several layouts need layout_idx")
+        device = torch.device(device)
+        if layout_idx is not None:
+            _need("layout_idx", layout_idx, E, torch.int32, None)
+            if layout_idx.device.type != device.type:
+                raise ValueError(f"layout_idx: on {layout_idx.device}, the statistics are on {device}")
+        self.P, self.n_layouts, self.cap, self.record = P, n_layouts, cap, record
+        self.layout_idx = layout_idx
+        for name in _I64:
+            setattr(self, name, torch.zeros(E, dtype=torch.int64, device=device))
+        for name in _F64:
+            setattr(self, name, torch.zeros(E, dtype=torch.float64, device=device))
+        for name in _I32:
+            setattr(self, name, torch.zeros(E, dtype=torch.int32, device=device))
+        if record:
+            self.tab_avg = torch.zeros(E, record, dtype=torch.float64, device=device)
+            self.tab_min = torch.zeros(E, record, dtype=torch.float64, device=device)
+            self.tab_alive = torch.zeros(E, record, dtype=torch.int32, device=device)
+        self.device = self.w_avg.device  # with its index
+        self.rows = torch.zeros((n_layouts + 1) * ROW_WORDS, dtype=torch.int64, device=device)
+        super().__init__(self, 0, E)
+        hcheck(hlib().evx_health_init(C.byref(self.c), _stream()), "health_init")
+
+    def view(self, lo: int, n: int) -> _Slice:
+        """The slice object of envs [lo, lo + n): its update touches only those."""
+        lo, n = int(lo), int(n)
+        if lo < 0 or n < 1 or lo + n > self.E:
+            raise ValueError(f"view: envs [{lo}, {lo + n}) are not within 0..{self.E}")
+        return _Slice(self, lo, n)
+
+    def summary(self, clear: bool = True) -> dict:
+        """Reduce the window over envs (one launch, plus one that empties the window when
+        ``clear``), copy the rows to the host (this waits for the current stream) and return the
+        "all" row: ``episodes``, ``health_episodes`` (the ones with somebody alive), ``avg_health``
+        (mean of avg_health over those, None if none), ``min_health_mean``, ``min_health`` (the
+        smallest), ``alive_mean`` (None with no episode), the raw sums, and ``per_layout``."""
+        hcheck(hlib().evx_health_reduce(C.byref(self.c), _ptr(self.layout_idx), self.n_layouts, self.rows.data_ptr(),
+                                        int(bool(clear)), _stream()), "health_reduce")
+        host = self.rows.cpu()
+        irows = host.view(self.n_layouts + 1, ROW_WORDS).tolist()
+        frows = host.view(torch.float64).view(self.n_layouts + 1, ROW_WORDS).tolist()
+        out = _row_dict(irows[-1], frows[-1])
+        out["per_layout"] = [_row_dict(irows[l], frows[l]) for l in range(self.n_layouts)]
+        return out
+
+
+__all__ = ["HealthStats", "evx_health", "MAX_P"]

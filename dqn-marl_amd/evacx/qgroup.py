@@ -182,6 +182,24 @@ class GroupedLearner:
         """Net g's parameters in DQNNetwork's state_dict order (evacx.qnet.FlatParams)."""
         return self.online[g].state_dict()
 
+    def load_state_dict(self, g: int, sd):
+        """The counterpart of state_dict(g): net g's online parameters from the reference's
+        ``q_network`` dict of an MLP (fc1 / fc2 / fc3 weight and bias), then its operand copies are
+        repacked. The target net keeps its weights (sync_target([g]) copies them over). A missing
+        key or another shape is refused before anything is written."""
+        if not 0 <= int(g) < self.G:
+            raise ValueError(f"load_state_dict: g must be 0..{self.G - 1}, not {g}")
+        for k, shape in self.shapes.items():
+            if k not in sd:
+                raise ValueError(f"load_state_dict: {k} is missing (an MLP q_network dict is needed)")
+            if tuple(sd[k].shape) != tuple(shape):
+                raise ValueError(f"load_state_dict: {k} has shape {tuple(sd[k].shape)}, the net's is {tuple(shape)}")
+        extra = [k for k in sd if k not in self.shapes]
+        if extra:
+            raise ValueError(f"load_state_dict: unexpected {extra[0]} (an MLP q_network dict is needed)")
+        self.online[g].load_state_dict(sd)
+        self.fast.nets[g].repack()
+
 
 class GroupedQMix:
     """QMIX learn step (runners/train_qmix.py:78-118) on a GroupedLearner of n agents: the agents'

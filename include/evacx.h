@@ -735,6 +735,66 @@ int evx_episode_reduce(const evx_episodes *ep, const int32_t *layout_idx, int32_
                        evx_episode_row *out, int32_t clear, void *stream);
 const char *evx_episode_last_error(void);
 
+/* ---- Terminal health (csrc/health.hip): EvacuationEnv.get_performance_metrics()'s avg_health
+ * and min_health (envs/evacuation_env.py:290-309) of every finished episode, taken on the device
+ * from the persons' pk / health as the step left them and before any reset (step with resets
+ * apart, evx_health_update, then evx_env_reset with the done mask). Per env, like evx_episodes:
+ * an env's numbers depend on its own episodes only, and a part of the envs is a descriptor
+ * whose pointers are offset to its first env. The lifetime count is its own, so the result does
+ * not depend on whether the update runs before or after evx_episode_update. */
+typedef struct {
+    int32_t E;
+    int32_t tab_slots;     /* K: episodes per env the health table holds (0 = no table) */
+    int64_t *n_total;      /* episodes seen since evx_health_init (never cleared) */
+    /* the window: episodes folded since the last clear */
+    int64_t *w_n;          /* episodes */
+    int64_t *w_has;        /* episodes among them with alive > 0 (the ones that have an avg_health) */
+    int64_t *w_alive;      /* sum of alive */
+    double *w_avg;         /* sum of avg_health over the episodes that have one, in episode order */
+    double *w_min;         /* sum of min_health, in episode order */
+    double *w_lo;          /* smallest min_health (+inf when empty) */
+    /* the last finished episode */
+    double *last_avg, *last_min;
+    int32_t *last_alive;
+    /* optional table [E][K]: the env's episode with lifetime index k < K in slot k */
+    double *tab_avg, *tab_min;
+    int32_t *tab_alive;
+} evx_health;
+
+/* One row of evx_health_reduce: the window summed over a set of envs. */
+typedef struct {
+    int64_t episodes, health_episodes, alive_sum;
+    double avg_sum, min_sum, min_min;
+} evx_health_row;
+
+/* the largest P evx_health_update takes (the env's own bound) */
+#define EVX_HEALTH_MAX_P 16383
+
+/* Everything zeroed: empty window (w_lo +inf), last-episode slots 0, lifetime 0. */
+int evx_health_init(const evx_health *h, void *stream);
+/* One launch, one wave per env of h; an env with done[e] == 0 is left untouched. For the others,
+ * from pk[e][0..P) and health[e][0..P) (any [E][P] arrays; P 1..EVX_HEALTH_MAX_P):
+ *   alive      = persons whose dead bit (pk bit 25) is clear (evacuated persons count);
+ *   min_health = the smallest health among them, 100.0 when there are none;
+ *   avg_health = np.mean of their healths in person order, bit for bit: the compacted list is
+ *                cut into consecutive chunks of 8192, each chunk is summed with numpy's pairwise
+ *                sum (n < 8 a plain loop from 0.0; n <= 128 eight strided accumulators combined
+ *                as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the tail in order; else split at
+ *                n/2 rounded down to a multiple of 8), the chunk sums are added left to right
+ *                onto the first and the total is divided by alive; NaN when alive == 0.
+ * The three values go to the last-episode slots, to table slot n_total[e] if it is < tab_slots,
+ * and into the window unless cap > 0 and n_total[e] >= cap (evx_episode_update's rule); then
+ * n_total[e] is bumped. No atomics, no host sync. */
+int evx_health_update(const evx_health *h, const int32_t *pk, const double *health, int32_t P, const uint8_t *done,
+                      int64_t cap, void *stream);
+/* The window summed over envs into out[0 .. n_layouts] (rows as in evx_episode_reduce) in the same
+ * fixed order: thread t of EVX_EPISODE_REDUCE_SPAN adds the row's envs t, t + SPAN, ... ascending
+ * onto 0.0, then the thread sums are added pairwise, s[t] = s[t] + s[t + h] for h = SPAN/2, ..., 1.
+ * Integer fields are exact. clear != 0: the window arrays are emptied by a second launch. */
+int evx_health_reduce(const evx_health *h, const int32_t *layout_idx, int32_t n_layouts, evx_health_row *out,
+                      int32_t clear, void *stream);
+const char *evx_health_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

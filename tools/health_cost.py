@@ -1,0 +1,54 @@
+"""Evaluator steps per second with and without the health metrics.
+
+One measurement per process: builds the shape's layout, runs one small warm-up evaluation
+(kernel loading), then times whole ``evacx.evaluate`` calls (host clock, the call ends in a
+device-to-host copy) and prints one JSON line: steps, seconds and steps per second of every
+repeat. ``--root DIR`` measures another checkout of the repository (e.g. the parent commit,
+built), so one session can alternate the two.
+
+Usage: python tools/health_cost.py [--metrics] [--root DIR] [--grid 64 --people 569 --robots 8 --envs 4096]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--root", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    ap.add_argument("--metrics", action="store_true")
+    ap.add_argument("--grid", type=int, default=64)
+    ap.add_argument("--people", type=int, default=569)
+    ap.add_argument("--robots", type=int, default=8)
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--episodes", type=int, default=1)
+    ap.add_argument("--policy", type=int, default=4)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--label", default="")
+    args = ap.parse_args()
+    root = os.path.abspath(args.root)
+    sys.path[:0] = [root, os.path.join(root, "dqn-marl_amd")]
+    import torch
+    from evacx.env import DeviceLayout
+    from evacx.evaluate import evaluate
+    from evacx.layout import build_tables, synthetic
+    kw = dict(metrics=True) if args.metrics else {}
+    lay = DeviceLayout(build_tables(synthetic(args.grid, args.grid, args.robots)), args.people)
+    evaluate(lay, 64, 1, args.policy, **kw)
+    torch.cuda.synchronize()
+    runs = []
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        ev = evaluate(lay, args.envs, args.episodes, args.policy, **kw)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        runs.append(dict(steps=ev["steps"], seconds=round(dt, 4), steps_per_s=round(ev["steps"] / dt, 1)))
+    print(json.dumps(dict(label=args.label, root=root, metrics=args.metrics, envs=args.envs, grid=args.grid,
+                          people=args.people, robots=args.robots, runs=runs,
+                          avg_health=ev.get("avg_health"), death_rate=ev["death_rate"])))
+
+
+if __name__ == "__main__":
+    main()
