@@ -32,6 +32,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from learn_util import torch_q as _torch_q, torch_q_gated as _torch_q_gated
+
 pytestmark = pytest.mark.gpu
 
 
@@ -118,23 +120,7 @@ def test_cfg5_env_at_bench_scale():
 
 
 # ------------------------------------------------------------------------- learn
-def _torch_q(sd, X, mask):
-    h = F.relu(F.linear(X, sd["fc1.weight"], sd["fc1.bias"]))
-    if mask is not None:
-        h = h * mask.float() / 0.8
-    h = F.relu(F.linear(h, sd["fc2.weight"], sd["fc2.bias"]))
-    return F.linear(h, sd["fc3.weight"], sd["fc3.bias"])
-
-
-def _torch_q_gated(sd, X, g1, g2):
-    """The same network with the ReLU/dropout pattern given (g1: keep AND fc1 > 0, g2: fc2 > 0) --
-    the device's own pattern, so autograd walks the branches the device's backward walked."""
-    z1 = F.linear(X, sd["fc1.weight"], sd["fc1.bias"])
-    h1 = z1 * g1 / 0.8
-    z2 = F.linear(h1, sd["fc2.weight"], sd["fc2.bias"])
-    return F.linear(z2 * g2, sd["fc3.weight"], sd["fc3.bias"]), z1, z2
-
-
+# (_torch_q, _torch_q_gated: the torch restatements, shared through tests/learn_util.py)
 @pytest.mark.parametrize("B,table", [(8192, False), (8192, True), (32768, False), (32768, True)])
 def test_x3_learn_at_bench_batch(B, table):
     """Two learn steps (each from the same parameters and Adam moments on both sides) at the
