@@ -3355,15 +3355,8 @@ static int heavy_cap(const evx_layout& l, int* hmin) {
 }
 
 namespace {
-thread_local char g_err[512] = "";
-int fail(int code, const char* msg) {
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-int hip_fail(hipError_t e, const char* what) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return -5;
-}
+using evxh::fail;
+using evxh::hip_status;
 int check_layout(const evx_layout* l) {
     if (!l) return fail(-22, "layout is NULL");
     if (l->L < 3 || l->W < 3 || l->L > 4000 || l->W > 4000) return fail(-22, "grid size out of range");
@@ -3434,7 +3427,7 @@ int step_select(const evx_layout& l, const evx_state& s, StepLaunch* sl) {
 
 extern "C" {
 
-const char* evx_last_error(void) { return g_err; }
+const char* evx_last_error(void) { return evxh::g_err; }
 
 int evx_env_step_occupancy(const evx_layout* l, const evx_state* s, int32_t* blocks_per_cu, int32_t* lds_bytes,
                            int32_t* block_threads) {
@@ -3447,7 +3440,7 @@ int evx_env_step_occupancy(const evx_layout* l, const evx_state* s, int32_t* blo
     int n = 0;
     const hipError_t e =
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)sl.fn, 64 * sl.nwb, sl.lds);
-    if (e != hipSuccess) return hip_fail(e, "env_step occupancy query");
+    if (e != hipSuccess) return hip_status("env_step occupancy query", e);
     *blocks_per_cu = n;
     *lds_bytes = (int32_t)sl.lds;
     *block_threads = 64 * sl.nwb;
@@ -3493,7 +3486,7 @@ int evx_env_step_part(const evx_layout* l, const evx_state* s, const int32_t* ac
     hipLaunchKernelGGL(sl.fn, dim3(nblk), dim3(64 * sl.nwb), sl.lds, (hipStream_t)stream, *l, *s, actions, *o, sl.hcap,
                        sl.pslots, (int)part);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "env_step launch");
+    return hip_status("env_step launch", e);
 }
 
 int evx_env_reset(const evx_layout* l, const evx_state* s, const uint8_t* mask, evx_obs* obs, int32_t* err,
@@ -3518,7 +3511,7 @@ int evx_env_reset(const evx_layout* l, const evx_state* s, const uint8_t* mask, 
         hipLaunchKernelGGL(evx::env_reset_kernel<false>, dim3(s->E), dim3(64), lds, (hipStream_t)stream, *l, *s, mask,
                            obs, err);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "env_reset launch");
+    return hip_status("env_reset launch", e);
 }
 
 // The scheduling permutations' workspace in evx_state.perm_ws: the class byte of every env.
@@ -3542,7 +3535,7 @@ int evx_diag_sort_keys(uint32_t* keys, uint32_t* pad, int32_t n, void* stream) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(evx::diag_sort_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, keys, pad, n);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "diag_sort_keys launch");
+    return hip_status("diag_sort_keys launch", e);
 }
 
 static int launch_orders(const evx_layout* l, const evx_state* s, int32_t* order, int32_t* perm, hipStream_t st) {
@@ -3556,7 +3549,7 @@ static int launch_orders(const evx_layout* l, const evx_state* s, int32_t* order
         hipLaunchKernelGGL(evx::env_orders_kernel<false>, grid, dim3(1024), 0, st, (const uint8_t*)s->perm_ws, s->E,
                            hcap, order, perm);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "env_orders launch");
+    return hip_status("env_orders launch", e);
 }
 
 int evx_env_order(const evx_layout* l, const evx_state* s, void* stream) {
@@ -3577,7 +3570,7 @@ int evx_env_order(const evx_layout* l, const evx_state* s, void* stream) {
     const size_t lds = ((size_t)s->E + 3) & ~(size_t)3;  // one bucket byte per env
     hipLaunchKernelGGL(evx::env_order_kernel, dim3(1), dim3(1024), lds, (hipStream_t)stream, *l, *s, hcap, hmin);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "env_order launch");
+    return hip_status("env_order launch", e);
 }
 
 int64_t evx_perm_ws_bytes(int32_t E) { return E > 0 ? perm_ws_need(E) : 0; }
@@ -3640,7 +3633,7 @@ int evx_env_orders_push_sample(const evx_layout* l, const evx_state* s, int32_t*
         hipLaunchKernelGGL(evx::env_orders_push_kernel<false>, dim3(nblk), dim3(1024), 0, (hipStream_t)stream,
                            (const uint8_t*)s->perm_ws, s->E, hcap, s->order, perm, nord, nsmp, pa, sa);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "env_orders_push launch");
+    return hip_status("env_orders_push launch", e);
 }
 
 int evx_env_classes(const evx_layout* l, const evx_state* s, void* stream) {
@@ -3651,7 +3644,7 @@ int evx_env_classes(const evx_layout* l, const evx_state* s, void* stream) {
     hipLaunchKernelGGL(evx::env_classes_kernel, dim3((unsigned)((s->E + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        *l, *s);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "env_classes launch");
+    return hip_status("env_classes launch", e);
 }
 
 int evx_obs_expand_f32(const evx_layout* l, const evx_obs* obs, int64_t n, float* out, void* stream) {
@@ -3663,7 +3656,7 @@ int evx_obs_expand_f32(const evx_layout* l, const evx_obs* obs, int64_t n, float
     hipLaunchKernelGGL(evx::obs_expand_kernel<float>, dim3((unsigned)((total / 6 + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, *l, obs, n, out);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "obs_expand launch");
+    return hip_status("obs_expand launch", e);
 }
 
 int evx_obs_expand_f64(const evx_layout* l, const evx_obs* obs, int64_t n, double* out, void* stream) {
@@ -3674,7 +3667,7 @@ int evx_obs_expand_f64(const evx_layout* l, const evx_obs* obs, int64_t n, doubl
     hipLaunchKernelGGL(evx::obs_expand_kernel<double>, dim3((unsigned)((total / 6 + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, *l, obs, n, out);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "obs_expand launch");
+    return hip_status("obs_expand launch", e);
 }
 
 // random.seed(int) -> init_by_array([seed]); numpy RandomState(int) -> init_genrand

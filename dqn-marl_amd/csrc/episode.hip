@@ -16,6 +16,7 @@
 #include <stdio.h>
 
 #include "evacx.h"
+#include "evx_host.h"
 
 namespace evxe {
 
@@ -189,36 +190,27 @@ __global__ __launch_bounds__(RT) void episode_reduce_kernel(evx_episodes ep, con
 }  // namespace evxe
 
 namespace {
-thread_local char g_eerr[256] = "";
-int efail(int code, const char* msg) {
-    snprintf(g_eerr, sizeof(g_eerr), "%s", msg);
-    return code;
-}
-int elaunch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_eerr, sizeof(g_eerr), "%s: %s", what, hipGetErrorString(e));
-    return -5;
-}
+using evxh::fail;
+using evxh::hip_status;
 int check_ep(const evx_episodes* ep, const char* who) {
     static thread_local char msg[128];
     if (!ep) {
         snprintf(msg, sizeof(msg), "%s: NULL episode descriptor", who);
-        return efail(-22, msg);
+        return fail(-22, msg);
     }
     if (ep->E < 1) {
         snprintf(msg, sizeof(msg), "%s: E must be >= 1", who);
-        return efail(-22, msg);
+        return fail(-22, msg);
     }
     if (!ep->ret || !ep->len || !ep->w_n || !ep->w_len || !ep->w_evac || !ep->w_dead || !ep->w_ret || !ep->w_ret2 ||
         !ep->w_min || !ep->w_max || !ep->last_ret || !ep->last_len || !ep->last_evac || !ep->last_dead ||
         !ep->n_total) {
         snprintf(msg, sizeof(msg), "%s: NULL episode buffer", who);
-        return efail(-22, msg);
+        return fail(-22, msg);
     }
     if (ep->tab_slots < 0 || (ep->tab_slots > 0 && (!ep->tab_ret || !ep->tab_len || !ep->tab_evac || !ep->tab_dead))) {
         snprintf(msg, sizeof(msg), "%s: episode table slots without its buffers", who);
-        return efail(-22, msg);
+        return fail(-22, msg);
     }
     return 0;
 }
@@ -227,44 +219,44 @@ unsigned blocks(int32_t E) { return (unsigned)((E + evxe::NT - 1) / evxe::NT); }
 
 extern "C" {
 
-const char* evx_episode_last_error(void) { return g_eerr; }
+const char* evx_episode_last_error(void) { return evxh::g_err; }
 
 int evx_episode_init(const evx_episodes* ep, void* stream) {
     if (int rc = check_ep(ep, "episode_init")) return rc;
     hipLaunchKernelGGL(evxe::episode_clear_kernel, dim3(blocks(ep->E)), dim3(evxe::NT), 0, (hipStream_t)stream, *ep,
                        1);
-    return elaunch("episode_init");
+    return hip_status("episode_init");
 }
 
 int evx_episode_update(const evx_episodes* ep, const double* reward, const uint8_t* done, const int32_t* counts,
                        int64_t cap, void* stream) {
     if (int rc = check_ep(ep, "episode_update")) return rc;
-    if (!reward || !done || !counts) return efail(-22, "episode_update: NULL reward, done or counts");
+    if (!reward || !done || !counts) return fail(-22, "episode_update: NULL reward, done or counts");
     hipLaunchKernelGGL(evxe::episode_update_kernel, dim3(blocks(ep->E)), dim3(evxe::NT), 0, (hipStream_t)stream, *ep,
                        reward, done, counts, cap);
-    return elaunch("episode_update");
+    return hip_status("episode_update");
 }
 
 int evx_episode_discard(const evx_episodes* ep, const uint8_t* mask, void* stream) {
     if (int rc = check_ep(ep, "episode_discard")) return rc;
     hipLaunchKernelGGL(evxe::episode_discard_kernel, dim3(blocks(ep->E)), dim3(evxe::NT), 0, (hipStream_t)stream, *ep,
                        mask);
-    return elaunch("episode_discard");
+    return hip_status("episode_discard");
 }
 
 int evx_episode_reduce(const evx_episodes* ep, const int32_t* layout_idx, int32_t n_layouts, int64_t cap,
                        evx_episode_row* out, int32_t clear, void* stream) {
     if (int rc = check_ep(ep, "episode_reduce")) return rc;
-    if (!out) return efail(-22, "episode_reduce: NULL output rows");
-    if (n_layouts < 1 || n_layouts > 65535) return efail(-22, "episode_reduce: n_layouts must be 1..65535");
-    if (n_layouts > 1 && !layout_idx) return efail(-22, "episode_reduce: several layouts need layout_idx");
+    if (!out) return fail(-22, "episode_reduce: NULL output rows");
+    if (n_layouts < 1 || n_layouts > 65535) return fail(-22, "episode_reduce: n_layouts must be 1..65535");
+    if (n_layouts > 1 && !layout_idx) return fail(-22, "episode_reduce: several layouts need layout_idx");
     const hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(evxe::episode_reduce_kernel, dim3((unsigned)n_layouts + 1), dim3(evxe::RT), 0, st, *ep,
                        layout_idx, n_layouts, cap, out);
-    if (int rc = elaunch("episode_reduce")) return rc;
+    if (int rc = hip_status("episode_reduce")) return rc;
     if (clear) {  // after every row's workgroup has read the window (stream order)
         hipLaunchKernelGGL(evxe::episode_clear_kernel, dim3(blocks(ep->E)), dim3(evxe::NT), 0, st, *ep, 0);
-        return elaunch("episode_reduce (clear)");
+        return hip_status("episode_reduce (clear)");
     }
     return 0;
 }

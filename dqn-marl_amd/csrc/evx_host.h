@@ -1,5 +1,5 @@
-// Host-side helpers shared by the C-ABI entry points: per-device one-time work and device
-// properties. A process may drive several GPUs through the C-ABI (one device per thread, or a
+// Host-side helpers shared by the C-ABI entry points: the error text, per-device one-time work
+// and device properties. A process may drive several GPUs through the C-ABI (one device per thread, or a
 // loop over devices), so nothing here is a per-process flag: kernel attributes are set once per
 // device, the CU count is cached per device, and both are safe to call from several threads.
 #pragma once
@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <stdint.h>
+#include <stdio.h>
 
 namespace evxh {
 
@@ -31,6 +32,22 @@ inline void max_lds_once(std::atomic<uint64_t>& done, const void* const* kernels
     once_per_device(done, [&] {
         for (int i = 0; i < n; i++) (void)hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     });
+}
+
+// The C-ABI's error text: the message of the calling thread's last failed call, whichever entry
+// point it came from. evx_last_error() and the per-family getters all return this buffer.
+inline thread_local char g_err[512] = "";
+
+inline int fail(int code, const char* msg) {
+    snprintf(g_err, sizeof(g_err), "%s", msg);
+    return code;
+}
+
+// 0 when e (default: the pending launch error) is hipSuccess, else -5 with "<what>: <hip's text>".
+inline int hip_status(const char* what, hipError_t e = hipGetLastError()) {
+    if (e == hipSuccess) return 0;
+    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
+    return -5;
 }
 
 // Compute units of the current device (cached per device; 256 if the query fails).

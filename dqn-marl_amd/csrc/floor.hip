@@ -22,7 +22,6 @@
 
 #include <cmath>
 #include <cstdio>
-#include <string>
 
 #include "evacx.h"
 #include "evx_host.h"
@@ -31,11 +30,7 @@ namespace evxf {
 constexpr int NT = 1024;
 constexpr int LDS_CELLS = 18432;
 
-static std::string g_err;
-static int fail(int code, const std::string& m) {
-    g_err = m;
-    return code;
-}
+using evxh::fail;
 
 // MoveTO (envs/map.py:11-19): index < 4 orthogonal (cost 1.0), else diagonal (1.4)
 __constant__ int MDX[8] = {1, 0, -1, 0, 1, -1, -1, 1};
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(NT) void floor_kernel(int GX, int GY, const uint8_t
 
 extern "C" {
 
-const char* evx_floor_last_error(void) { return evxf::g_err.c_str(); }
+const char* evx_floor_last_error(void) { return evxh::g_err; }
 
 int evx_floor_field(int32_t n_layouts, int32_t GX, int32_t GY, const uint8_t* valid, const uint8_t* source,
                     const double* pen, double* floor, int32_t* passes, void* stream) {
@@ -135,9 +130,7 @@ int evx_floor_field(int32_t n_layouts, int32_t GX, int32_t GY, const uint8_t* va
         hipLaunchKernelGGL(floor_kernel<false>, dim3(n_layouts), dim3(NT), 0, s, GX, GY, valid, source, pen, floor,
                            passes, max_passes);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-5, std::string("floor_field launch: ") + hipGetErrorString(e));
-    return 0;
+    return evxh::hip_status("floor_field launch");
 }
 
 }  // extern "C"

@@ -17,7 +17,10 @@
 
 #include "evacx.h"
 #include "evx_device.h"
+#include "evx_host.h"
 
+// (this file's kernels and constants share the name evxh with evx_host.h's host helpers -- the
+// error text, fail, hip_status -- which the entry points below use; the two sets do not overlap)
 namespace evxh {
 
 constexpr int NT = 256;                      // init / clear: one env per thread
@@ -214,35 +217,26 @@ __global__ __launch_bounds__(RT) void health_reduce_kernel(evx_health h, const i
 }  // namespace evxh
 
 namespace {
-thread_local char g_herr[256] = "";
-int hfail(int code, const char* msg) {
-    snprintf(g_herr, sizeof(g_herr), "%s", msg);
-    return code;
-}
-int hlaunch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_herr, sizeof(g_herr), "%s: %s", what, hipGetErrorString(e));
-    return -5;
-}
+using evxh::fail;
+using evxh::hip_status;
 int check_h(const evx_health* h, const char* who) {
     static thread_local char msg[128];
     if (!h) {
         snprintf(msg, sizeof(msg), "%s: NULL health descriptor", who);
-        return hfail(-22, msg);
+        return fail(-22, msg);
     }
     if (h->E < 1) {
         snprintf(msg, sizeof(msg), "%s: E must be >= 1", who);
-        return hfail(-22, msg);
+        return fail(-22, msg);
     }
     if (!h->n_total || !h->w_n || !h->w_has || !h->w_alive || !h->w_avg || !h->w_min || !h->w_lo || !h->last_avg ||
         !h->last_min || !h->last_alive) {
         snprintf(msg, sizeof(msg), "%s: NULL health buffer", who);
-        return hfail(-22, msg);
+        return fail(-22, msg);
     }
     if (h->tab_slots < 0 || (h->tab_slots > 0 && (!h->tab_avg || !h->tab_min || !h->tab_alive))) {
         snprintf(msg, sizeof(msg), "%s: health table slots without its buffers", who);
-        return hfail(-22, msg);
+        return fail(-22, msg);
     }
     return 0;
 }
@@ -251,38 +245,38 @@ unsigned blocks(int32_t E) { return (unsigned)((E + evxh::NT - 1) / evxh::NT); }
 
 extern "C" {
 
-const char* evx_health_last_error(void) { return g_herr; }
+const char* evx_health_last_error(void) { return evxh::g_err; }
 
 int evx_health_init(const evx_health* h, void* stream) {
     if (int rc = check_h(h, "health_init")) return rc;
     hipLaunchKernelGGL(evxh::health_clear_kernel, dim3(blocks(h->E)), dim3(evxh::NT), 0, (hipStream_t)stream, *h, 1);
-    return hlaunch("health_init");
+    return hip_status("health_init");
 }
 
 int evx_health_update(const evx_health* h, const int32_t* pk, const double* health, int32_t P, const uint8_t* done,
                       int64_t cap, void* stream) {
     if (int rc = check_h(h, "health_update")) return rc;
-    if (!pk || !health || !done) return hfail(-22, "health_update: NULL pk, health or done");
-    if (P < 1 || P > EVX_HEALTH_MAX_P) return hfail(-22, "health_update: P must be 1..16383");
+    if (!pk || !health || !done) return fail(-22, "health_update: NULL pk, health or done");
+    if (P < 1 || P > EVX_HEALTH_MAX_P) return fail(-22, "health_update: P must be 1..16383");
     const size_t lds = (size_t)P * sizeof(double);  // the compacted healths
     hipLaunchKernelGGL(evxh::health_update_kernel, dim3((unsigned)h->E), dim3(evxh::WAVE), lds, (hipStream_t)stream,
                        *h, (const uint32_t*)pk, health, (int)P, done, cap);
-    return hlaunch("health_update");
+    return hip_status("health_update");
 }
 
 int evx_health_reduce(const evx_health* h, const int32_t* layout_idx, int32_t n_layouts, evx_health_row* out,
                       int32_t clear, void* stream) {
     if (int rc = check_h(h, "health_reduce")) return rc;
-    if (!out) return hfail(-22, "health_reduce: NULL output rows");
-    if (n_layouts < 1 || n_layouts > 65535) return hfail(-22, "health_reduce: n_layouts must be 1..65535");
-    if (n_layouts > 1 && !layout_idx) return hfail(-22, "health_reduce: several layouts need layout_idx");
+    if (!out) return fail(-22, "health_reduce: NULL output rows");
+    if (n_layouts < 1 || n_layouts > 65535) return fail(-22, "health_reduce: n_layouts must be 1..65535");
+    if (n_layouts > 1 && !layout_idx) return fail(-22, "health_reduce: several layouts need layout_idx");
     const hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(evxh::health_reduce_kernel, dim3((unsigned)n_layouts + 1), dim3(evxh::RT), 0, st, *h,
                        layout_idx, n_layouts, out);
-    if (int rc = hlaunch("health_reduce")) return rc;
+    if (int rc = hip_status("health_reduce")) return rc;
     if (clear) {  // after every row's workgroup has read the window (stream order)
         hipLaunchKernelGGL(evxh::health_clear_kernel, dim3(blocks(h->E)), dim3(evxh::NT), 0, st, *h, 0);
-        return hlaunch("health_reduce (clear)");
+        return hip_status("health_reduce (clear)");
     }
     return 0;
 }

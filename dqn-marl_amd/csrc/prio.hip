@@ -19,6 +19,7 @@
 #include <stdio.h>
 
 #include "evacx.h"
+#include "evx_host.h"
 
 namespace evxp {
 
@@ -187,21 +188,12 @@ __global__ __launch_bounds__(NT) void prio_sample_kernel(evx_replay rp, evx_prio
 }  // namespace evxp
 
 namespace {
-thread_local char g_perr[256] = "";
-int pfail(int code, const char* msg) {
-    snprintf(g_perr, sizeof(g_perr), "%s", msg);
-    return code;
-}
-int plaunch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_perr, sizeof(g_perr), "%s: %s", what, hipGetErrorString(e));
-    return -5;
-}
+using evxh::fail;
+using evxh::hip_status;
 int check_tree(const evx_prio* t) {
-    if (!t || !t->sum || !t->mn || !t->max_leaf || !t->owner) return pfail(-22, "prio: NULL tree");
+    if (!t || !t->sum || !t->mn || !t->max_leaf || !t->owner) return fail(-22, "prio: NULL tree");
     const int64_t C = t->capacity;
-    if (C < 1024 || C > ((int64_t)1 << 26) || (C & (C - 1))) return pfail(-22, "prio: capacity must be 2^10..2^26");
+    if (C < 1024 || C > ((int64_t)1 << 26) || (C & (C - 1))) return fail(-22, "prio: capacity must be 2^10..2^26");
     return 0;
 }
 // rebuild both trees over the leaf range [pos, pos + n) mod C (n >= C: everything),
@@ -219,7 +211,7 @@ int rebuild(const evx_prio* t, int64_t pos, int64_t n, int leaf_mode, int64_t n_
         if (nblk > nb) nblk = nb;
         hipLaunchKernelGGL(evxp::tree_pass_kernel, dim3((unsigned)nblk), dim3(evxp::NT), 0, st, *t, base, bl,
                            first % nb, leaf && leaf_mode, pos, n_new, n_hide);
-        int rc = plaunch("prio tree pass");
+        int rc = hip_status("prio tree pass");
         if (rc) return rc;
         if (nb == 1) return 0;
         base = nb;
@@ -232,18 +224,18 @@ int rebuild(const evx_prio* t, int64_t pos, int64_t n, int leaf_mode, int64_t n_
 
 extern "C" {
 
-const char* evx_prio_last_error(void) { return g_perr; }
+const char* evx_prio_last_error(void) { return evxh::g_err; }
 
 int evx_prio_init(const evx_prio* t, void* stream) {
     if (int rc = check_tree(t)) return rc;
     hipLaunchKernelGGL(evxp::prio_init_kernel, dim3((unsigned)((2 * t->capacity + evxp::NT - 1) / evxp::NT)),
                        dim3(evxp::NT), 0, (hipStream_t)stream, *t);
-    return plaunch("prio_init");
+    return hip_status("prio_init");
 }
 
 int evx_prio_set_range(const evx_prio* t, int64_t pos, int64_t n_new, int64_t n_hide, void* stream) {
     if (int rc = check_tree(t)) return rc;
-    if (n_new < 0 || n_hide < 0 || n_new + n_hide > t->capacity) return pfail(-22, "prio_set_range: bad counts");
+    if (n_new < 0 || n_hide < 0 || n_new + n_hide > t->capacity) return fail(-22, "prio_set_range: bad counts");
     if (n_new + n_hide == 0) return 0;
     pos &= t->capacity - 1;
     return rebuild(t, pos, n_new + n_hide, 1, n_new, n_hide, (hipStream_t)stream);
@@ -253,12 +245,12 @@ int evx_prio_update(const evx_prio* t, const int64_t* idx, const float* td_abs, 
                     void* stream) {
     if (int rc = check_tree(t)) return rc;
     if (B <= 0) return 0;
-    if (!idx || !td_abs) return pfail(-22, "prio_update: NULL argument");
+    if (!idx || !td_abs) return fail(-22, "prio_update: NULL argument");
     const hipStream_t st = (hipStream_t)stream;
     const unsigned g = (unsigned)((B + evxp::NT - 1) / evxp::NT);
     hipLaunchKernelGGL(evxp::prio_owner_kernel, dim3(g), dim3(evxp::NT), 0, st, *t, idx, B);
     hipLaunchKernelGGL(evxp::prio_leaf_kernel, dim3(g), dim3(evxp::NT), 0, st, *t, idx, td_abs, B, eps, alpha);
-    if (int rc = plaunch("prio_update")) return rc;
+    if (int rc = hip_status("prio_update")) return rc;
     return rebuild(t, 0, t->capacity, 0, 0, 0, st);
 }
 
@@ -266,12 +258,12 @@ int evx_prio_sample(const evx_replay* rp, const evx_prio* t, int32_t B, double b
                     evx_obs* s, evx_obs* s2, int32_t* a, float* r, uint8_t* done, int64_t* idx_out, float* w_out,
                     void* stream) {
     if (int rc = check_tree(t)) return rc;
-    if (!rp || rp->capacity != t->capacity) return pfail(-22, "prio_sample: ring and tree capacities differ");
+    if (!rp || rp->capacity != t->capacity) return fail(-22, "prio_sample: ring and tree capacities differ");
     if (B <= 0) return 0;
-    if (!s || !s2 || !a || !r || !done) return pfail(-22, "prio_sample: NULL output");
+    if (!s || !s2 || !a || !r || !done) return fail(-22, "prio_sample: NULL output");
     hipLaunchKernelGGL(evxp::prio_sample_kernel, dim3((unsigned)((B + evxp::NT - 1) / evxp::NT)), dim3(evxp::NT), 0,
                        (hipStream_t)stream, *rp, *t, B, beta, seed, offset, s, s2, a, r, done, idx_out, w_out);
-    return plaunch("prio_sample");
+    return hip_status("prio_sample");
 }
 
 }  // extern "C"

@@ -159,16 +159,12 @@ __global__ __launch_bounds__(256) void qmix_reduce_kernel(const float* __restric
 }  // namespace evxx
 
 namespace {
-thread_local char x_err[256] = "";
-int xfail(int code, const char* msg) {
-    snprintf(x_err, sizeof(x_err), "%s", msg);
-    return code;
-}
+using evxh::fail;
 }  // namespace
 
 extern "C" {
 
-const char* evx_qmix_last_error(void) { return x_err; }
+const char* evx_qmix_last_error(void) { return evxh::g_err; }
 
 int32_t evx_qmix_nparams(int32_t n) { return evxx::mix_params(n); }
 
@@ -181,10 +177,10 @@ int evx_qmix_loss(const float* Q, const float* Qt, int32_t A, const int32_t* act
                   float gamma, int32_t B, int32_t n, const float* mix, const float* mix_t, float* dQ, float* mix_grad,
                   float* loss, float* part, float* zero, int64_t nzero, void* stream) {
     if (B <= 0) return 0;
-    if (n < 1 || n > evxx::NMAX) return xfail(-22, "qmix_loss: 1..16 agents");
-    if (A < 1 || A > 64) return xfail(-22, "qmix_loss: 1..64 actions");
+    if (n < 1 || n > evxx::NMAX) return fail(-22, "qmix_loss: 1..16 agents");
+    if (A < 1 || A > 64) return fail(-22, "qmix_loss: 1..64 actions");
     if (!Q || !Qt || !act || !rew || !done || !mix || !mix_t || !dQ || !mix_grad || !loss || !part)
-        return xfail(-22, "qmix_loss: NULL argument");
+        return fail(-22, "qmix_loss: NULL argument");
     const int nrb = (B + evxx::ROWS - 1) / evxx::ROWS;
     const int nz = zero && nzero > 0 ? (int)std::min<int64_t>((nzero + 256 * 16 - 1) / (256 * 16), 512) : 0;
     const size_t lds = (size_t)evxx::ROWS * (n + 2 * evxx::EMB + 2) * 4;
@@ -197,12 +193,7 @@ int evx_qmix_loss(const float* Q, const float* Qt, int32_t A, const int32_t* act
     hipLaunchKernelGGL(evxx::qmix_rows_kernel, dim3(nrb + nz), dim3(evxx::ROWS), lds, st, Q, Qt, A, act, rew, done, gamma,
                        B, n, mix, mix_t, dQ, part, nrb, nz ? zero : nullptr, nzero);
     hipLaunchKernelGGL(evxx::qmix_reduce_kernel, dim3(1), dim3(256), 0, st, part, nrb, n, B, mix, mix_grad, loss);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(x_err, sizeof(x_err), "qmix_loss: %s", hipGetErrorString(e));
-        return -5;
-    }
-    return 0;
+    return evxh::hip_status("qmix_loss");
 }
 
 }  // extern "C"

@@ -2754,50 +2754,41 @@ __global__ __launch_bounds__(256) void sumsq_parts_kernel(const float* __restric
 
 // ===================================================================== C-ABI
 namespace {
-thread_local char m_err[256] = "";
-int mfail(int code, const char* msg) {
-    snprintf(m_err, sizeof(m_err), "%s", msg);
-    return code;
-}
-int mlaunch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(m_err, sizeof(m_err), "%s: %s", what, hipGetErrorString(e));
-    return -5;
-}
+using evxh::fail;
+using evxh::hip_status;
 }  // namespace
 
 extern "C" {
 
-const char* evx_qmlp_last_error(void) { return m_err; }
+const char* evx_qmlp_last_error(void) { return evxh::g_err; }
 
 int evx_qmlp_pack(const float* w1, const float* b1, const float* w2, uint16_t* w1b, float* b1c, uint16_t* w2b,
                   uint16_t* w2t, uint16_t* w1o, void* stream) {
-    if (!w1 || !b1 || !w2 || !w1b || !b1c || !w2b) return mfail(-22, "qmlp_pack: NULL argument");
+    if (!w1 || !b1 || !w2 || !w1b || !b1c || !w2b) return fail(-22, "qmlp_pack: NULL argument");
     const int n = evxm::HID * evxm::K1P;
     hipLaunchKernelGGL(evxm::pack_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, w1, b1, w2,
                        reinterpret_cast<__bf16*>(w1b), b1c, reinterpret_cast<__bf16*>(w2b),
                        reinterpret_cast<__bf16*>(w2t), reinterpret_cast<__bf16*>(w1o));
-    return mlaunch("qmlp_pack");
+    return hip_status("qmlp_pack");
 }
 
 int evx_qmlp_pack_occ3(const float* w1, uint16_t* w1o, uint16_t* w1ol, void* stream) {
-    if (!w1 || !w1o || !w1ol) return mfail(-22, "qmlp_pack_occ3: NULL argument");
+    if (!w1 || !w1o || !w1ol) return fail(-22, "qmlp_pack_occ3: NULL argument");
     hipLaunchKernelGGL(evxm::pack_occ3_kernel, dim3(evxm::HID * 128 / 256), dim3(256), 0, (hipStream_t)stream, w1,
                        reinterpret_cast<__bf16*>(w1o), reinterpret_cast<__bf16*>(w1ol));
-    return mlaunch("qmlp_pack_occ3");
+    return hip_status("qmlp_pack_occ3");
 }
 
 int evx_qmlp_pack3(const float* w1, const float* b1, const float* w2, uint16_t* w1b, uint16_t* w1l, float* b1c,
                    uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl, void* stream) {
-    if (!w1 || !b1 || !w2 || !w1b || !w1l || !b1c || !w2b || !w2l) return mfail(-22, "qmlp_pack3: NULL argument");
-    if ((w2t == nullptr) != (w2tl == nullptr)) return mfail(-22, "qmlp_pack3: w2t and w2tl go together");
+    if (!w1 || !b1 || !w2 || !w1b || !w1l || !b1c || !w2b || !w2l) return fail(-22, "qmlp_pack3: NULL argument");
+    if ((w2t == nullptr) != (w2tl == nullptr)) return fail(-22, "qmlp_pack3: w2t and w2tl go together");
     const int n = evxm::HID * evxm::K1X;
     hipLaunchKernelGGL(evxm::pack3_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, w1, b1, w2,
                        reinterpret_cast<__bf16*>(w1b), reinterpret_cast<__bf16*>(w1l), b1c,
                        reinterpret_cast<__bf16*>(w2b), reinterpret_cast<__bf16*>(w2l), reinterpret_cast<__bf16*>(w2t),
                        reinterpret_cast<__bf16*>(w2tl));
-    return mlaunch("qmlp_pack3");
+    return hip_status("qmlp_pack3");
 }
 
 // the x3 act kernel for the dropout mode of a (fc1_slab_m)
@@ -2821,11 +2812,11 @@ static void launch_act3(const evxm::Fwd& a, int32_t n, int nets, hipStream_t st)
 
 static int make_fwd(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
                     const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, evxm::Fwd& a) {
-    if (!lay || !obs || !p || !out) return mfail(-22, "qmlp_forward: NULL argument");
-    if (!p->w1 || !p->b1c || !p->w2 || !p->b2 || !p->w3 || !p->b3) return mfail(-22, "qmlp_forward: missing parameter");
-    if (!out->h1) return mfail(-22, "qmlp_forward: h1 buffer required");
+    if (!lay || !obs || !p || !out) return fail(-22, "qmlp_forward: NULL argument");
+    if (!p->w1 || !p->b1c || !p->w2 || !p->b2 || !p->w3 || !p->b3) return fail(-22, "qmlp_forward: missing parameter");
+    if (!out->h1) return fail(-22, "qmlp_forward: h1 buffer required");
     if (!lay->danger_o32 || !lay->cellinfo || !lay->obs_feat)
-        return mfail(-22, "qmlp_forward: layout tables missing (obs_feat)");
+        return fail(-22, "qmlp_forward: layout tables missing (obs_feat)");
     a.N = n;
     a.obs = obs;
     a.cellinfo = lay->cellinfo;
@@ -2850,7 +2841,7 @@ static int make_fwd(const evx_layout* lay, const evx_obs* obs, int32_t n, const 
     a.drop_seed = drop ? drop->seed : 0u;
     a.drop_stream = drop ? drop->stream : 0u;
     a.drop_row0 = drop ? drop->row0 : 0u;
-    if (a.drop_row0 & 1u) return mfail(-22, "qmlp_forward: dropout row0 must be even (one hash per row pair)");
+    if (a.drop_row0 & 1u) return fail(-22, "qmlp_forward: dropout row0 must be even (one hash per row pair)");
     const float dp = drop ? drop->p : 0.f;
     a.drop_thresh = dp > 0.f ? (uint32_t)((double)dp * 65536.0) : 0u;  // 16-bit uniforms
     if (dp > 0.f && a.drop_thresh == 0u) a.drop_thresh = 1u;
@@ -2869,22 +2860,22 @@ static int make_fwd(const evx_layout* lay, const evx_obs* obs, int32_t n, const 
     a.stat_x0 = p->stat_nx > 0 ? p->stat_x0 : 0;
     a.stat_nx = p->stat_nx > 0 ? p->stat_nx : lay->L + 2;
     if (a.stat && (a.stat_x0 < 0 || a.stat_x0 + a.stat_nx > lay->L + 2))
-        return mfail(-22, "qmlp: the table's centre range must lie in [0, L + 2)");
+        return fail(-22, "qmlp: the table's centre range must lie in [0, L + 2)");
     a.raw = nullptr;
     a.rest_ws = nullptr;
     a.xin = nullptr;
     a.xtab = (p->x3 && a.stat) ? reinterpret_cast<const __bf16*>(p->stat_xin) : nullptr;
     a.drop_mask = drop ? drop->mask : nullptr;
-    if (a.drop_mask && !(dp > 0.f)) return mfail(-22, "qmlp_forward: an explicit dropout mask needs p > 0 (its scale)");
+    if (a.drop_mask && !(dp > 0.f)) return fail(-22, "qmlp_forward: an explicit dropout mask needs p > 0 (its scale)");
     a.feat_lo = nullptr;
     a.feats_lo = nullptr;
     a.w1l = a.w2l = nullptr;
     a.h1l = nullptr;
     a.w1ol = nullptr;
     if (p->x3) {
-        if (!p->w1l || !p->w2l) return mfail(-22, "qmlp_forward: x3 needs w1l / w2l (evx_qmlp_pack3)");
+        if (!p->w1l || !p->w2l) return fail(-22, "qmlp_forward: x3 needs w1l / w2l (evx_qmlp_pack3)");
         if (!lay->obs_feat_lo || (lay->layout_set && !lay->obs_feats_lo))
-            return mfail(-22, "qmlp_forward: x3 needs the layout's obs_feat_lo");
+            return fail(-22, "qmlp_forward: x3 needs the layout's obs_feat_lo");
         a.feat_lo = lay->obs_feat_lo;
         a.feats_lo = lay->layout_set ? lay->obs_feats_lo : nullptr;
         a.w1l = reinterpret_cast<const __bf16*>(p->w1l);
@@ -2898,7 +2889,7 @@ static int make_fwd(const evx_layout* lay, const evx_obs* obs, int32_t n, const 
     a.gn = 0;
     a.g = 0;
     // rows_per_env even: dropout row pairs stay together in a tile
-    if (a.perm && (a.rpe & 1)) return mfail(-22, "qmlp_forward: rows_per_env must be even (dropout row pairs)");
+    if (a.perm && (a.rpe & 1)) return fail(-22, "qmlp_forward: rows_per_env must be even (dropout row pairs)");
     return 0;
 }
 
@@ -2912,10 +2903,10 @@ static int launch_fwd(const evxm::Fwd& a0, const evxm::Fwd& a1, int32_t n, int p
             hipLaunchKernelGGL((evxm::qfc1_kernel<4, 1, 8, true, true>), dim3(big, 2, z), dim3(512), 0, st, a0, a1, pairs);
         else
             hipLaunchKernelGGL((evxm::qfc1_kernel<2, 1, 4, true, true>), dim3(blocks, 4, z), dim3(256), 0, st, a0, a1, pairs);
-        int rc = mlaunch("qfc1 grouped");
+        int rc = hip_status("qfc1 grouped");
         if (rc || !fc23) return rc;
         hipLaunchKernelGGL((evxm::qfc23_kernel<true, true>), dim3(blocks, 1, z), dim3(256), 0, st, a0, a1, pairs);
-        return mlaunch("qfc23 grouped");
+        return hip_status("qfc23 grouped");
     }
     if (x3) {  // f32-accurate: 128 x 256 tiles for large batches (register budget), else 64 x 128
         // one problem (the learner's online forward beside the target through the fused act):
@@ -2926,7 +2917,7 @@ static int launch_fwd(const evxm::Fwd& a0, const evxm::Fwd& a1, int32_t n, int p
             hipLaunchKernelGGL((evxm::qfc1_kernel<4, 1, 8, true>), dim3(big, 2, pairs), dim3(512), 0, st, a0, a1, pairs);
         else
             hipLaunchKernelGGL((evxm::qfc1_kernel<2, 1, 4, true>), dim3(blocks, 4, pairs), dim3(256), 0, st, a0, a1, pairs);
-        int rc = mlaunch("qfc1");
+        int rc = hip_status("qfc1");
         if (rc || !fc23) return rc;
         // 32-row tiles while 64-row ones would leave CUs without a workgroup (cfg2's B = 4096: learn
         // 0.133 -> 0.128 ms; fc1 in 32 x 64 tiles of 2 waves for small problems measured slower)
@@ -2935,16 +2926,16 @@ static int launch_fwd(const evxm::Fwd& a0, const evxm::Fwd& a1, int32_t n, int p
                                pairs);
         else
             hipLaunchKernelGGL(evxm::qfc23_kernel<true>, dim3(blocks, 1, pairs), dim3(256), 0, st, a0, a1, pairs);
-        return mlaunch("qfc23");
+        return hip_status("qfc23");
     }
     if (big * pairs >= 384)  // enough 128-row tiles (all 512 columns each) to fill the chip
         hipLaunchKernelGGL((evxm::qfc1_kernel<4, 2, 8>), dim3(big, 1, pairs), dim3(512), 0, st, a0, a1, pairs);
     else
         hipLaunchKernelGGL((evxm::qfc1_kernel<2, 1, 4>), dim3(blocks, 4, pairs), dim3(256), 0, st, a0, a1, pairs);
-    int rc = mlaunch("qfc1");
+    int rc = hip_status("qfc1");
     if (rc || !fc23) return rc;
     hipLaunchKernelGGL(evxm::qfc23_kernel<false>, dim3(blocks, 1, pairs), dim3(256), 0, st, a0, a1, pairs);
-    return mlaunch("qfc23");
+    return hip_status("qfc23");
 }
 
 int evx_qmlp_forward(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
@@ -3015,8 +3006,8 @@ static void act_x3(const evxm::Fwd& a, int32_t n, hipStream_t st, bool kernel64)
 static int qmlp_act_impl(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
                          const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream, bool kernel64) {
     if (n <= 0) return 0;
-    if (!out) return mfail(-22, "qmlp_act: NULL out");
-    if (!out->q && !out->actions) return mfail(-22, "qmlp_act: needs q or actions");
+    if (!out) return fail(-22, "qmlp_act: NULL out");
+    if (!out->q && !out->actions) return fail(-22, "qmlp_act: needs q or actions");
     evx_qmlp_fwd_out o = *out;
     o.h1 = o.h1 ? o.h1 : reinterpret_cast<uint16_t*>(1);  // unused: H1 stays in LDS
     o.x = nullptr;
@@ -3037,7 +3028,7 @@ static int qmlp_act_impl(const evx_layout* lay, const evx_obs* obs, int32_t n, c
     else
         hipLaunchKernelGGL(evxm::qact_kernel, dim3((unsigned)((n + 127) / 128)), dim3(512), evxm::ACT_LDS,
                            (hipStream_t)stream, a);
-    return mlaunch("qact");
+    return hip_status("qact");
 }
 
 extern "C" {
@@ -3056,9 +3047,9 @@ int evx_qmlp_act64(const evx_layout* lay, const evx_obs* obs, int32_t n, const e
 
 int evx_qmlp_expand_x3(const evx_layout* lay, const evx_obs* obs, int32_t n, uint16_t* x, void* stream) {
     if (n <= 0) return 0;
-    if (!lay || !obs || !x) return mfail(-22, "qmlp_expand_x3: NULL argument");
+    if (!lay || !obs || !x) return fail(-22, "qmlp_expand_x3: NULL argument");
     if (!lay->obs_feat || !lay->obs_feat_lo || (lay->layout_set && (!lay->obs_feats || !lay->obs_feats_lo)))
-        return mfail(-22, "qmlp_expand_x3: layout tables missing (obs_feat, obs_feat_lo)");
+        return fail(-22, "qmlp_expand_x3: layout tables missing (obs_feat, obs_feat_lo)");
     evxm::Fwd a{};
     a.N = n;
     a.obs = obs;
@@ -3072,15 +3063,15 @@ int evx_qmlp_expand_x3(const evx_layout* lay, const evx_obs* obs, int32_t n, uin
     a.x = reinterpret_cast<__bf16*>(x);
     const int64_t nx = (int64_t)n * 20;
     hipLaunchKernelGGL(evxm::x_expand_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return mlaunch("qmlp_expand_x3");
+    return hip_status("qmlp_expand_x3");
 }
 
 int evx_qmlp_stat_x(const evx_layout* lay, const evx_obs* obs, const uint16_t* x, int32_t n, const evx_qmlp_params* p,
                     float* out, void* stream) {
     if (!x) return evx_qmlp_stat(lay, obs, n, p, out, stream);
     if (n <= 0) return 0;
-    if (!out || !p) return mfail(-22, "qmlp_stat_x: NULL argument");
-    if (!p->x3) return mfail(-22, "qmlp_stat_x: the X input is the x3 layout (p->x3)");
+    if (!out || !p) return fail(-22, "qmlp_stat_x: NULL argument");
+    if (!p->x3) return fail(-22, "qmlp_stat_x: the X input is the x3 layout (p->x3)");
     evx_qmlp_fwd_out o{};
     o.h1 = reinterpret_cast<uint16_t*>(out);  // not written in raw mode
     evxm::Fwd a;
@@ -3095,13 +3086,13 @@ int evx_qmlp_stat_x(const evx_layout* lay, const evx_obs* obs, const uint16_t* x
     const unsigned blocks = (unsigned)((n + evxm::RM - 1) / evxm::RM);
     hipLaunchKernelGGL((evxm::qfc1_kernel<2, 1, 4, true, false, true>), dim3(blocks, 4, 1), dim3(256), 0,
                        (hipStream_t)stream, a, a, 1);
-    return mlaunch("qmlp_stat_x");
+    return hip_status("qmlp_stat_x");
 }
 
 int evx_qmlp_stat(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p, float* out,
                   void* stream) {
     if (n <= 0) return 0;
-    if (!out) return mfail(-22, "qmlp_stat: NULL out");
+    if (!out) return fail(-22, "qmlp_stat: NULL out");
     evx_qmlp_fwd_out o{};
     o.h1 = reinterpret_cast<uint16_t*>(out);  // not written in raw mode
     evxm::Fwd a;
@@ -3125,8 +3116,8 @@ int evx_qmlp_forward2(const evx_layout* lay, int32_t n, const evx_obs* obs0, con
     if (!rc) rc = make_fwd(lay, obs1, n, p1, drop1, out1, a1);
     if (rc) return rc;
     if (!(out0->q || out0->actions || out0->h2) || !(out1->q || out1->actions || out1->h2))
-        return mfail(-22, "qmlp_forward2: both problems need an fc2/fc3 output");
-    if ((p0->x3 != 0) != (p1->x3 != 0)) return mfail(-22, "qmlp_forward2: both problems in one precision");
+        return fail(-22, "qmlp_forward2: both problems need an fc2/fc3 output");
+    if ((p0->x3 != 0) != (p1->x3 != 0)) return fail(-22, "qmlp_forward2: both problems in one precision");
     // (at n >= 32768 only: a fused act workgroup lives ~65 us on the full path, so below a full
     // round of workgroups the two-kernel forward wins -- B = 4096: learn 187 vs 127 us)
     const int dm0 = a0.drop_mask ? 2 : a0.drop_thresh ? 1 : 0, dm1 = a1.drop_mask ? 2 : a1.drop_thresh ? 1 : 0;
@@ -3151,7 +3142,7 @@ int evx_qmlp_forward2(const evx_layout* lay, int32_t n, const evx_obs* obs0, con
             hipLaunchKernelGGL(evxm::qfwd2_kernel<1>, grid, dim3(256), evxm::ACT3H_LDS, (hipStream_t)stream, a0, a1);
         else
             hipLaunchKernelGGL(evxm::qfwd2_kernel<0>, grid, dim3(256), evxm::ACT3H_LDS, (hipStream_t)stream, a0, a1);
-        return mlaunch("qmlp_forward2 paired");
+        return hip_status("qmlp_forward2 paired");
     }
     if (p0->x3 && out1->q && !out1->h2 && !out1->actions && !out1->x && n >= 32768) {
         // x3 learner: the second problem (the target net: Q only) through the fused act kernel
@@ -3180,7 +3171,7 @@ int evx_qmlp_forward2(const evx_layout* lay, int32_t n, const evx_obs* obs0, con
             if (rc2) return rc2;
         }
         launch_act3<false>(a1, n, 1, (hipStream_t)stream);
-        return mlaunch("qmlp_forward2 target act");
+        return hip_status("qmlp_forward2 target act");
     }
     return launch_fwd(a0, a1, n, 2, true, (hipStream_t)stream, p0->x3 != 0);
 }
@@ -3302,16 +3293,16 @@ struct TdIn {
 static int qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, const uint16_t* x, const uint16_t* h1,
                          const float* h2, float drop_p, uint16_t* dz2, uint16_t* dz1, const evx_qmlp_grads* g,
                          int32_t zero_grads, float* ss, void* stream, int nets = 1, const TdIn* td = nullptr) {
-    if (!p || !g || !(dq || td) || !x || !h1 || !h2 || !dz2 || !dz1) return mfail(-22, "qmlp_backward: NULL argument");
+    if (!p || !g || !(dq || td) || !x || !h1 || !h2 || !dz2 || !dz1) return fail(-22, "qmlp_backward: NULL argument");
     if (td && (!td->Q || !td->Qt || !td->act || !td->rew || !td->done || !td->loss))
-        return mfail(-22, "qmlp_td_backward: NULL TD argument");
-    if (td && nets > 1) return mfail(-22, "qmlp_td_backward: one net");
-    if (!p->w2t || !p->w3) return mfail(-22, "qmlp_backward: w2t / w3 required");
-    if (!g->w1 || !g->b1 || !g->w2 || !g->b2 || !g->w3 || !g->b3) return mfail(-22, "qmlp_backward: missing grad");
+        return fail(-22, "qmlp_td_backward: NULL TD argument");
+    if (td && nets > 1) return fail(-22, "qmlp_td_backward: one net");
+    if (!p->w2t || !p->w3) return fail(-22, "qmlp_backward: w2t / w3 required");
+    if (!g->w1 || !g->b1 || !g->w2 || !g->b2 || !g->w3 || !g->b3) return fail(-22, "qmlp_backward: missing grad");
     if (ss && (g->b1 != g->w1 + evxm::OB1 || g->w2 != g->w1 + evxm::OW2 || g->b2 != g->w1 + evxm::OB2 ||
                g->w3 != g->w1 + evxm::OW3 || g->b3 != g->w1 + evxm::OB3))
-        return mfail(-22, "qmlp_backward: norm partials need the gradients as one flat state_dict-order buffer");
-    if (!g->part) return mfail(-22, "qmlp_backward: g->part required (evx_qmlp_backward_part_floats(B) floats)");
+        return fail(-22, "qmlp_backward: norm partials need the gradients as one flat state_dict-order buffer");
+    if (!g->part) return fail(-22, "qmlp_backward: g->part required (evx_qmlp_backward_part_floats(B) floats)");
     if (B <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int rb3 = evxm::qbwd3_rows(B);
@@ -3353,7 +3344,7 @@ static int qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, c
     a.gamma_row = td ? td->gamma_row : nullptr;
     float* loss = td ? td->loss : nullptr;
     if (p->x3) {
-        if (!p->w2tl) return mfail(-22, "qmlp_backward: x3 needs w2tl (evx_qmlp_pack3)");
+        if (!p->w2tl) return fail(-22, "qmlp_backward: x3 needs w2tl (evx_qmlp_pack3)");
         a.h1l = a.h1 + (size_t)B * evxm::HID;  // lo planes after the hi planes
         a.w2tl = reinterpret_cast<const __bf16*>(p->w2tl);
         a.dz2l = a.dz2 + (size_t)B * evxm::HID2;
@@ -3362,17 +3353,17 @@ static int qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, c
             hipLaunchKernelGGL((evxm::qbwd3_kernel<true, true>), dim3((unsigned)((B + rb3 - 1) / rb3), nets),
                                dim3(256), 0, st, a, rb3);
             launch_tail<true, 2, 2, 2, 1>(a, B, g, ss, st, nets, acc, nullptr);
-            return mlaunch("qmlp_backward grouped");
+            return hip_status("qmlp_backward grouped");
         }
         hipLaunchKernelGGL(evxm::qbwd3_kernel<true>, dim3((unsigned)((B + rb3 - 1) / rb3)), dim3(256), 0, st, a, rb3);
         // dW2: both operands split; dW1 over the 640 x3 columns (X exact in bf16): the danger
         // residual column of a cell adds into its danger column
         launch_tail<true, 2, 2, 2, 1>(a, B, g, ss, st, 1, acc, loss);
-        return mlaunch("qmlp_backward");
+        return hip_status("qmlp_backward");
     }
     hipLaunchKernelGGL(evxm::qbwd3_kernel<false>, dim3((unsigned)((B + rb3 - 1) / rb3)), dim3(256), 0, st, a, rb3);
     launch_tail<false, 1, 1, 1, 1>(a, B, g, ss, st, 1, acc, loss);
-    return mlaunch("qmlp_backward");
+    return hip_status("qmlp_backward");
 }
 
 int evx_qmlp_td_backward_ss(const evx_qmlp_params* p, int32_t B, const float* Q, const float* Qt, const int32_t* act,
@@ -3391,7 +3382,7 @@ int evx_qmlp_td_backward_opt(const evx_qmlp_params* p, int32_t B, const float* Q
     TdIn td{Q, Qt, rew, w, act, done, gamma, loss, td_abs};
     if (opt) {
         if (!(opt->huber_delta >= 0.f) || !std::isfinite(opt->huber_delta))
-            return mfail(-22, "qmlp_td_backward: huber_delta must be finite and >= 0");
+            return fail(-22, "qmlp_td_backward: huber_delta must be finite and >= 0");
         td.sel = opt->sel;
         td.delta = opt->huber_delta;
         td.gamma_row = opt->gamma_row;
@@ -3402,11 +3393,11 @@ int evx_qmlp_td_backward_opt(const evx_qmlp_params* p, int32_t B, const float* Q
 int evx_qmlp_polyak_pack3(const float* p, float* t, float tau, float one_minus_tau, uint16_t* w1b, uint16_t* w1l,
                           float* b1c, uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl, uint16_t* w1o,
                           uint16_t* w1ol, void* stream) {
-    if (!(tau >= 0.f && tau <= 1.f)) return mfail(-22, "qmlp_polyak_pack3: tau must lie in [0, 1]");
-    if (!std::isfinite(one_minus_tau)) return mfail(-22, "qmlp_polyak_pack3: one_minus_tau must be finite");
-    if (!p || !t || !w1b || !w1l || !b1c || !w2b || !w2l) return mfail(-22, "qmlp_polyak_pack3: NULL argument");
-    if ((w1o == nullptr) != (w1ol == nullptr)) return mfail(-22, "qmlp_polyak_pack3: w1o and w1ol go together");
-    if ((w2t == nullptr) != (w2tl == nullptr)) return mfail(-22, "qmlp_polyak_pack3: w2t and w2tl go together");
+    if (!(tau >= 0.f && tau <= 1.f)) return fail(-22, "qmlp_polyak_pack3: tau must lie in [0, 1]");
+    if (!std::isfinite(one_minus_tau)) return fail(-22, "qmlp_polyak_pack3: one_minus_tau must be finite");
+    if (!p || !t || !w1b || !w1l || !b1c || !w2b || !w2l) return fail(-22, "qmlp_polyak_pack3: NULL argument");
+    if ((w1o == nullptr) != (w1ol == nullptr)) return fail(-22, "qmlp_polyak_pack3: w1o and w1ol go together");
+    if ((w2t == nullptr) != (w2tl == nullptr)) return fail(-22, "qmlp_polyak_pack3: w2t and w2tl go together");
     evxm::AdamPack a = {};
     a.p = t;
     a.g = const_cast<float*>(p);  // read only (polyak_one)
@@ -3417,7 +3408,7 @@ int evx_qmlp_polyak_pack3(const float* p, float* t, float tau, float one_minus_t
     a.b1c = b1c;
     hipLaunchKernelGGL(evxm::polyak_pack3_kernel, dim3((unsigned)((evxm::NPAR + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, a, tau, one_minus_tau);
-    return mlaunch("qmlp_polyak_pack3");
+    return hip_status("qmlp_polyak_pack3");
 }
 
 int evx_qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, const uint16_t* x, const uint16_t* h1,
@@ -3429,14 +3420,14 @@ int evx_qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, cons
 int evx_qmlp_backward_ss(const evx_qmlp_params* p, int32_t B, const float* dq, const uint16_t* x, const uint16_t* h1,
                          const float* h2, float drop_p, uint16_t* dz2, uint16_t* dz1, const evx_qmlp_grads* g,
                          int32_t zero_grads, float* ss, void* stream) {
-    if (!ss) return mfail(-22, "qmlp_backward_ss: NULL ss");
+    if (!ss) return fail(-22, "qmlp_backward_ss: NULL ss");
     return qmlp_backward(p, B, dq, x, h1, h2, drop_p, dz2, dz1, g, zero_grads, ss, stream);
 }
 
 int evx_qmlp_sumsq_parts(const float* g, float* ss, void* stream) {
-    if (!g || !ss) return mfail(-22, "qmlp_sumsq_parts: NULL argument");
+    if (!g || !ss) return fail(-22, "qmlp_sumsq_parts: NULL argument");
     hipLaunchKernelGGL(evxm::sumsq_parts_kernel, dim3((unsigned)norm_parts()), dim3(256), 0, (hipStream_t)stream, g, ss);
-    return mlaunch("qmlp_sumsq_parts");
+    return hip_status("qmlp_sumsq_parts");
 }
 
 static int adam_pack3(float* p, float* g, float* m, float* v, float max_norm, const evx_adam* h, uint16_t* w1b,
@@ -3453,7 +3444,7 @@ int evx_qmlp_adam_pack3_g(float* p, float* g, float* m, float* v, float max_norm
                           uint16_t* w1l, float* b1c, uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl,
                           uint16_t* w1o, uint16_t* w1ol, const float* ss, int32_t nss, float* norm_out, int32_t nets,
                           void* stream) {
-    if (nets < 1 || nets > 1024) return mfail(-22, "qmlp_adam_pack3_g: nets must be 1..1024");
+    if (nets < 1 || nets > 1024) return fail(-22, "qmlp_adam_pack3_g: nets must be 1..1024");
     return adam_pack3(p, g, m, v, max_norm, h, w1b, w1l, b1c, w2b, w2l, w2t, w2tl, w1o, w1ol, ss, nss, norm_out,
                       stream, nets);
 }
@@ -3461,11 +3452,11 @@ static int adam_pack3(float* p, float* g, float* m, float* v, float max_norm, co
                       uint16_t* w1l, float* b1c, uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl,
                       uint16_t* w1o, uint16_t* w1ol, const float* ss, int32_t nss, float* norm_out, void* stream,
                       int nets) {
-    if ((w1o == nullptr) != (w1ol == nullptr)) return mfail(-22, "qmlp_adam_pack3: w1o and w1ol go together");
+    if ((w1o == nullptr) != (w1ol == nullptr)) return fail(-22, "qmlp_adam_pack3: w1o and w1ol go together");
     if (!p || !g || !m || !v || !h || !w1b || !w1l || !b1c || !w2b || !w2l || !ss)
-        return mfail(-22, "qmlp_adam_pack3: NULL argument");
-    if ((w2t == nullptr) != (w2tl == nullptr)) return mfail(-22, "qmlp_adam_pack3: w2t and w2tl go together");
-    if (nss <= 0) return mfail(-22, "qmlp_adam_pack3: no norm partials");
+        return fail(-22, "qmlp_adam_pack3: NULL argument");
+    if ((w2t == nullptr) != (w2tl == nullptr)) return fail(-22, "qmlp_adam_pack3: w2t and w2tl go together");
+    if (nss <= 0) return fail(-22, "qmlp_adam_pack3: no norm partials");
     evxm::AdamPack a;
     a.p = p; a.g = g; a.m = m; a.v = v;
     a.ss = ss; a.nss = nss;
@@ -3482,14 +3473,14 @@ static int adam_pack3(float* p, float* g, float* m, float* v, float max_norm, co
     a.w1o = reinterpret_cast<__bf16*>(w1o); a.w1ol = reinterpret_cast<__bf16*>(w1ol);
     hipLaunchKernelGGL(evxm::adam_pack3_kernel, dim3((unsigned)((evxm::NPAR + 255) / 256), nets), dim3(256), 0,
                        (hipStream_t)stream, a);
-    return mlaunch("qmlp_adam_pack3");
+    return hip_status("qmlp_adam_pack3");
 }
 
 // ------------------------------------------------ grouped nets
 // Every per-net buffer is an array [nets][one net's buffer]: the pointers passed are net 0's.
 static int group_check(int32_t nets, const evx_qmlp_params* p, const char* what) {
-    if (nets < 1 || nets > 1024) return mfail(-22, "grouped qmlp: nets must be 1..1024");
-    if (!p || !p->x3) return mfail(-22, "grouped qmlp: x3 parameters required (the [nets] operand layout is x3's)");
+    if (nets < 1 || nets > 1024) return fail(-22, "grouped qmlp: nets must be 1..1024");
+    if (!p || !p->x3) return fail(-22, "grouped qmlp: x3 parameters required (the [nets] operand layout is x3's)");
     (void)what;
     return 0;
 }
@@ -3499,10 +3490,10 @@ int evx_qmlp_act_g(const evx_layout* lay, const evx_obs* obs, int32_t n, int32_t
     int rc = group_check(nets, p, "act");
     if (rc) return rc;
     if (n <= 0) return 0;
-    if (!out || (!out->q && !out->actions)) return mfail(-22, "qmlp_act_g: needs q or actions");
-    if (out->perm) return mfail(-22, "qmlp_act_g: no act permutation with grouped nets");
-    if (p->stat) return mfail(-22, "qmlp_act_g: the act table path is single-net");
-    if (n & 1) return mfail(-22, "qmlp_act_g: rows per net must be even (dropout row pairs)");
+    if (!out || (!out->q && !out->actions)) return fail(-22, "qmlp_act_g: needs q or actions");
+    if (out->perm) return fail(-22, "qmlp_act_g: no act permutation with grouped nets");
+    if (p->stat) return fail(-22, "qmlp_act_g: the act table path is single-net");
+    if (n & 1) return fail(-22, "qmlp_act_g: rows per net must be even (dropout row pairs)");
     evx_qmlp_fwd_out o = *out;
     o.h1 = reinterpret_cast<uint16_t*>(1);
     o.x = nullptr;
@@ -3514,7 +3505,7 @@ int evx_qmlp_act_g(const evx_layout* lay, const evx_obs* obs, int32_t n, int32_t
     a.h1l = nullptr;
     a.gn = nets;
     launch_act3<true>(a, n, nets, (hipStream_t)stream);
-    return mlaunch("qact_g");
+    return hip_status("qact_g");
 }
 
 int evx_qmlp_forward2_g(const evx_layout* lay, int32_t n, int32_t nets, const evx_obs* obs0, const evx_qmlp_params* p0,
@@ -3525,14 +3516,14 @@ int evx_qmlp_forward2_g(const evx_layout* lay, int32_t n, int32_t nets, const ev
     if (!rc) rc = group_check(nets, p1, "forward2");
     if (rc) return rc;
     if (n <= 0) return 0;
-    if (n & 1) return mfail(-22, "qmlp_forward2_g: rows per net must be even (dropout row pairs)");
+    if (n & 1) return fail(-22, "qmlp_forward2_g: rows per net must be even (dropout row pairs)");
     evxm::Fwd a0, a1;
     rc = make_fwd(lay, obs0, n, p0, drop0, out0, a0);
     if (!rc) rc = make_fwd(lay, obs1, n, p1, drop1, out1, a1);
     if (rc) return rc;
-    if (a0.stat || a1.stat || a0.perm || a1.perm) return mfail(-22, "qmlp_forward2_g: no table path / permutation");
-    if (!(out0->q || out0->h2) || !(out1->q || out1->h2)) return mfail(-22, "qmlp_forward2_g: needs fc2/fc3 outputs");
-    if ((int64_t)n * nets * 2 > (int64_t)1 << 31) return mfail(-22, "qmlp_forward2_g: too many rows");
+    if (a0.stat || a1.stat || a0.perm || a1.perm) return fail(-22, "qmlp_forward2_g: no table path / permutation");
+    if (!(out0->q || out0->h2) || !(out1->q || out1->h2)) return fail(-22, "qmlp_forward2_g: needs fc2/fc3 outputs");
+    if ((int64_t)n * nets * 2 > (int64_t)1 << 31) return fail(-22, "qmlp_forward2_g: too many rows");
     return launch_fwd(a0, a1, n, 2, true, (hipStream_t)stream, true, nets);
 }
 
@@ -3541,8 +3532,8 @@ int evx_qmlp_backward_ss_g(const evx_qmlp_params* p, int32_t B, int32_t nets, co
                            const evx_qmlp_grads* g, float* ss, void* stream) {
     int rc = group_check(nets, p, "backward");
     if (rc) return rc;
-    if (!g || !g->part) return mfail(-22, "qmlp_backward_ss_g: split-K partials required ([nets][part floats(B)])");
-    if (!ss) return mfail(-22, "qmlp_backward_ss_g: NULL ss");
+    if (!g || !g->part) return fail(-22, "qmlp_backward_ss_g: split-K partials required ([nets][part floats(B)])");
+    if (!ss) return fail(-22, "qmlp_backward_ss_g: NULL ss");
     return qmlp_backward(p, B, dq, x, h1, h2, drop_p, dz2, dz1, g, 0, ss, stream, nets);
 }
 

@@ -1259,23 +1259,14 @@ __global__ __launch_bounds__(256) void relu_grad_kernel(float* __restrict__ dy, 
 
 // ===================================================================== C-ABI
 namespace {
-thread_local char q_err[256] = "";
-int qfail(int code, const char* msg) {
-    snprintf(q_err, sizeof(q_err), "%s", msg);
-    return code;
-}
-int qlaunch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(q_err, sizeof(q_err), "%s: %s", what, hipGetErrorString(e));
-    return -5;
-}
+using evxh::fail;
+using evxh::hip_status;
 unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 
 extern "C" {
 
-const char* evx_q_last_error(void) { return q_err; }
+const char* evx_q_last_error(void) { return evxh::g_err; }
 
 }  // extern "C"
 
@@ -1781,17 +1772,17 @@ static int tn3_ok(const evx_gemm_desc* g, int cm, int cs) {
     return 0;
 }
 int gemm_launch(const evx_gemm_desc* g, int cm, int cs, void* stream) {
-    if (!g || !g->A || !g->B || !g->C) return qfail(-22, "gemm: NULL operand");
+    if (!g || !g->A || !g->B || !g->C) return fail(-22, "gemm: NULL operand");
     if (g->M <= 0 || g->N <= 0 || g->K <= 0) return 0;
-    if (g->ws_elems < 0) return qfail(-22, "gemm: ws_elems < 0");
+    if (g->ws_elems < 0) return fail(-22, "gemm: ws_elems < 0");
     const int TB = evxq::TB;
     int klen = 0;
     const int S = gemm_slices(g, g->ws ? g->ws_elems : 0, &klen);
     dim3 grid((unsigned)((g->N + TB - 1) / TB), (unsigned)((g->M + TB - 1) / TB), (unsigned)S);
-    if (grid.y > 65535u) return qfail(-22, "gemm: M too large for one launch");
+    if (grid.y > 65535u) return fail(-22, "gemm: M too large for one launch");
     hipStream_t st = (hipStream_t)stream;
-    if ((cm == evxq::CV_FWD || cm == evxq::CV_DX) && S == 1 && conv_direct(g, cm, cs, st)) return qlaunch("conv3x3");
-    if (g->flags & EVX_GEMM_OUT_SPLIT) return qfail(-22, "gemm: OUT_SPLIT needs the LDS-staged conv forward (and its workspace)");
+    if ((cm == evxq::CV_FWD || cm == evxq::CV_DX) && S == 1 && conv_direct(g, cm, cs, st)) return hip_status("conv3x3");
+    if (g->flags & EVX_GEMM_OUT_SPLIT) return fail(-22, "gemm: OUT_SPLIT needs the LDS-staged conv forward (and its workspace)");
     if (const int tk = tn3_ok(g, cm, cs)) {  // B k-major (weight gradients: fc and conv dW; activation gradients)
         {
             static std::atomic<uint64_t> attr_done;
@@ -1810,7 +1801,7 @@ int gemm_launch(const evx_gemm_desc* g, int cm, int cs, void* stream) {
     if (g->flags & EVX_GEMM_SPLIT_AB) {
         if (cm != evxq::CV_NONE || g->precision != EVX_PREC_X3 || g->sak != 1 || g->sbk != 1 || (g->K & 7) ||
             (g->sam & 7) || (g->sbn & 7))
-            return qfail(-22, "gemm: SPLIT_AB needs x3, k-contiguous operands, K and row strides multiples of 8");
+            return fail(-22, "gemm: SPLIT_AB needs x3, k-contiguous operands, K and row strides multiples of 8");
         hipLaunchKernelGGL((evxq::gemm128x3_kernel<evxq::CV_NONE, true>), grid, dim3(256), 0, st, *g, klen, 0);
     } else
     if (cm == evxq::CV_FWD)
@@ -1841,7 +1832,7 @@ int gemm_launch(const evx_gemm_desc* g, int cm, int cs, void* stream) {
     else
         hipLaunchKernelGGL(evxq::gemm128_kernel<float>, grid, dim3(256), 0, st, *g, klen);
     if (S > 1) {  // the slices' partials summed in slice order, then the epilogue
-        const int e = qlaunch("gemm");
+        const int e = hip_status("gemm");
         if (e) return e;
         const int64_t MN = (int64_t)g->M * g->N;
         if (S >= 8 && (MN & 3) == 0)
@@ -1849,7 +1840,7 @@ int gemm_launch(const evx_gemm_desc* g, int cm, int cs, void* stream) {
         else
             hipLaunchKernelGGL(evxq::splitk_reduce_kernel, dim3(nblk((MN + 3) / 4)), dim3(256), 0, st, *g, S);
     }
-    return qlaunch("gemm");
+    return hip_status("gemm");
 }
 }  // namespace
 
@@ -1873,15 +1864,15 @@ int64_t evx_conv3x3_ws_elems(const evx_gemm_desc* g, int32_t mode, int32_t cs) {
 }
 
 int evx_conv3x3_gemm(const evx_gemm_desc* g, int32_t mode, int32_t cs, void* stream) {
-    if (!g) return qfail(-22, "conv3x3: NULL descriptor");
-    if (g->precision != EVX_PREC_X3) return qfail(-22, "conv3x3: implicit-GEMM convolution is x3 only");
-    if (mode < EVX_CONV_FWD || mode > EVX_CONV_DW) return qfail(-22, "conv3x3: bad mode");
-    if (cs <= 0) return qfail(-22, "conv3x3: channels <= 0");
+    if (!g) return fail(-22, "conv3x3: NULL descriptor");
+    if (g->precision != EVX_PREC_X3) return fail(-22, "conv3x3: implicit-GEMM convolution is x3 only");
+    if (mode < EVX_CONV_FWD || mode > EVX_CONV_DW) return fail(-22, "conv3x3: bad mode");
+    if (cs <= 0) return fail(-22, "conv3x3: channels <= 0");
     const int64_t pix = mode == EVX_CONV_DW ? g->K : g->M;  // rows of the pixel-major activations
-    if (pix % 121 || pix >= (1LL << 26)) return qfail(-22, "conv3x3: pixel count not 121*B (< 2^26)");
-    if ((mode == EVX_CONV_DW ? g->N : g->K) != 9 * cs) return qfail(-22, "conv3x3: 3x3 taps x channels mismatch");
+    if (pix % 121 || pix >= (1LL << 26)) return fail(-22, "conv3x3: pixel count not 121*B (< 2^26)");
+    if ((mode == EVX_CONV_DW ? g->N : g->K) != 9 * cs) return fail(-22, "conv3x3: 3x3 taps x channels mismatch");
     if (mode == EVX_CONV_DW && (g->sam != 1 || g->sak != g->M))
-        return qfail(-22, "conv3x3 dW: A must be dY [pixels][M]");
+        return fail(-22, "conv3x3 dW: A must be dY [pixels][M]");
     return gemm_launch(g, mode, cs, stream);
 }
 
@@ -1890,12 +1881,12 @@ int evx_colsum(const float* X, int64_t ld, int32_t M, int32_t N, float* out, int
     if (M <= 0 || N <= 0) return 0;
     int chunks = (M + evxq::COLSUM_ROWS - 1) / evxq::COLSUM_ROWS;
     if ((int64_t)chunks * N > scratch_elems) chunks = scratch_elems / N;
-    if (chunks < 1) return qfail(-22, "colsum: scratch too small");
+    if (chunks < 1) return fail(-22, "colsum: scratch too small");
     hipLaunchKernelGGL(evxq::colsum_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((chunks + 3) / 4)), dim3(256), 0,
                        (hipStream_t)stream, X, ld, M, N, scratch, chunks);
     hipLaunchKernelGGL(evxq::colsum_finish, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, scratch, N, chunks,
                        out, accum);
-    return qlaunch("colsum");
+    return hip_status("colsum");
 }
 
 int64_t evx_td_loss_ws_floats(int32_t B, int32_t nets) {
@@ -1910,18 +1901,18 @@ static int td_launch(const float* Q, const float* Qt, int32_t A, const int32_t* 
     const int32_t* sel = opt ? opt->sel : nullptr;
     const float delta = opt ? opt->huber_delta : 0.f;
     const float* gamma_row = opt ? opt->gamma_row : nullptr;
-    if (!(delta >= 0.f) || !std::isfinite(delta)) return qfail(-22, "td_loss: huber_delta must be finite and >= 0");
+    if (!(delta >= 0.f) || !std::isfinite(delta)) return fail(-22, "td_loss: huber_delta must be finite and >= 0");
     if (B <= 0) return 0;
-    if (nets < 1 || nets > 65535) return qfail(-22, "td_loss: nets must be 1..65535");
-    if (!Q || !Qt || !act || !rew || !done || !dQ || !loss) return qfail(-22, "td_loss: NULL argument");
+    if (nets < 1 || nets > 65535) return fail(-22, "td_loss: nets must be 1..65535");
+    if (!Q || !Qt || !act || !rew || !done || !dQ || !loss) return fail(-22, "td_loss: NULL argument");
     const int ntd = (B + 255) / 256;
-    if (!ws || ws_floats < (int64_t)ntd * nets) return qfail(-22, "td_loss: workspace smaller than evx_td_loss_ws_floats");
+    if (!ws || ws_floats < (int64_t)ntd * nets) return fail(-22, "td_loss: workspace smaller than evx_td_loss_ws_floats");
     const int nz = zero && nzero > 0 ? (int)std::min<int64_t>((nzero + 256 * 16 - 1) / (256 * 16), 512) : 0;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(evxq::td_loss_kernel, dim3(ntd + nz, nets), dim3(256), 0, st, Q, Qt, A, act, rew, done, gamma, B,
                        w, dQ, ws, td_abs, ntd, nz ? zero : nullptr, nzero, sel, delta, gamma_row);
     hipLaunchKernelGGL(evxq::td_finish_kernel, dim3(nets), dim3(256), 0, st, (const float*)ws, ntd, B, loss);
-    return qlaunch(what);
+    return hip_status(what);
 }
 
 int evx_td_loss_w(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew,
@@ -1954,13 +1945,13 @@ int evx_td_loss_opt(const float* Q, const float* Qt, int32_t A, const int32_t* a
 }
 
 int evx_polyak(const float* p, float* t, int64_t n, float tau, float one_minus_tau, void* stream) {
-    if (!(tau >= 0.f && tau <= 1.f)) return qfail(-22, "polyak: tau must lie in [0, 1]");
-    if (!std::isfinite(one_minus_tau)) return qfail(-22, "polyak: one_minus_tau must be finite");
-    if (!p || !t) return qfail(-22, "polyak: NULL argument");
+    if (!(tau >= 0.f && tau <= 1.f)) return fail(-22, "polyak: tau must lie in [0, 1]");
+    if (!std::isfinite(one_minus_tau)) return fail(-22, "polyak: one_minus_tau must be finite");
+    if (!p || !t) return fail(-22, "polyak: NULL argument");
     if (n <= 0) return 0;
     const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(evxq::polyak_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, p, t, n, tau, one_minus_tau);
-    return qlaunch("polyak");
+    return hip_status("polyak");
 }
 
 int evx_td_loss(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew, const uint8_t* done,
@@ -1975,12 +1966,12 @@ int evx_sumsq_norm(const float* g, int64_t n, float* scratch, int32_t scratch_el
     if (parts < 1) parts = 1;
     hipLaunchKernelGGL(evxq::sumsq_kernel, dim3(parts), dim3(256), 0, (hipStream_t)stream, g, n, scratch);
     hipLaunchKernelGGL(evxq::sumsq_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, parts, norm);
-    return qlaunch("sumsq");
+    return hip_status("sumsq");
 }
 
 int evx_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const float* norm, float max_norm,
                   const evx_adam* h, void* stream) {
-    if (!h) return qfail(-22, "adam: NULL hyper-parameters");
+    if (!h) return fail(-22, "adam: NULL hyper-parameters");
     if (n <= 0) return 0;
     const double bc1 = 1.0 - pow((double)h->beta1, (double)h->step);
     const double bc2 = 1.0 - pow((double)h->beta2, (double)h->step);
@@ -1990,14 +1981,14 @@ int evx_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const float
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(evxq::clip_adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, norm,
                        max_norm, h->lr, h->beta1, h->beta2, h->eps, step_size, bc2_sqrt, h->weight_decay);
-    return qlaunch("clip_adam");
+    return hip_status("clip_adam");
 }
 
 int evx_dropout_mask(uint8_t* mask, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(evxq::dropout_mask_kernel, dim3(nblk((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, mask, n,
                        p, seed, offset);
-    return qlaunch("dropout_mask");
+    return hip_status("dropout_mask");
 }
 
 int evx_act(const float* Q, int32_t n, int32_t A, float epsilon, uint64_t seed, uint64_t offset, int32_t* actions,
@@ -2005,134 +1996,134 @@ int evx_act(const float* Q, int32_t n, int32_t A, float epsilon, uint64_t seed, 
     if (n <= 0) return 0;
     hipLaunchKernelGGL(evxq::act_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, Q, n, A, epsilon, seed,
                        offset, actions);
-    return qlaunch("act");
+    return hip_status("act");
 }
 
 int evx_replay_push(const evx_replay* rp, const evx_obs* s, const evx_obs* s2, const int32_t* a, const double* r_env,
                     const uint8_t* done_env, int32_t n, int32_t agents_per_env, int64_t pos, void* stream) {
-    if (!rp || rp->capacity <= 0) return qfail(-22, "replay: bad ring");
+    if (!rp || rp->capacity <= 0) return fail(-22, "replay: bad ring");
     if (n <= 0) return 0;
     hipLaunchKernelGGL(evxq::replay_push_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, *rp, s, s2,
                        (const evx_obs*)nullptr, a, r_env, done_env, n, agents_per_env, pos);
-    return qlaunch("replay_push");
+    return hip_status("replay_push");
 }
 
 int evx_replay_push_term(const evx_replay* rp, const evx_obs* s, const evx_obs* s2, const evx_obs* s2_term,
                          const int32_t* a, const double* r_env, const uint8_t* done_env, int32_t n,
                          int32_t agents_per_env, int64_t pos, void* stream) {
-    if (!rp || rp->capacity <= 0) return qfail(-22, "replay: bad ring");
+    if (!rp || rp->capacity <= 0) return fail(-22, "replay: bad ring");
     if (n <= 0) return 0;
     hipLaunchKernelGGL(evxq::replay_push_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, *rp, s, s2, s2_term,
                        a, r_env, done_env, n, agents_per_env, pos);
-    return qlaunch("replay_push_term");
+    return hip_status("replay_push_term");
 }
 
 int evx_replay_sample(const evx_replay* rp, int64_t size, int32_t B, uint64_t seed, uint64_t offset, evx_obs* s,
                       evx_obs* s2, int32_t* a, float* r, uint8_t* done, int64_t* idx_out, void* stream) {
-    if (!rp || size <= 0) return qfail(-22, "replay: empty");
+    if (!rp || size <= 0) return fail(-22, "replay: empty");
     if (B <= 0) return 0;
-    if (size > rp->capacity) return qfail(-22, "replay: size > capacity");
-    if (B > size) return qfail(-22, "replay: sample larger than population (random.sample)");
+    if (size > rp->capacity) return fail(-22, "replay: size > capacity");
+    if (B > size) return fail(-22, "replay: sample larger than population (random.sample)");
     hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, (int64_t)0,
                        size, B, seed, offset, s, s2, a, r, done, idx_out);
-    return qlaunch("replay_sample");
+    return hip_status("replay_sample");
 }
 
 int evx_replay_sample_agents(const evx_replay* rp, int64_t size, int32_t B, int32_t nets, uint64_t seed,
                              uint64_t offset, evx_obs* s, evx_obs* s2, int32_t* a, float* r, uint8_t* done,
                              void* stream) {
-    if (!rp || !s || !s2 || !a || !r || !done) return qfail(-22, "replay_sample_agents: NULL argument");
+    if (!rp || !s || !s2 || !a || !r || !done) return fail(-22, "replay_sample_agents: NULL argument");
     if (B <= 0) return 0;
-    if (nets < 1 || nets > 65535) return qfail(-22, "replay_sample_agents: nets must be 1..65535");
-    if (rp->capacity % nets) return qfail(-22, "replay_sample_agents: capacity must be a multiple of nets");
+    if (nets < 1 || nets > 65535) return fail(-22, "replay_sample_agents: nets must be 1..65535");
+    if (rp->capacity % nets) return fail(-22, "replay_sample_agents: capacity must be a multiple of nets");
     if (size < nets || size > rp->capacity || size % nets)
-        return qfail(-22, "replay_sample_agents: size must be a positive multiple of nets within the capacity");
-    if (B > size / nets) return qfail(-22, "replay_sample_agents: sample larger than an agent's population");
+        return fail(-22, "replay_sample_agents: size must be a positive multiple of nets within the capacity");
+    if (B > size / nets) return fail(-22, "replay_sample_agents: sample larger than an agent's population");
     hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B), nets), dim3(256), 0, (hipStream_t)stream, *rp, (int64_t)0,
                        size, B, seed, offset, s, s2, a, r, done, nullptr, (int)nets);
-    return qlaunch("replay_sample_agents");
+    return hip_status("replay_sample_agents");
 }
 
 int evx_replay_sample_joint(const evx_replay* rp, int64_t size, int32_t B, int32_t nets, uint64_t seed,
                             uint64_t offset, evx_obs* s, evx_obs* s2, int32_t* a, float* r, uint8_t* done,
                             void* stream) {
-    if (!rp || !s || !s2 || !a || !r || !done) return qfail(-22, "replay_sample_joint: NULL argument");
+    if (!rp || !s || !s2 || !a || !r || !done) return fail(-22, "replay_sample_joint: NULL argument");
     if (B <= 0) return 0;
-    if (nets < 1 || nets > 65535) return qfail(-22, "replay_sample_joint: nets must be 1..65535");
-    if (rp->capacity % nets) return qfail(-22, "replay_sample_joint: capacity must be a multiple of nets");
+    if (nets < 1 || nets > 65535) return fail(-22, "replay_sample_joint: nets must be 1..65535");
+    if (rp->capacity % nets) return fail(-22, "replay_sample_joint: capacity must be a multiple of nets");
     if (size < nets || size > rp->capacity || size % nets)
-        return qfail(-22, "replay_sample_joint: size must be a positive multiple of nets within the capacity");
-    if (B > size / nets) return qfail(-22, "replay_sample_joint: sample larger than the population");
+        return fail(-22, "replay_sample_joint: size must be a positive multiple of nets within the capacity");
+    if (B > size / nets) return fail(-22, "replay_sample_joint: sample larger than the population");
     hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B), nets), dim3(256), 0, (hipStream_t)stream, *rp, (int64_t)0,
                        size, B, seed, offset, s, s2, a, r, done, nullptr, (int)nets, 1);
-    return qlaunch("replay_sample_joint");
+    return hip_status("replay_sample_joint");
 }
 
 int evx_replay_sample_window(const evx_replay* rp, int64_t base, int64_t count, int32_t B, uint64_t seed,
                              uint64_t offset, evx_obs* s, evx_obs* s2, int32_t* a, float* r, uint8_t* done,
                              int64_t* idx_out, void* stream) {
-    if (!rp || count <= 0) return qfail(-22, "replay: empty window");
-    if (count > rp->capacity || base < 0 || base >= rp->capacity) return qfail(-22, "replay: bad window");
+    if (!rp || count <= 0) return fail(-22, "replay: empty window");
+    if (count > rp->capacity || base < 0 || base >= rp->capacity) return fail(-22, "replay: bad window");
     if (B <= 0) return 0;
-    if (B > count) return qfail(-22, "replay: sample larger than the window (random.sample)");
+    if (B > count) return fail(-22, "replay: sample larger than the window (random.sample)");
     hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, base, count,
                        B, seed, offset, s, s2, a, r, done, idx_out);
-    return qlaunch("replay_sample_window");
+    return hip_status("replay_sample_window");
 }
 
 int evx_replay_nstep(const evx_replay* rp, const int64_t* idx, int32_t B, int64_t base, int64_t count, int64_t stride,
                      int32_t n_step, float gamma, evx_obs* s2, float* r, uint8_t* done, float* gamma_row, int32_t* len,
                      void* stream) {
-    if (!rp || rp->capacity <= 0) return qfail(-22, "replay_nstep: bad ring");
-    if (!idx || !s2 || !r || !done || !gamma_row) return qfail(-22, "replay_nstep: NULL argument");
-    if (n_step < 1 || n_step > EVX_NSTEP_MAX) return qfail(-22, "replay_nstep: n_step must be 1..EVX_NSTEP_MAX (32)");
-    if (stride < 1) return qfail(-22, "replay_nstep: stride must be >= 1");
-    if (count < 0 || count > rp->capacity) return qfail(-22, "replay_nstep: count must lie in [0, capacity]");
-    if (base < 0 || base >= rp->capacity) return qfail(-22, "replay_nstep: base must lie in [0, capacity)");
-    if (!std::isfinite(gamma)) return qfail(-22, "replay_nstep: gamma must be finite");
+    if (!rp || rp->capacity <= 0) return fail(-22, "replay_nstep: bad ring");
+    if (!idx || !s2 || !r || !done || !gamma_row) return fail(-22, "replay_nstep: NULL argument");
+    if (n_step < 1 || n_step > EVX_NSTEP_MAX) return fail(-22, "replay_nstep: n_step must be 1..EVX_NSTEP_MAX (32)");
+    if (stride < 1) return fail(-22, "replay_nstep: stride must be >= 1");
+    if (count < 0 || count > rp->capacity) return fail(-22, "replay_nstep: count must lie in [0, capacity]");
+    if (base < 0 || base >= rp->capacity) return fail(-22, "replay_nstep: base must lie in [0, capacity)");
+    if (!std::isfinite(gamma)) return fail(-22, "replay_nstep: gamma must be finite");
     if (B <= 0) return 0;
-    if (!rp->s2 || !rp->r || !rp->done) return qfail(-22, "replay_nstep: ring without s2 / r / done");
+    if (!rp->s2 || !rp->r || !rp->done) return fail(-22, "replay_nstep: ring without s2 / r / done");
     // a stride beyond the ring never finds a successor inside the range (count <= capacity): the
     // capacity stands for it, so L * stride cannot overflow
     hipLaunchKernelGGL(evxq::replay_nstep_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, idx, (int)B,
                        base, count, std::min<int64_t>(stride, rp->capacity), (int)n_step, gamma, s2, r, done,
                        gamma_row, len);
-    return qlaunch("replay_nstep");
+    return hip_status("replay_nstep");
 }
 
 int evx_gather_obs(const evx_obs* src, const int64_t* idx, int32_t n, evx_obs* dst, void* stream) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(evxq::gather_rows_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, src, idx, n, dst);
-    return qlaunch("gather_obs");
+    return hip_status("gather_obs");
 }
 
 int evx_im2col3x3(const float* x, int32_t B, int32_t C, int32_t nhwc, float* cols, void* stream) {
     const int64_t total = (int64_t)B * 121 * C * 9;
     if (total <= 0) return 0;
     hipLaunchKernelGGL(evxq::im2col_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, B, C, nhwc, cols);
-    return qlaunch("im2col");
+    return hip_status("im2col");
 }
 
 int evx_col2im3x3(const float* dcols, int32_t B, int32_t C, float* dx, void* stream) {
     const int64_t total = (int64_t)B * C * 121;
     if (total <= 0) return 0;
     hipLaunchKernelGGL(evxq::col2im_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, dcols, B, C, dx);
-    return qlaunch("col2im");
+    return hip_status("col2im");
 }
 
 int evx_relu_grad(float* dy, const float* y, int64_t n, void* stream) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(evxq::relu_grad_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, dy, y, n);
-    return qlaunch("relu_grad");
+    return hip_status("relu_grad");
 }
 
 int evx_pix_split(const float* src, int32_t B, int32_t C, uint16_t* dst, void* stream) {
     if (B <= 0 || C <= 0) return 0;
     const size_t lds = (size_t)121 * (C + 1) * 4;
-    if (lds > 64 * 1024) return qfail(-22, "pix_split: C > 134 channels");
+    if (lds > 64 * 1024) return fail(-22, "pix_split: C > 134 channels");
     hipLaunchKernelGGL(evxq::pix_split_kernel, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, src, B, C,
                        reinterpret_cast<__bf16*>(dst));
-    return qlaunch("pix_split");
+    return hip_status("pix_split");
 }
 
 int evx_pix_nchw(const float* src, int32_t B, int32_t C, int32_t to_nchw, float* dst, void* stream) {
@@ -2142,11 +2133,11 @@ int evx_pix_nchw(const float* src, int32_t B, int32_t C, int32_t to_nchw, float*
     if (lds > 64 * 1024) {  // the LDS tile holds C <= 134: element-wise beyond
         hipLaunchKernelGGL(evxq::pix2nchw_flat_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, src, total,
                            C, to_nchw, dst);
-        return qlaunch("pix_nchw");
+        return hip_status("pix_nchw");
     }
     hipLaunchKernelGGL(evxq::pix2nchw_kernel, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, src, B, C, to_nchw,
                        dst);
-    return qlaunch("pix_nchw");
+    return hip_status("pix_nchw");
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@ from . import _lib
 from .layout import LayoutSpec, LayoutTables, build_tables
 
 REWARD_DEFAULTS = dict(evac_reward=50.0, death_penalty=200.0, death_acc_penalty=0.5, alive_bonus=1.0)
-OBS_WORDS = 8  # sizeof(evx_obs) / 4
+OBS_WORDS = _lib.OBS_WORDS
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)

@@ -15,47 +15,16 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from ._lib import EPISODE_REDUCE_SPAN as REDUCE_SPAN, EPISODE_ROW_WORDS as ROW_WORDS  # noqa: F401
+from ._lib import check, evx_episodes, lib
 from .env import _ptr, _stream
-
-REDUCE_SPAN = 1024  # EVX_EPISODE_REDUCE_SPAN: envs one pass of a reduce workgroup covers
-ROW_WORDS = 10      # sizeof(evx_episode_row) / 8
 
 _I64 = ("w_n", "w_len", "w_evac", "w_dead", "n_total")
 _F64 = ("ret", "w_ret", "w_ret2", "w_min", "w_max", "last_ret")
 _I32 = ("len", "last_len", "last_evac", "last_dead")
 _TAB = ("tab_ret", "tab_len", "tab_evac", "tab_dead")
-
-
-class evx_episodes(C.Structure):
-    _fields_ = [("E", C.c_int32), ("tab_slots", C.c_int32)] + \
-               [(n, C.c_void_p) for n in ["ret", "len", "w_n", "w_len", "w_evac", "w_dead", "w_ret", "w_ret2",
-                                         "w_min", "w_max", "last_ret", "last_len", "last_evac", "last_dead",
-                                         "n_total", "tab_ret", "tab_len", "tab_evac", "tab_dead"]]
-
-
-_inited = False
-
-
-def elib():
-    global _inited
-    L = _lib.lib()
-    if not _inited:
-        P = C.POINTER(evx_episodes)
-        L.evx_episode_last_error.restype = C.c_char_p
-        L.evx_episode_init.argtypes = [P, C.c_void_p]
-        L.evx_episode_update.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        L.evx_episode_discard.argtypes = [P, C.c_void_p, C.c_void_p]
-        L.evx_episode_reduce.argtypes = [P, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
-        for name in ("evx_episode_init", "evx_episode_update", "evx_episode_discard", "evx_episode_reduce"):
-            getattr(L, name).restype = C.c_int
-        _inited = True
-    return L
-
-
-def echeck(rc, what):
-    if rc != 0:
-        raise _lib.EvacxError(f"{what} failed ({rc}): {elib().evx_episode_last_error().decode()}")
+# the loader's earlier name here, kept for callers written against them
+elib = lib
 
 
 def _need(name, t, n, dtype, device):
@@ -102,8 +71,8 @@ class _Slice:
         _need("reward", reward, self.E, torch.float64, dev)
         _need("done", done, self.E, torch.uint8, dev)
         _need("counts", counts, 2 * self.E, torch.int32, dev)
-        echeck(elib().evx_episode_update(C.byref(self.c), reward.data_ptr(), done.data_ptr(), counts.data_ptr(),
-                                         self.owner.cap, _stream()), "episode_update")
+        check(lib().evx_episode_update(C.byref(self.c), reward.data_ptr(), done.data_ptr(), counts.data_ptr(),
+                                       self.owner.cap, _stream()), "episode_update")
 
     def discard(self, mask: Optional[torch.Tensor] = None):
         """Drop the episode in progress of the masked envs (None: all): for envs reset from
@@ -113,7 +82,7 @@ class _Slice:
             if isinstance(m, torch.Tensor) and m.dtype == torch.bool:
                 m = m.to(torch.uint8)
             _need("mask", m, self.E, torch.uint8, self.owner.device)
-        echeck(elib().evx_episode_discard(C.byref(self.c), _ptr(m), _stream()), "episode_discard")
+        check(lib().evx_episode_discard(C.byref(self.c), _ptr(m), _stream()), "episode_discard")
 
 
 class EpisodeStats(_Slice):
@@ -161,7 +130,7 @@ class EpisodeStats(_Slice):
         self.last_return = self.last_ret
         self.rows = torch.zeros((n_layouts + 1) * ROW_WORDS, dtype=torch.int64, device=device)
         super().__init__(self, 0, E)
-        echeck(elib().evx_episode_init(C.byref(self.c), _stream()), "episode_init")
+        check(lib().evx_episode_init(C.byref(self.c), _stream()), "episode_init")
 
     def view(self, lo: int, n: int) -> _Slice:
         """The slice object of envs [lo, lo + n): its update / discard touch only those."""
@@ -175,8 +144,8 @@ class EpisodeStats(_Slice):
         ``clear``), copy the rows to the host (this waits for the current stream) and return
         the "all" row as a dict, with ``per_layout`` a list of the same dicts. With no episode
         in the window the means and rates are None."""
-        echeck(elib().evx_episode_reduce(C.byref(self.c), _ptr(self.layout_idx), self.n_layouts, self.cap,
-                                         self.rows.data_ptr(), int(bool(clear)), _stream()), "episode_reduce")
+        check(lib().evx_episode_reduce(C.byref(self.c), _ptr(self.layout_idx), self.n_layouts, self.cap,
+                                       self.rows.data_ptr(), int(bool(clear)), _stream()), "episode_reduce")
         host = self.rows.cpu()
         irows = host.view(self.n_layouts + 1, ROW_WORDS).tolist()
         frows = host.view(torch.float64).view(self.n_layouts + 1, ROW_WORDS).tolist()

@@ -77,24 +77,19 @@ class _EachRobot:
     (evx_gather_obs), run through learner r in eval mode and the actions scattered back."""
 
     def __init__(self, learners, layout, E: int):
-        from .qnet import qlib
         self.learners, self.lay, self.E, self.R = learners, layout, E, layout.R
         for lr in learners:
             _check_table(getattr(lr, "fast", None), layout)
         dev = layout.device
-        L = qlib()
-        L.evx_gather_obs.restype = C.c_int
-        L.evx_gather_obs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         self.idx = [(torch.arange(E, dtype=torch.int64, device=dev) * self.R + r).contiguous() for r in range(self.R)]
         self.obs = torch.zeros(E * OBS_WORDS, dtype=torch.int32, device=dev)
         self.act_r = torch.zeros(E, dtype=torch.int32, device=dev)
 
     def __call__(self, env, actions, seed: int, offset: int):
-        from .qnet import qcheck, qlib
         E, lay = self.E, self.lay
         for r, lr in enumerate(self.learners):
-            qcheck(qlib().evx_gather_obs(env.obs.data_ptr(), self.idx[r].data_ptr(), E, self.obs.data_ptr(), _stream()),
-                   "gather_obs")
+            _lib.check(_lib.lib().evx_gather_obs(env.obs.data_ptr(), self.idx[r].data_ptr(), E, self.obs.data_ptr(),
+                                                 _stream()), "gather_obs")
             fast = getattr(lr, "fast", None)
             if fast is not None:
                 fast.act(lay.c, self.obs, E, drop=None, actions=self.act_r, epsilon=0.0, act_seed=seed,
@@ -104,8 +99,8 @@ class _EachRobot:
                 _lib.check(_lib.lib().evx_obs_expand_f32(C.byref(lay.c), self.obs.data_ptr(), E, x.data_ptr(),
                                                          _stream()), "evx_obs_expand")
                 Q = lr.q_values(x, train=False, tag="eval")
-                qcheck(qlib().evx_act(Q.data_ptr(), E, lr.actions, 0.0, seed, offset + r * E, self.act_r.data_ptr(),
-                                      _stream()), "act")
+                _lib.check(_lib.lib().evx_act(Q.data_ptr(), E, lr.actions, 0.0, seed, offset + r * E,
+                                              self.act_r.data_ptr(), _stream()), "act")
             actions.view(E, self.R)[:, r].copy_(self.act_r)
 
 
@@ -146,7 +141,6 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
     multi = _multi_agent(learner, layout, E) if policy == "greedy" else None
     fast = getattr(learner, "fast", None) if policy == "greedy" and multi is None else None
     _check_table(fast, layout)
-    from .qnet import qcheck, qlib
 
     env = VecEnv(layout, E, layout_of=layout_of)
     env.seed([seed_base + i for i in range(E)])
@@ -168,8 +162,8 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
             raise RuntimeError(f"evaluate: {stats.summary(clear=False)['remaining']} envs have not finished "
                                f"{K} episodes after {steps} steps")
         if policy == "random":
-            qcheck(qlib().evx_act(q0.data_ptr(), n, N_ACTIONS, 1.0, seed, steps * n, actions.data_ptr(), _stream()),
-                   "act")
+            _lib.check(_lib.lib().evx_act(q0.data_ptr(), n, N_ACTIONS, 1.0, seed, steps * n, actions.data_ptr(),
+                                          _stream()), "act")
         elif each is not None:
             each(env, actions, seed, steps * n)
         elif multi is not None:
@@ -180,8 +174,8 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
         elif policy == "greedy":
             x = env.expand_obs(torch.float32)
             Q = learner.q_values(x.view(n, 11, 11, 6), train=False, tag="eval")
-            qcheck(qlib().evx_act(Q.data_ptr(), n, learner.actions, 0.0, seed, steps * n, actions.data_ptr(),
-                                  _stream()), "act")
+            _lib.check(_lib.lib().evx_act(Q.data_ptr(), n, learner.actions, 0.0, seed, steps * n, actions.data_ptr(),
+                                          _stream()), "act")
         if health is None:
             env.step(actions, auto_reset=True)
             stats.update(env.reward, env.done, env.counts)

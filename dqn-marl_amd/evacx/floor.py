@@ -9,7 +9,6 @@ the device the fields.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -17,19 +16,6 @@ import torch
 
 from . import _lib
 from .env import _stream
-
-_inited = False
-
-
-def flib():
-    global _inited
-    L = _lib.lib()
-    if not _inited:
-        L.evx_floor_last_error.restype = C.c_char_p
-        L.evx_floor_field.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
-        _inited = True
-    return L
-
 
 def floor_fields(valid: torch.Tensor, source: torch.Tensor, pen: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None, passes: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -49,11 +35,9 @@ def floor_fields(valid: torch.Tensor, source: torch.Tensor, pen: Optional[torch.
         pen = pen.contiguous()
     if out is None:
         out = torch.empty(n, GX, GY, dtype=torch.float64, device=valid.device)
-    rc = flib().evx_floor_field(n, GX, GY, valid.data_ptr(), source.data_ptr(),
-                                None if pen is None else pen.data_ptr(), out.data_ptr(),
-                                None if passes is None else passes.data_ptr(), _stream())
-    if rc != 0:
-        raise _lib.EvacxError(f"floor_field failed ({rc}): {flib().evx_floor_last_error().decode()}")
+    _lib.check(_lib.lib().evx_floor_field(n, GX, GY, valid.data_ptr(), source.data_ptr(),
+                                           None if pen is None else pen.data_ptr(), out.data_ptr(),
+                                           None if passes is None else passes.data_ptr(), _stream()), "floor_field")
     return out
 
 

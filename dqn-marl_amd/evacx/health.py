@@ -15,46 +15,17 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from ._lib import HEALTH_MAX_P as MAX_P, HEALTH_ROW_WORDS as ROW_WORDS
+from ._lib import check, evx_health, lib
 from .env import _ptr, _stream
 from .episodes import _need
-
-MAX_P = 16383   # EVX_HEALTH_MAX_P
-ROW_WORDS = 6   # sizeof(evx_health_row) / 8
 
 _I64 = ("n_total", "w_n", "w_has", "w_alive")
 _F64 = ("w_avg", "w_min", "w_lo", "last_avg", "last_min")
 _I32 = ("last_alive",)
 _TAB = ("tab_avg", "tab_min", "tab_alive")
-
-
-class evx_health(C.Structure):
-    _fields_ = [("E", C.c_int32), ("tab_slots", C.c_int32)] + \
-               [(n, C.c_void_p) for n in ["n_total", "w_n", "w_has", "w_alive", "w_avg", "w_min", "w_lo", "last_avg",
-                                         "last_min", "last_alive", "tab_avg", "tab_min", "tab_alive"]]
-
-
-_inited = False
-
-
-def hlib():
-    global _inited
-    L = _lib.lib()
-    if not _inited:
-        P = C.POINTER(evx_health)
-        L.evx_health_last_error.restype = C.c_char_p
-        L.evx_health_init.argtypes = [P, C.c_void_p]
-        L.evx_health_update.argtypes = [P, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        L.evx_health_reduce.argtypes = [P, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-        for name in ("evx_health_init", "evx_health_update", "evx_health_reduce"):
-            getattr(L, name).restype = C.c_int
-        _inited = True
-    return L
-
-
-def hcheck(rc, what):
-    if rc != 0:
-        raise _lib.EvacxError(f"{what} failed ({rc}): {hlib().evx_health_last_error().decode()}")
+# the loader's earlier name here, kept for callers written against them
+hlib = lib
 
 
 def _row_dict(irow, frow) -> dict:
@@ -93,8 +64,8 @@ class _Slice:
         _need("pk", pk, self.E * P, torch.int32, dev)
         _need("health", health, self.E * P, torch.float64, dev)
         _need("done", done, self.E, torch.uint8, dev)
-        hcheck(hlib().evx_health_update(C.byref(self.c), pk.data_ptr(), health.data_ptr(), P, done.data_ptr(),
-                                        self.owner.cap, _stream()), "health_update")
+        check(lib().evx_health_update(C.byref(self.c), pk.data_ptr(), health.data_ptr(), P, done.data_ptr(),
+                                      self.owner.cap, _stream()), "health_update")
 
 
 class HealthStats(_Slice):
@@ -136,7 +107,7 @@ class HealthStats(_Slice):
         self.device = self.w_avg.device  # with its index
         self.rows = torch.zeros((n_layouts + 1) * ROW_WORDS, dtype=torch.int64, device=device)
         super().__init__(self, 0, E)
-        hcheck(hlib().evx_health_init(C.byref(self.c), _stream()), "health_init")
+        check(lib().evx_health_init(C.byref(self.c), _stream()), "health_init")
 
     def view(self, lo: int, n: int) -> _Slice:
         """The slice object of envs [lo, lo + n): its update touches only those."""
@@ -151,8 +122,8 @@ class HealthStats(_Slice):
         "all" row: ``episodes``, ``health_episodes`` (the ones with somebody alive), ``avg_health``
         (mean of avg_health over those, None if none), ``min_health_mean``, ``min_health`` (the
         smallest), ``alive_mean`` (None with no episode), the raw sums, and ``per_layout``."""
-        hcheck(hlib().evx_health_reduce(C.byref(self.c), _ptr(self.layout_idx), self.n_layouts, self.rows.data_ptr(),
-                                        int(bool(clear)), _stream()), "health_reduce")
+        check(lib().evx_health_reduce(C.byref(self.c), _ptr(self.layout_idx), self.n_layouts, self.rows.data_ptr(),
+                                      int(bool(clear)), _stream()), "health_reduce")
         host = self.rows.cpu()
         irows = host.view(self.n_layouts + 1, ROW_WORDS).tolist()
         frows = host.view(torch.float64).view(self.n_layouts + 1, ROW_WORDS).tolist()

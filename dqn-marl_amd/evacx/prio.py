@@ -24,37 +24,9 @@ import ctypes as C
 
 import torch
 
-from . import _lib
-from .env import OBS_WORDS, _stream
+from ._lib import OBS_WORDS, check, evx_prio, lib
+from .env import _stream
 from .trainer import Replay
-
-
-class evx_prio(C.Structure):
-    _fields_ = [("capacity", C.c_int64), ("sum", C.c_void_p), ("mn", C.c_void_p), ("max_leaf", C.c_void_p),
-                ("owner", C.c_void_p)]
-
-
-_inited = False
-
-
-def plib():
-    global _inited
-    L = _lib.lib()
-    if not _inited:
-        P = C.POINTER(evx_prio)
-        L.evx_prio_last_error.restype = C.c_char_p
-        L.evx_prio_init.argtypes = [P, C.c_void_p]
-        L.evx_prio_set_range.argtypes = [P, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
-        L.evx_prio_update.argtypes = [P, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p]
-        L.evx_prio_sample.argtypes = [C.c_void_p, P, C.c_int32, C.c_double, C.c_uint64, C.c_uint64] + \
-            [C.c_void_p] * 8
-        _inited = True
-    return L
-
-
-def pcheck(rc, what):
-    if rc != 0:
-        raise _lib.EvacxError(f"{what} failed ({rc}): {plib().evx_prio_last_error().decode()}")
 
 
 class PrioReplay(Replay):
@@ -72,7 +44,7 @@ class PrioReplay(Replay):
         self.owner = torch.zeros(capacity, dtype=torch.int32, device=device)
         self.t = evx_prio(capacity=capacity, sum=self.tsum.data_ptr(), mn=self.tmin.data_ptr(),
                           max_leaf=self.max_leaf.data_ptr(), owner=self.owner.data_ptr())
-        pcheck(plib().evx_prio_init(C.byref(self.t), _stream()), "prio_init")
+        check(lib().evx_prio_init(C.byref(self.t), _stream()), "prio_init")
         self.unexposed = 0  # pushed transitions whose leaves are not set yet
 
     def push(self, *args, **kw):
@@ -85,18 +57,18 @@ class PrioReplay(Replay):
         next n_hide slots (those the next push overwrites)."""
         n_new = min(self.unexposed, self.capacity - n_hide)
         start = (self.pos - n_new) % self.capacity
-        pcheck(plib().evx_prio_set_range(C.byref(self.t), start, n_new, n_hide, _stream()), "prio_set_range")
+        check(lib().evx_prio_set_range(C.byref(self.t), start, n_new, n_hide, _stream()), "prio_set_range")
         self.unexposed = 0
 
     def sample_prio(self, B, beta, seed, offset, out, idx, w):
-        pcheck(plib().evx_prio_sample(C.byref(self.c), C.byref(self.t), B, beta, seed, offset,
-                                      out["s"].data_ptr(), out["s2"].data_ptr(), out["a"].data_ptr(),
-                                      out["r"].data_ptr(), out["done"].data_ptr(), idx.data_ptr(), w.data_ptr(),
-                                      _stream()), "prio_sample")
+        check(lib().evx_prio_sample(C.byref(self.c), C.byref(self.t), B, beta, seed, offset,
+                                    out["s"].data_ptr(), out["s2"].data_ptr(), out["a"].data_ptr(),
+                                    out["r"].data_ptr(), out["done"].data_ptr(), idx.data_ptr(), w.data_ptr(),
+                                    _stream()), "prio_sample")
 
     def update(self, idx, td_abs, B):
-        pcheck(plib().evx_prio_update(C.byref(self.t), idx.data_ptr(), td_abs.data_ptr(), B, self.eps, self.alpha,
-                                      _stream()), "prio_update")
+        check(lib().evx_prio_update(C.byref(self.t), idx.data_ptr(), td_abs.data_ptr(), B, self.eps, self.alpha,
+                                    _stream()), "prio_update")
 
 
 __all__ = ["PrioReplay", "evx_prio", "OBS_WORDS"]

@@ -24,9 +24,10 @@ from typing import List, Optional
 
 import torch
 
+from ._lib import check, evx_adam, evx_qmlp_fwd_out, evx_qmlp_grads, lib
 from .env import _stream
-from .qmlp import HID, HID2, K1X, NACT, MLPFast, _need, evx_qmlp_fwd_out, evx_qmlp_grads, mcheck, mlib
-from .qnet import DROPOUT_P, FlatParams, evx_adam, layer_specs, param_shapes, qcheck, qlib
+from .qmlp import HID, HID2, K1X, NACT, MLPFast, _need
+from .qnet import DROPOUT_P, FlatParams, layer_specs, param_shapes
 
 
 def _p(t):
@@ -60,7 +61,7 @@ class GroupedLearner:
         self.G, self.device = int(nets), torch.device(device)
         self.shapes = param_shapes(layer_specs("mlp"))
         self.npar = sum(int(torch.Size(s).numel()) for s in self.shapes.values())
-        assert self.npar == int(mlib().evx_qmlp_nparams()), "MLP parameter count"
+        assert self.npar == int(lib().evx_qmlp_nparams()), "MLP parameter count"
         f32 = dict(dtype=torch.float32, device=self.device)
         G = self.G
         self.flat = torch.zeros(G, self.npar, **f32)
@@ -80,7 +81,7 @@ class GroupedLearner:
         self.lr, self.gamma, self.max_norm, self.betas, self.eps = lr, gamma, max_norm, betas, eps
         self.seed, self.drop_stream, self.adam_step, self._act_calls = seed, 0, 0, 0
         self.drop_p = DROPOUT_P  # nn.Dropout(0.2) of DQNNetwork (0: off, tests)
-        self.nss = int(mlib().evx_qmlp_norm_parts())
+        self.nss = int(lib().evx_qmlp_norm_parts())
         self._ss = torch.zeros(G, self.nss, **f32)
         self.norm = torch.zeros(G, **f32)
         self.loss = torch.zeros(G, **f32)
@@ -108,8 +109,8 @@ class GroupedLearner:
         d = MLPFast._drop((self.seed if drop_seed is None else drop_seed, drop_stream, drop_p))
         o = evx_qmlp_fwd_out(q=_p(q), actions=_p(actions), epsilon=float(epsilon), act_seed=act_seed,
                              act_offset=act_offset)
-        mcheck(mlib().evx_qmlp_act_g(C.byref(lay_c), obs.data_ptr(), n, G, C.byref(self.fast.c), C.byref(d),
-                                     C.byref(o), _stream()), "qmlp_act_g")
+        check(lib().evx_qmlp_act_g(C.byref(lay_c), obs.data_ptr(), n, G, C.byref(self.fast.c), C.byref(d),
+                                   C.byref(o), _stream()), "qmlp_act_g")
 
     # ---------------------------------------------------------------- learn
     def learn_obs(self, lay_c, s_obs, a, r, done, s2_obs, B: int, update: bool = True):
@@ -131,15 +132,15 @@ class GroupedLearner:
         d_tg = MLPFast._drop((self.seed, self.drop_stream + 1, self.drop_p))
         o_on = MLPFast._out(H1, X, H2, Q)
         o_tg = MLPFast._out(H1t, None, None, Qt)
-        mcheck(mlib().evx_qmlp_forward2_g(C.byref(lay_c), B, G, s_obs.data_ptr(), C.byref(self.fast.c), C.byref(d_on),
-                                          C.byref(o_on), s2_obs.data_ptr(), C.byref(self.fast_t.c), C.byref(d_tg),
-                                          C.byref(o_tg), _stream()), "qmlp_forward2_g")
+        check(lib().evx_qmlp_forward2_g(C.byref(lay_c), B, G, s_obs.data_ptr(), C.byref(self.fast.c), C.byref(d_on),
+                                        C.byref(o_on), s2_obs.data_ptr(), C.byref(self.fast_t.c), C.byref(d_tg),
+                                        C.byref(o_tg), _stream()), "qmlp_forward2_g")
         dQ = self._buf("dq", G * B * NACT, torch.float32)
-        tw = self._buf("td_ws", max(1, int(qlib().evx_td_loss_ws_floats(B, G))), torch.float32)
-        qcheck(qlib().evx_td_loss_zero_g(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(), done.data_ptr(),
-                                         self.gamma, B, G, None, dQ.data_ptr(), self.loss.data_ptr(), None,
-                                         self.gflat.data_ptr(), self.gflat.numel(), tw.data_ptr(), tw.numel(),
-                                         _stream()), "td_loss_zero_g")
+        tw = self._buf("td_ws", max(1, int(lib().evx_td_loss_ws_floats(B, G))), torch.float32)
+        check(lib().evx_td_loss_zero_g(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(), done.data_ptr(),
+                                       self.gamma, B, G, None, dQ.data_ptr(), self.loss.data_ptr(), None,
+                                       self.gflat.data_ptr(), self.gflat.numel(), tw.data_ptr(), tw.numel(),
+                                       _stream()), "td_loss_zero_g")
         self._backward(B, dQ, X, H1, H2)
         if update:
             self.step_optimizer()
@@ -149,14 +150,14 @@ class GroupedLearner:
         G = self.G
         dz2 = self._buf("dz2", G * 2 * B * HID2, torch.int16)
         dz1 = self._buf("dz1", G * 2 * B * HID, torch.int16)
-        part = self._buf("part", G * int(mlib().evx_qmlp_backward_part_floats(B)), torch.float32)
+        part = self._buf("part", G * int(lib().evx_qmlp_backward_part_floats(B)), torch.float32)
         g0 = self.grads[0]
         g = evx_qmlp_grads(w1=g0["fc1.weight"].data_ptr(), b1=g0["fc1.bias"].data_ptr(), w2=g0["fc2.weight"].data_ptr(),
                            b2=g0["fc2.bias"].data_ptr(), w3=g0["fc3.weight"].data_ptr(), b3=g0["fc3.bias"].data_ptr(),
                            part=part.data_ptr())
-        mcheck(mlib().evx_qmlp_backward_ss_g(C.byref(self.fast.c), B, G, dQ.data_ptr(), X.data_ptr(), H1.data_ptr(),
-                                             H2.data_ptr(), float(self.drop_p), dz2.data_ptr(), dz1.data_ptr(),
-                                             C.byref(g), self._ss.data_ptr(), _stream()), "qmlp_backward_ss_g")
+        check(lib().evx_qmlp_backward_ss_g(C.byref(self.fast.c), B, G, dQ.data_ptr(), X.data_ptr(), H1.data_ptr(),
+                                           H2.data_ptr(), float(self.drop_p), dz2.data_ptr(), dz1.data_ptr(),
+                                           C.byref(g), self._ss.data_ptr(), _stream()), "qmlp_backward_ss_g")
 
     def step_optimizer(self):
         """clip_grad_norm_(net g, max_norm) + Adam for every net (one launch, evx_qmlp_adam_pack3_g)."""
@@ -164,13 +165,13 @@ class GroupedLearner:
         h = evx_adam(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=0.0,
                      step=self.adam_step)
         b = self.fast.bufs
-        mcheck(mlib().evx_qmlp_adam_pack3_g(self.flat.data_ptr(), self.gflat.data_ptr(), self.m.data_ptr(),
-                                            self.v.data_ptr(), float(self.max_norm or 0.0), C.byref(h),
-                                            b["w1b"].data_ptr(), b["w1l"].data_ptr(), b["b1c"].data_ptr(),
-                                            b["w2b"].data_ptr(), b["w2l"].data_ptr(), b["w2t"].data_ptr(),
-                                            b["w2tl"].data_ptr(), b["w1o"].data_ptr(), b["w1ol"].data_ptr(),
-                                            self._ss.data_ptr(), self.nss, self.norm.data_ptr(), self.G, _stream()),
-               "qmlp_adam_pack3_g")
+        check(lib().evx_qmlp_adam_pack3_g(self.flat.data_ptr(), self.gflat.data_ptr(), self.m.data_ptr(),
+                                          self.v.data_ptr(), float(self.max_norm or 0.0), C.byref(h),
+                                          b["w1b"].data_ptr(), b["w1l"].data_ptr(), b["b1c"].data_ptr(),
+                                          b["w2b"].data_ptr(), b["w2l"].data_ptr(), b["w2t"].data_ptr(),
+                                          b["w2tl"].data_ptr(), b["w1o"].data_ptr(), b["w1ol"].data_ptr(),
+                                          self._ss.data_ptr(), self.nss, self.norm.data_ptr(), self.G, _stream()),
+              "qmlp_adam_pack3_g")
 
     def sync_target(self, nets: Optional[List[int]] = None):
         """agent.update_target_network() of the given nets (all by default)."""
@@ -213,7 +214,7 @@ class GroupedQMix:
         n = agents.G
         if embed != 32:
             raise ValueError("GroupedQMix: embed_dim 32 (the reference's MixingNetwork)")
-        self.nmix = int(mlib().evx_qmix_nparams(n))
+        self.nmix = int(lib().evx_qmix_nparams(n))
         f32 = dict(dtype=torch.float32, device=agents.device)
         self.mix = torch.zeros(self.nmix, **f32)
         if mixing is not None:  # a MixingNetwork (evacx.qmix / the reference's): its state_dict order
@@ -252,27 +253,25 @@ class GroupedQMix:
         d_tg = MLPFast._drop((A.seed, A.drop_stream + 1, A.drop_p))
         o_on = MLPFast._out(H1, X, H2, Q)
         o_tg = MLPFast._out(H1t, None, None, Qt)
-        mcheck(mlib().evx_qmlp_forward2_g(C.byref(lay_c), B, n, s_obs.data_ptr(), C.byref(A.fast.c), C.byref(d_on),
-                                          C.byref(o_on), s2_obs.data_ptr(), C.byref(A.fast_t.c), C.byref(d_tg),
-                                          C.byref(o_tg), _stream()), "qmlp_forward2_g")
+        check(lib().evx_qmlp_forward2_g(C.byref(lay_c), B, n, s_obs.data_ptr(), C.byref(A.fast.c), C.byref(d_on),
+                                        C.byref(o_on), s2_obs.data_ptr(), C.byref(A.fast_t.c), C.byref(d_tg),
+                                        C.byref(o_tg), _stream()), "qmlp_forward2_g")
         dQ = A._buf("dq", n * B * NACT, torch.float32)
-        part = A._buf("mixpart", int(mlib().evx_qmix_part_floats(B, n)), torch.float32)
-        rc = mlib().evx_qmix_loss(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(), done.data_ptr(),
+        part = A._buf("mixpart", int(lib().evx_qmix_part_floats(B, n)), torch.float32)
+        check(lib().evx_qmix_loss(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(), done.data_ptr(),
                                   A.gamma, B, n, self.mix.data_ptr(), self.mix_t.data_ptr(), dQ.data_ptr(),
                                   self.mix_g.data_ptr(), self.loss.data_ptr(), part.data_ptr(), A.gflat.data_ptr(),
-                                  A.gflat.numel(), _stream())
-        if rc != 0:
-            raise RuntimeError(f"qmix_loss failed ({rc}): {mlib().evx_qmix_last_error().decode()}")
+                                  A.gflat.numel(), _stream()), "qmix_loss")
         A._backward(B, dQ, X, H1, H2)
         A.step_optimizer()  # clip_grad_norm_(agent_i, 1.0) + agent_i.optimizer.step()
-        L = qlib()
-        qcheck(L.evx_sumsq_norm(self.mix_g.data_ptr(), self.nmix, self._scratch.data_ptr(), self._scratch.numel(),
-                                self.mix_norm.data_ptr(), _stream()), "sumsq_norm")
+        L = lib()
+        check(L.evx_sumsq_norm(self.mix_g.data_ptr(), self.nmix, self._scratch.data_ptr(), self._scratch.numel(),
+                               self.mix_norm.data_ptr(), _stream()), "sumsq_norm")
         self.mix_step += 1
         h = evx_adam(lr=self.mix_lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=self.mix_step)
-        qcheck(L.evx_clip_adam(self.mix.data_ptr(), self.mix_g.data_ptr(), self.mix_m.data_ptr(), self.mix_v.data_ptr(),
-                               self.nmix, self.mix_norm.data_ptr(), float(A.max_norm or 0.0), C.byref(h), _stream()),
-               "clip_adam")
+        check(L.evx_clip_adam(self.mix.data_ptr(), self.mix_g.data_ptr(), self.mix_m.data_ptr(), self.mix_v.data_ptr(),
+                              self.nmix, self.mix_norm.data_ptr(), float(A.max_norm or 0.0), C.byref(h), _stream()),
+              "clip_adam")
         return self.loss
 
     def sync_targets(self):

@@ -17,12 +17,15 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from ._lib import (check, evx_qmlp_dropout, evx_qmlp_fwd_out, evx_qmlp_grads, evx_qmlp_params,  # noqa: F401
+                   evx_td_opts, lib)
 from .env import _stream
 
 HID, HID2, NACT, K1, K1P = 512, 256, 5, 726, 512
 K1X = 640  # x3: compact K + one danger-residual slot per cell
 NCELL, CENTRE_COL = 121, 60 * 6 + 5
+# the loader's earlier name here, kept for callers written against them
+mlib = lib
 
 
 def compact_ref_cols() -> np.ndarray:
@@ -30,28 +33,6 @@ def compact_ref_cols() -> np.ndarray:
     features k < 484 (k = 4 * cell + f <-> channel f + 1; evx_qmlp_pack)."""
     k = np.arange(4 * NCELL)
     return (k >> 2) * 6 + (k & 3) + 1
-
-
-class evx_qmlp_params(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ["w1", "b1c", "w2", "w2t", "b2", "w3", "b3", "w1o", "stat"]] + \
-        [("stat_fs", C.c_int32), ("x3", C.c_int32)] + [(n, C.c_void_p) for n in ["w1l", "w2l", "w2tl", "w1ol"]] + \
-        [("stat_x0", C.c_int32), ("stat_nx", C.c_int32), ("stat_xin", C.c_void_p)]
-
-
-class evx_qmlp_dropout(C.Structure):
-    _fields_ = [("seed", C.c_uint32), ("stream", C.c_uint32), ("p", C.c_float), ("row0", C.c_uint32),
-                ("mask", C.c_void_p)]
-
-
-class evx_qmlp_grads(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ["w1", "b1", "w2", "b2", "w3", "b3", "part"]]
-
-
-class evx_td_opts(C.Structure):
-    """TD options (include/evacx.h): sel = the bootstrap action per row (Double-Q; NULL: the
-    target's maximum), huber_delta (0: squared error), gamma_row = the discount per row (n-step
-    rows; NULL: the scalar gamma)."""
-    _fields_ = [("sel", C.c_void_p), ("huber_delta", C.c_float), ("gamma_row", C.c_void_p)]
 
 
 def validate_td_options(loss: str = "mse", huber_delta: float = 1.0, target_tau: float = 0.0) -> None:
@@ -75,93 +56,10 @@ def polyak_coeffs(tau: float):
     return t, float(np.float32(1.0 - t))
 
 
-class evx_qmlp_fwd_out(C.Structure):
-    _fields_ = [("h1", C.c_void_p), ("x", C.c_void_p), ("h2", C.c_void_p), ("q", C.c_void_p),
-                ("actions", C.c_void_p), ("epsilon", C.c_float), ("act_seed", C.c_uint64),
-                ("act_offset", C.c_uint64), ("perm", C.c_void_p), ("rows_per_env", C.c_int32),
-                ("act_ws", C.c_void_p)]
-
-
-_inited = False
-
-
-def mlib():
-    global _inited
-    L = _lib.lib()
-    if not _inited:
-        L.evx_qmlp_last_error.restype = C.c_char_p
-        L.evx_qmlp_pack.argtypes = [C.c_void_p] * 9
-        L.evx_qmlp_pack3.argtypes = [C.c_void_p] * 11
-        if hasattr(L, "evx_qmlp_stat_x"):  # (absent from older builds loaded through EVX_LIB for A/Bs)
-            L.evx_qmlp_stat_x.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(evx_qmlp_params),
-                                          C.c_void_p, C.c_void_p]
-            L.evx_qmlp_expand_x3.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-        L.evx_qmlp_stat.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(evx_qmlp_params), C.c_void_p,
-                                    C.c_void_p]
-        L.evx_qmlp_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(evx_qmlp_params),
-                                       C.POINTER(evx_qmlp_dropout), C.POINTER(evx_qmlp_fwd_out), C.c_void_p]
-        L.evx_qmlp_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(evx_qmlp_params),
-                                   C.POINTER(evx_qmlp_dropout), C.POINTER(evx_qmlp_fwd_out), C.c_void_p]
-        L.evx_qmlp_act64.argtypes = L.evx_qmlp_act.argtypes
-        L.evx_qmlp_forward2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(evx_qmlp_params),
-                                        C.POINTER(evx_qmlp_dropout), C.POINTER(evx_qmlp_fwd_out), C.c_void_p,
-                                        C.POINTER(evx_qmlp_params), C.POINTER(evx_qmlp_dropout),
-                                        C.POINTER(evx_qmlp_fwd_out), C.c_void_p]
-        L.evx_qmlp_backward_ss.argtypes = [C.POINTER(evx_qmlp_params), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(evx_qmlp_grads),
-                                           C.c_int32, C.c_void_p, C.c_void_p]
-        L.evx_qmlp_td_backward_ss.argtypes = [C.POINTER(evx_qmlp_params), C.c_int32] + [C.c_void_p] * 5 + \
-            [C.c_float] + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_void_p, C.POINTER(evx_qmlp_grads),
-                                              C.c_void_p, C.c_void_p]
-        L.evx_qmlp_td_backward_opt.argtypes = L.evx_qmlp_td_backward_ss.argtypes[:-1] + \
-            [C.POINTER(evx_td_opts), C.c_void_p]
-        L.evx_qmlp_polyak_pack3.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 10
-        L.evx_qmlp_norm_parts.restype = C.c_int32
-        L.evx_qmlp_nparams.restype = C.c_int64
-        if hasattr(L, "evx_qmlp_act_ws_ints"):  # (absent from older builds loaded through EVX_LIB for A/Bs)
-            L.evx_qmlp_act_ws_ints.restype = C.c_int64
-            L.evx_qmlp_act_ws_ints.argtypes = [C.c_int32]
-        L.evx_qmlp_sumsq_parts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.evx_qmlp_adam_pack3.argtypes = [C.c_void_p] * 4 + [C.c_float, C.c_void_p] + [C.c_void_p] * 10 + \
-            [C.c_int32, C.c_void_p, C.c_void_p]
-        L.evx_qmlp_pack_occ3.argtypes = [C.c_void_p] * 4
-        L.evx_qmlp_backward_part_floats.restype = C.c_int64
-        L.evx_qmlp_backward_part_floats.argtypes = [C.c_int32]
-        L.evx_qmlp_backward.argtypes = [C.POINTER(evx_qmlp_params), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(evx_qmlp_grads),
-                                        C.c_int32, C.c_void_p]
-        # grouped nets (evacx.qgroup)
-        L.evx_qmlp_act_g.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(evx_qmlp_params),
-                                     C.POINTER(evx_qmlp_dropout), C.POINTER(evx_qmlp_fwd_out), C.c_void_p]
-        L.evx_qmlp_forward2_g.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(evx_qmlp_params),
-                                          C.POINTER(evx_qmlp_dropout), C.POINTER(evx_qmlp_fwd_out), C.c_void_p,
-                                          C.POINTER(evx_qmlp_params), C.POINTER(evx_qmlp_dropout),
-                                          C.POINTER(evx_qmlp_fwd_out), C.c_void_p]
-        L.evx_qmlp_backward_ss_g.argtypes = [C.POINTER(evx_qmlp_params), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                             C.POINTER(evx_qmlp_grads), C.c_void_p, C.c_void_p]
-        L.evx_qmlp_adam_pack3_g.argtypes = [C.c_void_p] * 4 + [C.c_float, C.c_void_p] + [C.c_void_p] * 10 + \
-            [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-        L.evx_qmix_last_error.restype = C.c_char_p
-        L.evx_qmix_nparams.restype = C.c_int32
-        L.evx_qmix_part_floats.restype = C.c_int64
-        L.evx_qmix_part_floats.argtypes = [C.c_int32, C.c_int32]
-        L.evx_qmix_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
-                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        _inited = True
-    return L
-
-
 def act_ws_ints(n: int) -> int:
     """int32 elements of the act's workspace for n rows (evx_qmlp_act_ws_ints)."""
-    L = mlib()
+    L = lib()
     return int(L.evx_qmlp_act_ws_ints(int(n))) if hasattr(L, "evx_qmlp_act_ws_ints") else 0
-
-
-def mcheck(rc, what):
-    if rc != 0:
-        raise _lib.EvacxError(f"{what} failed ({rc}): {mlib().evx_qmlp_last_error().decode()}")
 
 
 def _p(t):
@@ -233,19 +131,19 @@ class MLPFast:
 
     def repack(self):
         if self.x3:
-            mcheck(mlib().evx_qmlp_pack3(self.P["fc1.weight"].data_ptr(), self.P["fc1.bias"].data_ptr(),
-                                         self.P["fc2.weight"].data_ptr(), self.w1b.data_ptr(), self.w1l.data_ptr(),
-                                         self.b1c.data_ptr(), self.w2b.data_ptr(), self.w2l.data_ptr(),
-                                         self.w2t.data_ptr(), self.w2tl.data_ptr(), _stream()), "qmlp_pack3")
-            mcheck(mlib().evx_qmlp_pack_occ3(self.P["fc1.weight"].data_ptr(), self.w1o.data_ptr(),
-                                             self.w1ol.data_ptr(), _stream()), "qmlp_pack_occ3")
+            check(lib().evx_qmlp_pack3(self.P["fc1.weight"].data_ptr(), self.P["fc1.bias"].data_ptr(),
+                                       self.P["fc2.weight"].data_ptr(), self.w1b.data_ptr(), self.w1l.data_ptr(),
+                                       self.b1c.data_ptr(), self.w2b.data_ptr(), self.w2l.data_ptr(),
+                                       self.w2t.data_ptr(), self.w2tl.data_ptr(), _stream()), "qmlp_pack3")
+            check(lib().evx_qmlp_pack_occ3(self.P["fc1.weight"].data_ptr(), self.w1o.data_ptr(),
+                                           self.w1ol.data_ptr(), _stream()), "qmlp_pack_occ3")
             if self._static is not None:
                 self._rebuild_static()
             return
-        mcheck(mlib().evx_qmlp_pack(self.P["fc1.weight"].data_ptr(), self.P["fc1.bias"].data_ptr(),
-                                    self.P["fc2.weight"].data_ptr(), self.w1b.data_ptr(), self.b1c.data_ptr(),
-                                    self.w2b.data_ptr(), self.w2t.data_ptr(), self.w1o.data_ptr(), _stream()),
-               "qmlp_pack")
+        check(lib().evx_qmlp_pack(self.P["fc1.weight"].data_ptr(), self.P["fc1.bias"].data_ptr(),
+                                  self.P["fc2.weight"].data_ptr(), self.w1b.data_ptr(), self.b1c.data_ptr(),
+                                  self.w2b.data_ptr(), self.w2t.data_ptr(), self.w1o.data_ptr(), _stream()),
+              "qmlp_pack")
         if self._static is not None:
             self._rebuild_static()
 
@@ -254,13 +152,13 @@ class MLPFast:
         network's x3 operand repack, one launch (evx_qmlp_adam_pack3); hyper: evacx.qnet.evx_adam."""
         if not self.x3:
             raise ValueError("adam_step: the fused repack writes the x3 operand layout")
-        mcheck(mlib().evx_qmlp_adam_pack3(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), float(max_norm),
-                                          C.byref(hyper), self.w1b.data_ptr(), self.w1l.data_ptr(),
-                                          self.b1c.data_ptr(), self.w2b.data_ptr(), self.w2l.data_ptr(),
-                                          self.w2t.data_ptr(), self.w2tl.data_ptr(), self.w1o.data_ptr(),
-                                          self.w1ol.data_ptr(), ss.data_ptr(), int(mlib().evx_qmlp_norm_parts()),
-                                          _p(norm_out), _stream()),
-               "qmlp_adam_pack3")
+        check(lib().evx_qmlp_adam_pack3(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), float(max_norm),
+                                        C.byref(hyper), self.w1b.data_ptr(), self.w1l.data_ptr(),
+                                        self.b1c.data_ptr(), self.w2b.data_ptr(), self.w2l.data_ptr(),
+                                        self.w2t.data_ptr(), self.w2tl.data_ptr(), self.w1o.data_ptr(),
+                                        self.w1ol.data_ptr(), ss.data_ptr(), int(lib().evx_qmlp_norm_parts()),
+                                        _p(norm_out), _stream()),
+              "qmlp_adam_pack3")
         if self._static is not None:  # the act table follows the weights
             self._rebuild_static()
 
@@ -269,21 +167,21 @@ class MLPFast:
         network's x3 operand repack, one launch (evx_qmlp_polyak_pack3); then the act table."""
         if not self.x3:
             raise ValueError("polyak_step: the fused repack writes the x3 operand layout")
-        if online_flat.numel() != target_flat.numel() or target_flat.numel() != int(mlib().evx_qmlp_nparams()):
+        if online_flat.numel() != target_flat.numel() or target_flat.numel() != int(lib().evx_qmlp_nparams()):
             raise ValueError("polyak_step: flat buffers of evx_qmlp_nparams() floats")
         t, omt = polyak_coeffs(tau)
-        mcheck(mlib().evx_qmlp_polyak_pack3(online_flat.data_ptr(), target_flat.data_ptr(), t, omt,
-                                            self.w1b.data_ptr(), self.w1l.data_ptr(), self.b1c.data_ptr(),
-                                            self.w2b.data_ptr(), self.w2l.data_ptr(), self.w2t.data_ptr(),
-                                            self.w2tl.data_ptr(), self.w1o.data_ptr(), self.w1ol.data_ptr(),
-                                            _stream()), "qmlp_polyak_pack3")
+        check(lib().evx_qmlp_polyak_pack3(online_flat.data_ptr(), target_flat.data_ptr(), t, omt,
+                                          self.w1b.data_ptr(), self.w1l.data_ptr(), self.b1c.data_ptr(),
+                                          self.w2b.data_ptr(), self.w2l.data_ptr(), self.w2t.data_ptr(),
+                                          self.w2tl.data_ptr(), self.w1o.data_ptr(), self.w1ol.data_ptr(),
+                                          _stream()), "qmlp_polyak_pack3")
         if self._static is not None:  # the act table follows the weights
             self._rebuild_static()
 
     @staticmethod
     def sumsq_parts(g, ss):
         """The squared-norm partials of a flat gradient buffer (evx_qmlp_sumsq_parts)."""
-        mcheck(mlib().evx_qmlp_sumsq_parts(g.data_ptr(), ss.data_ptr(), _stream()), "qmlp_sumsq_parts")
+        check(lib().evx_qmlp_sumsq_parts(g.data_ptr(), ss.data_ptr(), _stream()), "qmlp_sumsq_parts")
 
     def attach_static(self, lay_c, L: int, W: int, t_max: int, x_range=None):
         """Enable act()'s fast path for observations at fire step >= t_max (the fire has
@@ -307,11 +205,11 @@ class MLPFast:
         # x3: the table rows' fc1 inputs are fixed (every centre at the last fire step, no occupancy):
         # expanded once here, every rebuild reads them (evx_qmlp_stat_x) instead of regenerating them
         self._static_x = None
-        if self.x3 and hasattr(mlib(), "evx_qmlp_stat_x"):
+        if self.x3 and hasattr(lib(), "evx_qmlp_stat_x"):
             n = self._static[1].shape[0]
             self._static_x = torch.empty(n * K1X, dtype=torch.int16, device=self.device)
-            mcheck(mlib().evx_qmlp_expand_x3(C.byref(lay_c), self._static[1].data_ptr(), n,
-                                             self._static_x.data_ptr(), _stream()), "qmlp_expand_x3")
+            check(lib().evx_qmlp_expand_x3(C.byref(lay_c), self._static[1].data_ptr(), n,
+                                           self._static_x.data_ptr(), _stream()), "qmlp_expand_x3")
         self._rebuild_static()
         self.c.w1o, self.c.stat, self.c.stat_fs = self.w1o.data_ptr(), self._static[2].data_ptr(), int(t_max)
         self.c.stat_x0, self.c.stat_nx = x0, nx
@@ -326,15 +224,15 @@ class MLPFast:
     def _rebuild_static(self):
         lay_c, ob, T = self._static
         if getattr(self, "_static_x", None) is not None:
-            mcheck(mlib().evx_qmlp_stat_x(C.byref(lay_c), ob.data_ptr(), self._static_x.data_ptr(), ob.shape[0],
-                                          C.byref(self.c), T.data_ptr(), _stream()), "qmlp_stat_x")
+            check(lib().evx_qmlp_stat_x(C.byref(lay_c), ob.data_ptr(), self._static_x.data_ptr(), ob.shape[0],
+                                        C.byref(self.c), T.data_ptr(), _stream()), "qmlp_stat_x")
             return
         self.stat_table(lay_c, ob, ob.shape[0], T)
 
     def stat_table(self, lay_c, obs: torch.Tensor, n: int, out: torch.Tensor):
         """evx_qmlp_stat: fc1's pre-activation (f32, bias included) of n observations -> out [n][512]."""
-        mcheck(mlib().evx_qmlp_stat(C.byref(lay_c), obs.data_ptr(), n, C.byref(self.c), out.data_ptr(), _stream()),
-               "qmlp_stat")
+        check(lib().evx_qmlp_stat(C.byref(lay_c), obs.data_ptr(), n, C.byref(self.c), out.data_ptr(), _stream()),
+              "qmlp_stat")
 
     def forward(self, lay_c, obs: torch.Tensor, n: int, h1: torch.Tensor, drop=None, x=None, h2=None, q=None,
                 actions=None, epsilon=0.0, act_seed=0, act_offset=0):
@@ -344,9 +242,9 @@ class MLPFast:
         d = self._drop(drop) if drop else None
         o = evx_qmlp_fwd_out(h1=_p(h1), x=_p(x), h2=_p(h2), q=_p(q), actions=_p(actions), epsilon=float(epsilon),
                              act_seed=act_seed, act_offset=act_offset)
-        mcheck(mlib().evx_qmlp_forward(C.byref(lay_c), obs.data_ptr(), n, C.byref(self.c),
-                                       C.byref(d) if d is not None else None, C.byref(o), _stream()),
-               "qmlp_forward")
+        check(lib().evx_qmlp_forward(C.byref(lay_c), obs.data_ptr(), n, C.byref(self.c),
+                                     C.byref(d) if d is not None else None, C.byref(o), _stream()),
+              "qmlp_forward")
 
 
     def act(self, lay_c, obs: torch.Tensor, n: int, drop=None, q=None, actions=None, epsilon=0.0, act_seed=0,
@@ -370,9 +268,9 @@ class MLPFast:
         d = self._drop(drop) if drop else None
         o = evx_qmlp_fwd_out(q=_p(q), actions=_p(actions), epsilon=float(epsilon), act_seed=act_seed,
                              act_offset=act_offset, perm=_p(perm), rows_per_env=int(rows_per_env), act_ws=_p(ws))
-        fn = mlib().evx_qmlp_act64 if kernel64 else mlib().evx_qmlp_act
-        mcheck(fn(C.byref(lay_c), obs.data_ptr(), n, C.byref(self.c), C.byref(d) if d is not None else None,
-                  C.byref(o), _stream()), "qmlp_act")
+        fn = lib().evx_qmlp_act64 if kernel64 else lib().evx_qmlp_act
+        check(fn(C.byref(lay_c), obs.data_ptr(), n, C.byref(self.c), C.byref(d) if d is not None else None,
+                 C.byref(o), _stream()), "qmlp_act")
 
     @staticmethod
     def _drop(drop):
@@ -397,15 +295,15 @@ class MLPFast:
             _need("forward_pair q", o.get("q"), n, NACT)
         d0, d1 = MLPFast._drop(drop0), MLPFast._drop(drop1)
         o0, o1 = MLPFast._out(**out0), MLPFast._out(**out1)
-        mcheck(mlib().evx_qmlp_forward2(C.byref(lay_c), n, obs0.data_ptr(), C.byref(net0.c), C.byref(d0), C.byref(o0),
-                                        obs1.data_ptr(), C.byref(net1.c), C.byref(d1), C.byref(o1), _stream()),
-               "qmlp_forward2")
+        check(lib().evx_qmlp_forward2(C.byref(lay_c), n, obs0.data_ptr(), C.byref(net0.c), C.byref(d0), C.byref(o0),
+                                      obs1.data_ptr(), C.byref(net1.c), C.byref(d1), C.byref(o1), _stream()),
+              "qmlp_forward2")
 
     def _grads(self, B, grads):
         g = evx_qmlp_grads(**{k: grads[f"fc{k[1]}.{'weight' if k[0] == 'w' else 'bias'}"].data_ptr()
                               for k in ["w1", "b1", "w2", "b2", "w3", "b3"]})
         # every gradient sum through partials added in a fixed order (the same bits on every run)
-        nf = int(mlib().evx_qmlp_backward_part_floats(B))
+        nf = int(lib().evx_qmlp_backward_part_floats(B))
         if self._part is None or self._part.numel() < nf:
             self._part = torch.empty(nf, dtype=torch.float32, device=self.device)
         g.part = self._part.data_ptr()
@@ -425,24 +323,24 @@ class MLPFast:
             if t.numel() < n:
                 raise ValueError(f"qmlp td_backward: {name} has {t.numel()} elements, needs {n}")
         if ss is not None:
-            _need("td_backward ss", ss, 1, int(mlib().evx_qmlp_norm_parts()))
+            _need("td_backward ss", ss, 1, int(lib().evx_qmlp_norm_parts()))
         g = self._grads(B, grads)
         if sel is not None or huber_delta or gamma_row is not None:
             _need("td_backward sel", sel, B, 1)
             _need("td_backward gamma_row", gamma_row, B, 1)
             o = td_opts(sel, huber_delta, gamma_row)
-            mcheck(mlib().evx_qmlp_td_backward_opt(C.byref(self.c), B, Q.data_ptr(), Qt.data_ptr(), act.data_ptr(),
-                                                   rew.data_ptr(), done.data_ptr(), float(gamma), _p(weights),
-                                                   loss.data_ptr(), _p(td_abs), x.data_ptr(), h1.data_ptr(),
-                                                   h2.data_ptr(), float(drop_p), dz2.data_ptr(), dz1.data_ptr(),
-                                                   C.byref(g), _p(ss), C.byref(o), _stream()),
-                   "qmlp_td_backward_opt")
+            check(lib().evx_qmlp_td_backward_opt(C.byref(self.c), B, Q.data_ptr(), Qt.data_ptr(), act.data_ptr(),
+                                                 rew.data_ptr(), done.data_ptr(), float(gamma), _p(weights),
+                                                 loss.data_ptr(), _p(td_abs), x.data_ptr(), h1.data_ptr(),
+                                                 h2.data_ptr(), float(drop_p), dz2.data_ptr(), dz1.data_ptr(),
+                                                 C.byref(g), _p(ss), C.byref(o), _stream()),
+                  "qmlp_td_backward_opt")
             return
-        mcheck(mlib().evx_qmlp_td_backward_ss(C.byref(self.c), B, Q.data_ptr(), Qt.data_ptr(), act.data_ptr(),
-                                              rew.data_ptr(), done.data_ptr(), float(gamma), _p(weights),
-                                              loss.data_ptr(), _p(td_abs), x.data_ptr(), h1.data_ptr(), h2.data_ptr(),
-                                              float(drop_p), dz2.data_ptr(), dz1.data_ptr(), C.byref(g), _p(ss),
-                                              _stream()), "qmlp_td_backward_ss")
+        check(lib().evx_qmlp_td_backward_ss(C.byref(self.c), B, Q.data_ptr(), Qt.data_ptr(), act.data_ptr(),
+                                            rew.data_ptr(), done.data_ptr(), float(gamma), _p(weights),
+                                            loss.data_ptr(), _p(td_abs), x.data_ptr(), h1.data_ptr(), h2.data_ptr(),
+                                            float(drop_p), dz2.data_ptr(), dz1.data_ptr(), C.byref(g), _p(ss),
+                                            _stream()), "qmlp_td_backward_ss")
 
     def backward(self, B: int, dq: torch.Tensor, x: torch.Tensor, h1: torch.Tensor, h2: torch.Tensor, drop_p: float,
                  dz2: torch.Tensor, dz1: torch.Tensor, grads, zero=True, ss: Optional[torch.Tensor] = None):
@@ -457,14 +355,14 @@ class MLPFast:
                 raise ValueError(f"qmlp backward: {name} has {t.numel()} elements, needs {n}")
         g = self._grads(B, grads)
         if ss is not None:
-            _need("backward ss", ss, 1, int(mlib().evx_qmlp_norm_parts()))
-            mcheck(mlib().evx_qmlp_backward_ss(C.byref(self.c), B, dq.data_ptr(), x.data_ptr(), h1.data_ptr(),
-                                               h2.data_ptr(), float(drop_p), dz2.data_ptr(), dz1.data_ptr(), C.byref(g),
-                                               int(zero), ss.data_ptr(), _stream()), "qmlp_backward_ss")
+            _need("backward ss", ss, 1, int(lib().evx_qmlp_norm_parts()))
+            check(lib().evx_qmlp_backward_ss(C.byref(self.c), B, dq.data_ptr(), x.data_ptr(), h1.data_ptr(),
+                                             h2.data_ptr(), float(drop_p), dz2.data_ptr(), dz1.data_ptr(), C.byref(g),
+                                             int(zero), ss.data_ptr(), _stream()), "qmlp_backward_ss")
             return
-        mcheck(mlib().evx_qmlp_backward(C.byref(self.c), B, dq.data_ptr(), x.data_ptr(), h1.data_ptr(), h2.data_ptr(),
-                                        float(drop_p), dz2.data_ptr(), dz1.data_ptr(), C.byref(g), int(zero),
-                                        _stream()), "qmlp_backward")
+        check(lib().evx_qmlp_backward(C.byref(self.c), B, dq.data_ptr(), x.data_ptr(), h1.data_ptr(), h2.data_ptr(),
+                                      float(drop_p), dz2.data_ptr(), dz1.data_ptr(), C.byref(g), int(zero),
+                                      _stream()), "qmlp_backward")
 
 
 # ------------------------------------------------------------ host restatements

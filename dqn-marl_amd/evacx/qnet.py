@@ -21,79 +21,14 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from ._lib import (ACCUM, CONV_DW, CONV_DX, CONV_FWD, OUT_SPLIT, PREC, RELU, SPLIT_AB, check,  # noqa: F401
+                   evx_adam, evx_gemm_desc, lib)
 from .env import _stream
 from .qmlp import evx_td_opts, polyak_coeffs, td_opts, validate_td_options  # noqa: F401 (re-exported)
 
-PREC = {"f32": 0, "bf16": 1, "x3": 2}
-RELU, ACCUM, SPLIT_AB, OUT_SPLIT = 1, 2, 4, 8
 DROPOUT_P = 0.2
-
-
-class evx_gemm_desc(C.Structure):
-    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("precision", C.c_int32),
-                ("flags", C.c_int32), ("alpha", C.c_float),
-                ("A", C.c_void_p), ("sam", C.c_int64), ("sak", C.c_int64),
-                ("B", C.c_void_p), ("sbk", C.c_int64), ("sbn", C.c_int64),
-                ("C", C.c_void_p), ("ldc", C.c_int64), ("bias", C.c_void_p),
-                ("mask", C.c_void_p), ("ldm", C.c_int64), ("mask_scale", C.c_float),
-                ("gate", C.c_void_p), ("ldg", C.c_int64), ("ws", C.c_void_p), ("ws_elems", C.c_int64)]
-
-
-class evx_adam(C.Structure):
-    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
-                ("weight_decay", C.c_float), ("step", C.c_int64)]
-
-
-_q_inited = False
-
-
-def qlib():
-    global _q_inited
-    L = _lib.lib()
-    if not _q_inited:
-        L.evx_q_last_error.restype = C.c_char_p
-        L.evx_gemm.argtypes = [C.POINTER(evx_gemm_desc), C.c_void_p]
-        L.evx_gemm_ws_elems.argtypes = [C.POINTER(evx_gemm_desc)]
-        L.evx_gemm_ws_elems.restype = C.c_int64
-        L.evx_conv3x3_ws_elems.argtypes = [C.POINTER(evx_gemm_desc), C.c_int32, C.c_int32]
-        L.evx_conv3x3_ws_elems.restype = C.c_int64
-        L.evx_colsum.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                                 C.c_int32, C.c_void_p]
-        L.evx_td_loss_ws_floats.restype = C.c_int64
-        L.evx_td_loss_ws_floats.argtypes = [C.c_int32, C.c_int32]
-        L.evx_td_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
-                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        L.evx_td_loss_w.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_int64, C.c_void_p]
-        L.evx_td_loss_zero.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-        L.evx_td_loss_zero_g.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-        L.evx_td_loss_opt.argtypes = L.evx_td_loss_zero_g.argtypes[:-1] + [C.POINTER(evx_td_opts), C.c_void_p]
-        L.evx_polyak.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]
-        L.evx_sumsq_norm.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-        L.evx_clip_adam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                    C.c_float, C.POINTER(evx_adam), C.c_void_p]
-        L.evx_dropout_mask.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]
-        L.evx_act.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p,
-                              C.c_void_p]
-        L.evx_im2col3x3.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        L.evx_col2im3x3.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        L.evx_pix_nchw.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        L.evx_pix_split.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        L.evx_relu_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        L.evx_conv3x3_gemm.argtypes = [C.POINTER(evx_gemm_desc), C.c_int32, C.c_int32, C.c_void_p]
-        _q_inited = True
-    return L
-
-
-def qcheck(rc, what):
-    if rc != 0:
-        raise _lib.EvacxError(f"{what} failed ({rc}): {qlib().evx_q_last_error().decode()}")
+# the loader's and the check's earlier names here, kept for callers written against them
+qlib, qcheck = lib, check
 
 
 def _p(t):
@@ -102,7 +37,7 @@ def _p(t):
 
 def td_workspace(ws, B: int, nets: int, device, tag: str = "") -> torch.Tensor:
     """The TD loss's partials buffer (evx_td_loss_ws_floats) from a _Workspace pool."""
-    n = max(1, int(qlib().evx_td_loss_ws_floats(B, nets)))
+    n = max(1, int(lib().evx_td_loss_ws_floats(B, nets)))
     return ws.get(tag + "td_ws", (n,), torch.float32, device)
 
 
@@ -119,8 +54,8 @@ def _attach_ws(d, ws, tag, device, conv=None):
     key = (d.M, d.N, d.K, d.precision, d.flags, bool(d.bias), bool(d.mask), bool(d.gate), d.sbk, d.sbn, conv)
     need = _WS_NEED.get(key)
     if need is None:
-        need = _WS_NEED[key] = int(qlib().evx_conv3x3_ws_elems(C.byref(d), conv[0], conv[1]) if conv
-                                   else qlib().evx_gemm_ws_elems(C.byref(d)))
+        need = _WS_NEED[key] = int(lib().evx_conv3x3_ws_elems(C.byref(d), conv[0], conv[1]) if conv
+                                   else lib().evx_gemm_ws_elems(C.byref(d)))
     if need <= 0:
         return
     if isinstance(ws, torch.Tensor):
@@ -140,10 +75,7 @@ def gemm(M, N, K, A, sam, sak, B, sbk, sbn, Cm, ldc, precision="f32", bias=None,
                       alpha=alpha, A=_p(A), sam=sam, sak=sak, B=_p(B), sbk=sbk, sbn=sbn, C=_p(Cm), ldc=ldc,
                       bias=_p(bias), mask=_p(mask), ldm=ldm, mask_scale=mask_scale, gate=_p(gate), ldg=ldg)
     _attach_ws(d, ws, tag, Cm.device)
-    qcheck(qlib().evx_gemm(C.byref(d), _stream()), "evx_gemm")
-
-
-CONV_FWD, CONV_DX, CONV_DW = 1, 2, 3
+    check(lib().evx_gemm(C.byref(d), _stream()), "evx_gemm")
 
 
 def conv_gemm(mode, M, N, K, A, B, Cm, cs, sam=0, sak=0, sbk=0, sbn=0, bias=None, relu=False, gate=None,
@@ -155,11 +87,11 @@ def conv_gemm(mode, M, N, K, A, B, Cm, cs, sam=0, sak=0, sbk=0, sbn=0, bias=None
                       sam=sam, sak=sak, B=_p(B), sbk=sbk, sbn=sbn, C=_p(Cm), ldc=N, bias=_p(bias), mask=None,
                       ldm=0, mask_scale=1.0, gate=_p(gate), ldg=ldg)
     _attach_ws(d, ws, tag + f"cv{mode}_", Cm.device, conv=(mode, cs))
-    qcheck(qlib().evx_conv3x3_gemm(C.byref(d), mode, cs, _stream()), "evx_conv3x3_gemm")
+    check(lib().evx_conv3x3_gemm(C.byref(d), mode, cs, _stream()), "evx_conv3x3_gemm")
 
 
 def colsum(X, M, N, out, scratch):
-    qcheck(qlib().evx_colsum(_p(X), N, M, N, _p(out), 0, _p(scratch), scratch.numel(), _stream()), "evx_colsum")
+    check(lib().evx_colsum(_p(X), N, M, N, _p(out), 0, _p(scratch), scratch.numel(), _stream()), "evx_colsum")
 
 
 # ----------------------------------------------------------------------------
@@ -290,7 +222,7 @@ class QNet:
                 self.saved = dict(B=B, x=x, H1=H1, H2=H2, mask=mask)
             return Q
         ws, dev, P = self.ws, self.device, self.P
-        L = qlib()
+        L = lib()
         Mp = B * 121
         ins, cols, ys = [x], [], []
         cur, C_in = x, 6
@@ -310,7 +242,7 @@ class QNet:
                 cur, C_in = Y, cout
                 continue
             col = ws.get(tag + f"col{li}", (Mp, K9), torch.float32, dev)
-            qcheck(L.evx_im2col3x3(_p(cur), B, C_in, 1, _p(col), _stream()), "im2col")
+            check(L.evx_im2col3x3(_p(cur), B, C_in, 1, _p(col), _stream()), "im2col")
             Y = ws.get(tag + f"y{li}", (Mp, cout), torch.float32, dev)
             gemm(Mp, cout, K9, col, K9, 1, P[cname + ".weight"], 1, K9, Y, cout, self.prec, bias=P[cname + ".bias"],
                  relu=True, ws=self.ws, tag=tag)
@@ -324,18 +256,18 @@ class QNet:
             # transposing the activations (8192 rows: 507 MB, 0.57 ms).
             if split:
                 W1s = ws.get(tag + "w1s", (2 * self.hidden, 128 * 121), torch.int16, dev)
-                qcheck(L.evx_pix_split(_p(P["fc1.weight"]), self.hidden, 128, _p(W1s), _stream()), "pix_split")
+                check(L.evx_pix_split(_p(P["fc1.weight"]), self.hidden, 128, _p(W1s), _stream()), "pix_split")
                 _, _, Q = self._fc_forward(cur, B, 128 * 121, mask, tag, w1=W1s, split=True)
                 return Q
             W1p = ws.get(tag + "w1p", (self.hidden, 128 * 121), torch.float32, dev)
-            qcheck(L.evx_pix_nchw(_p(P["fc1.weight"]), self.hidden, 128, 0, _p(W1p), _stream()), "pix_nchw")
+            check(L.evx_pix_nchw(_p(P["fc1.weight"]), self.hidden, 128, 0, _p(W1p), _stream()), "pix_nchw")
             F = cur.view(B, 128 * 121)
             H1, H2, Q = self._fc_forward(F, B, 128 * 121, mask, tag, w1=W1p)
             if save:
                 self.saved = dict(B=B, x=F, H1=H1, H2=H2, mask=mask, cols=cols, ys=ys, w1p=W1p)
             return Q
         F = ws.get(tag + "flat", (B, 128 * 121), torch.float32, dev)
-        qcheck(L.evx_pix_nchw(_p(cur), B, 128, 1, _p(F), _stream()), "pix_nchw")  # torch reshape of NCHW
+        check(L.evx_pix_nchw(_p(cur), B, 128, 1, _p(F), _stream()), "pix_nchw")  # torch reshape of NCHW
         H1, H2, Q = self._fc_forward(F, B, 128 * 121, mask, tag)
         if save:
             self.saved = dict(B=B, x=F, H1=H1, H2=H2, mask=mask, cols=cols, ys=ys)
@@ -362,14 +294,14 @@ class QNet:
         gemm(B, H, H // 2, dZ2, H // 2, 1, P["fc2.weight"], H, 1, dZ1, H, pr, mask=mask, ldm=H,
              mask_scale=1.0 / (1.0 - DROPOUT_P), gate=H1, ldg=H, ws=self.ws, tag="bw_")
         # fc1
-        L = qlib()
+        L = lib()
         W1p = s.get("w1p")
         if W1p is None:
             gemm(H, K0, B, dZ1, 1, H, X, K0, 1, grads["fc1.weight"], K0, pr, ws=self.ws, tag="bw_")
         else:  # X is pixel-major: dW1 in that column order, then back to the reference's
             dW1p = ws.get("dw1p", (H, K0), torch.float32, dev)
             gemm(H, K0, B, dZ1, 1, H, X, K0, 1, dW1p, K0, pr, ws=self.ws, tag="bw_")
-            qcheck(L.evx_pix_nchw(_p(dW1p), H, 128, 1, _p(grads["fc1.weight"]), _stream()), "pix_nchw")
+            check(L.evx_pix_nchw(_p(dW1p), H, 128, 1, _p(grads["fc1.weight"]), _stream()), "pix_nchw")
         colsum(dZ1, B, H, grads["fc1.bias"], scratch)
         if self.kind == "mlp":
             return
@@ -380,7 +312,7 @@ class QNet:
         else:
             dF = ws.get("dflat", (B, K0), torch.float32, dev)
             gemm(B, K0, H, dZ1, H, 1, P["fc1.weight"], K0, 1, dF, K0, pr, gate=X, ldg=K0, ws=self.ws, tag="bw_")  # gate: relu(conv3) > 0
-            qcheck(L.evx_pix_nchw(_p(dF), B, 128, 0, _p(dY), _stream()), "pix_nchw")
+            check(L.evx_pix_nchw(_p(dF), B, 128, 0, _p(dY), _stream()), "pix_nchw")
         cols, ys = s["cols"], s["ys"]
         for li, (cname, cin, cout) in reversed(list(enumerate([("conv1", 6, 32), ("conv2", 32, 64),
                                                                 ("conv3", 64, 128)]))):
@@ -402,10 +334,10 @@ class QNet:
             dcol = ws.get(f"dcol{li}", (Mp, K9), torch.float32, dev)
             gemm(Mp, K9, cout, dY, cout, 1, P[cname + ".weight"], K9, 1, dcol, K9, pr, ws=self.ws, tag="bw_")
             dx = ws.get(f"dx{li}", (B, cin * 121), torch.float32, dev)
-            qcheck(L.evx_col2im3x3(_p(dcol), B, cin, _p(dx), _stream()), "col2im")
+            check(L.evx_col2im3x3(_p(dcol), B, cin, _p(dx), _stream()), "col2im")
             dYp = ws.get(f"dyp{li}", (Mp, cin), torch.float32, dev)
-            qcheck(L.evx_pix_nchw(_p(dx), B, cin, 0, _p(dYp), _stream()), "pix_nchw")
-            qcheck(L.evx_relu_grad(_p(dYp), _p(ys[li - 1]), dYp.numel(), _stream()), "relu_grad")
+            check(L.evx_pix_nchw(_p(dx), B, cin, 0, _p(dYp), _stream()), "pix_nchw")
+            check(L.evx_relu_grad(_p(dYp), _p(ys[li - 1]), dYp.numel(), _stream()), "relu_grad")
             dY = dYp
 
 
@@ -463,16 +395,15 @@ class Learner:
         # sumsq / clip_adam / pack3 launches -- tests compare the two)
         self.fused_opt = self.fast is not None and self.fast.x3
         if self.fused_opt:
-            from .qmlp import mlib
-            assert self.online.numel == int(mlib().evx_qmlp_nparams()), "MLP parameter count"
+            assert self.online.numel == int(lib().evx_qmlp_nparams()), "MLP parameter count"
         self._ss = torch.zeros(1024, dtype=torch.float32, device=self.device)
         self._ss_fresh = False
 
     # ------------------------------------------------------------ dropout
     def dropout_mask(self, B, tag="m"):
         m = self.net.ws.get("mask_" + tag, (B, self.hidden), torch.uint8, self.device)
-        qcheck(qlib().evx_dropout_mask(_p(m), m.numel(), DROPOUT_P, self.seed, self.rng_offset, _stream()),
-               "dropout_mask")
+        check(lib().evx_dropout_mask(_p(m), m.numel(), DROPOUT_P, self.seed, self.rng_offset, _stream()),
+              "dropout_mask")
         self.rng_offset += (m.numel() + 3) // 4
         return m
 
@@ -492,17 +423,17 @@ class Learner:
 
     def _td_loss(self, Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel, gamma_row=None):
         """The TD launch of the separate chain: today's entry with the options off."""
-        L = qlib()
+        L = lib()
         if gamma_row is not None and (gamma_row.dtype != torch.float32 or gamma_row.numel() < B):
             raise ValueError(f"gamma_row must be a float32 tensor of at least B = {B} elements")
         if sel is None and not self._delta and gamma_row is None:
-            qcheck(L.evx_td_loss_w(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, _p(weights),
-                                   _p(dQ), _p(self.loss), _p(td_abs), _p(tw), tw.numel(), _stream()), "td_loss")
+            check(L.evx_td_loss_w(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, _p(weights),
+                                  _p(dQ), _p(self.loss), _p(td_abs), _p(tw), tw.numel(), _stream()), "td_loss")
             return
         o = td_opts(sel, self._delta, gamma_row)
-        qcheck(L.evx_td_loss_opt(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, 1, _p(weights),
-                                 _p(dQ), _p(self.loss), _p(td_abs), None, 0, _p(tw), tw.numel(), C.byref(o),
-                                 _stream()), "td_loss_opt")
+        check(L.evx_td_loss_opt(_p(Q), _p(Qt), self.actions, _p(a), _p(r), _p(done), self.gamma, B, 1, _p(weights),
+                                _p(dQ), _p(self.loss), _p(td_abs), None, 0, _p(tw), tw.numel(), C.byref(o),
+                                _stream()), "td_loss_opt")
 
     def learn(self, s, a, r, done, s2, mask_online=None, mask_target=None, weights=None, td_abs=None,
               mask_select=None, gamma_row=None):
@@ -520,7 +451,7 @@ class Learner:
         if self.double_q:  # the online net's greedy action at s' (train mode, as every forward of learn)
             Qs = self.q_values(s2, train=True, mask=mask_select, target=False, tag="sel")
             sel = self.net.ws.get("sel", (B,), torch.int32, self.device)
-            qcheck(qlib().evx_act(_p(Qs), B, self.actions, 0.0, 0, 0, _p(sel), _stream()), "act (selection)")
+            check(lib().evx_act(_p(Qs), B, self.actions, 0.0, 0, 0, _p(sel), _stream()), "act (selection)")
             self.last_sel = sel
         Q = self.net.forward(s, mask_online, save=True)
         Qt = self.tnet.forward(s2, mask_target, save=False, tag="t_")
@@ -599,7 +530,7 @@ class Learner:
         return self.loss
 
     def step_optimizer(self):
-        L = qlib()
+        L = lib()
         n = self.online.numel
         if self.fused_opt:  # clip + Adam + x3 repack in one launch from the norm partials
             if not self._ss_fresh:
@@ -611,14 +542,14 @@ class Learner:
             self.fast.adam_step(self.online.flat, self.grads.flat, self.m, self.v, float(self.max_norm or 0.0), h,
                                 self._ss, self.norm)
             return
-        qcheck(L.evx_sumsq_norm(_p(self.grads.flat), n, _p(self.scratch), self.scratch.numel(), _p(self.norm),
-                                _stream()), "sumsq")
+        check(L.evx_sumsq_norm(_p(self.grads.flat), n, _p(self.scratch), self.scratch.numel(), _p(self.norm),
+                               _stream()), "sumsq")
         self.adam_step += 1
         h = evx_adam(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=0.0,
                      step=self.adam_step)
-        qcheck(L.evx_clip_adam(_p(self.online.flat), _p(self.grads.flat), _p(self.m), _p(self.v), n,
-                               _p(self.norm) if self.max_norm else None, float(self.max_norm or 0.0), C.byref(h),
-                               _stream()), "clip_adam")
+        check(L.evx_clip_adam(_p(self.online.flat), _p(self.grads.flat), _p(self.m), _p(self.v), n,
+                              _p(self.norm) if self.max_norm else None, float(self.max_norm or 0.0), C.byref(h),
+                              _stream()), "clip_adam")
         if self.fast is not None:
             self.fast.repack()  # bf16 copies follow the fp32 master parameters
 
@@ -644,8 +575,8 @@ class Learner:
             self.fast_t.polyak_step(self.online.flat, self.target.flat, self.target_tau)
             return
         t, omt = polyak_coeffs(self.target_tau)
-        qcheck(qlib().evx_polyak(_p(self.online.flat), _p(self.target.flat), self.target.numel, t, omt, _stream()),
-               "polyak")
+        check(lib().evx_polyak(_p(self.online.flat), _p(self.target.flat), self.target.numel, t, omt, _stream()),
+              "polyak")
         if self.fast_t is not None:
             self.fast_t.repack()
 

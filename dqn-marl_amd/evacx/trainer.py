@@ -26,11 +26,10 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import evx_replay
-from .env import OBS_WORDS, DeviceLayout, VecEnv, _ptr, _stream
+from ._lib import NSTEP_MAX, OBS_WORDS, check, evx_replay, lib
+from .env import DeviceLayout, VecEnv, _ptr, _stream
 from .qmlp import act_ws_ints
-from .qnet import DROPOUT_P, Learner, qcheck, qlib, validate_td_options
+from .qnet import DROPOUT_P, Learner, validate_td_options
 
 
 class Replay:
@@ -51,18 +50,13 @@ class Replay:
 
     def push(self, s, s2, a, r_env, done_env, n, agents_per_env, s2_term=None):
         """s2_term: terminal observations of auto-reset envs (taken where done_env)."""
-        L = _lib.lib()
         if s2_term is None:
-            L.evx_replay_push.argtypes = [C.POINTER(evx_replay), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]
-            qcheck(L.evx_replay_push(C.byref(self.c), s.data_ptr(), s2.data_ptr(), a.data_ptr(), r_env.data_ptr(),
-                                     done_env.data_ptr(), n, agents_per_env, self.pos, _stream()), "replay_push")
+            check(lib().evx_replay_push(C.byref(self.c), s.data_ptr(), s2.data_ptr(), a.data_ptr(), r_env.data_ptr(),
+                                        done_env.data_ptr(), n, agents_per_env, self.pos, _stream()), "replay_push")
         else:
-            L.evx_replay_push_term.argtypes = [C.POINTER(evx_replay)] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32,
-                                                                                          C.c_int64, C.c_void_p]
-            qcheck(L.evx_replay_push_term(C.byref(self.c), s.data_ptr(), s2.data_ptr(), s2_term.data_ptr(),
-                                          a.data_ptr(), r_env.data_ptr(), done_env.data_ptr(), n, agents_per_env,
-                                          self.pos, _stream()), "replay_push_term")
+            check(lib().evx_replay_push_term(C.byref(self.c), s.data_ptr(), s2.data_ptr(), s2_term.data_ptr(),
+                                             a.data_ptr(), r_env.data_ptr(), done_env.data_ptr(), n, agents_per_env,
+                                             self.pos, _stream()), "replay_push_term")
         self.pos = (self.pos + n) % self.capacity
         self.size = min(self.capacity, self.size + n)
 
@@ -73,7 +67,7 @@ class Replay:
         size = min(self.capacity, self.size + n)
         B, seed, offset, out = sample if sample is not None else (0, 0, 0, None)
         o = (lambda k: out[k].data_ptr()) if out is not None else (lambda k: None)
-        qcheck(_lib.lib().evx_env_orders_push_sample(
+        check(lib().evx_env_orders_push_sample(
             C.byref(env.lay.c), C.byref(env.c), _ptr(perm), C.byref(self.c), s.data_ptr(), s2.data_ptr(),
             _ptr(s2_term), a.data_ptr(), r_env.data_ptr(), done_env.data_ptr(), n, agents_per_env, self.pos,
             B, size, seed, offset, o("s"), o("s2"), o("a"), o("r"), o("done"), _stream()), "env_orders_push_sample")
@@ -87,23 +81,15 @@ class Replay:
         return (self.pos - count) % self.capacity, count
 
     def sample_window(self, base, count, B, seed, offset, out):
-        L = _lib.lib()
-        L.evx_replay_sample_window.argtypes = [C.POINTER(evx_replay), C.c_int64, C.c_int64, C.c_int32, C.c_uint64,
-                                               C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p]
-        qcheck(L.evx_replay_sample_window(C.byref(self.c), base, count, B, seed, offset, out["s"].data_ptr(),
-                                          out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
-                                          out["done"].data_ptr(), _ptr(out.get("idx")), _stream()),
-               "replay_sample_window")
+        check(lib().evx_replay_sample_window(C.byref(self.c), base, count, B, seed, offset, out["s"].data_ptr(),
+                                             out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
+                                             out["done"].data_ptr(), _ptr(out.get("idx")), _stream()),
+              "replay_sample_window")
 
     def sample(self, B, seed, offset, out):
-        L = _lib.lib()
-        L.evx_replay_sample.argtypes = [C.POINTER(evx_replay), C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p]
-        qcheck(L.evx_replay_sample(C.byref(self.c), self.size, B, seed, offset, out["s"].data_ptr(),
-                                   out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
-                                   out["done"].data_ptr(), _ptr(out.get("idx")), _stream()), "replay_sample")
+        check(lib().evx_replay_sample(C.byref(self.c), self.size, B, seed, offset, out["s"].data_ptr(),
+                                      out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
+                                      out["done"].data_ptr(), _ptr(out.get("idx")), _stream()), "replay_sample")
 
     def live_range(self):
         """(base, count) of the whole ring in push order, oldest first."""
@@ -124,10 +110,10 @@ class Replay:
         nlen = out.get("nlen")
         if nlen is not None and nlen.numel() < B:
             raise ValueError(f"nstep: out['nlen'] holds {nlen.numel()} rows, B = {B}")
-        qcheck(_lib.lib().evx_replay_nstep(C.byref(self.c), idx.data_ptr(), B, base, count, stride, n_step,
-                                           float(gamma), out["s2"].data_ptr(), out["r"].data_ptr(),
-                                           out["done"].data_ptr(), out["gamma_row"].data_ptr(), _ptr(nlen),
-                                           _stream()), "replay_nstep")
+        check(lib().evx_replay_nstep(C.byref(self.c), idx.data_ptr(), B, base, count, stride, n_step,
+                                     float(gamma), out["s2"].data_ptr(), out["r"].data_ptr(),
+                                     out["done"].data_ptr(), out["gamma_row"].data_ptr(), _ptr(nlen),
+                                     _stream()), "replay_nstep")
 
 
 class _Group:
@@ -195,8 +181,8 @@ class VecTrainer:
         schedules. nets="shared", groups=1 and no step(extra_reset=...). 1: nothing of it runs."""
         validate_td_options(loss, huber_delta, target_tau)
         self.target_tau = float(target_tau)
-        if not (isinstance(n_step, int) and 1 <= n_step <= _lib.NSTEP_MAX):
-            raise ValueError(f"n_step must be an integer in [1, {_lib.NSTEP_MAX}], not {n_step!r}")
+        if not (isinstance(n_step, int) and 1 <= n_step <= NSTEP_MAX):
+            raise ValueError(f"n_step must be an integer in [1, {NSTEP_MAX}], not {n_step!r}")
         if n_step > 1:
             if nets != "shared":
                 raise ValueError(f"n_step > 1 needs nets='shared': the samplers of nets={nets!r} return no slot "
@@ -376,8 +362,8 @@ class VecTrainer:
         x = grp.env.expand_obs(torch.float32)  # [E/G, R, 11, 11, 6]
         # per-group scratch: the groups' acts run concurrently on their own streams
         Q = self.learner.q_values(x.view(grp.n, 11, 11, 6), train=True, tag=f"act{grp.g}" if grp.g else "act")
-        qcheck(qlib().evx_act(Q.data_ptr(), grp.n, self.learner.actions, float(self.epsilon), self.act_seed, off,
-                              grp.actions.data_ptr(), _stream()), "act")
+        check(lib().evx_act(Q.data_ptr(), grp.n, self.learner.actions, float(self.epsilon), self.act_seed, off,
+                            grp.actions.data_ptr(), _stream()), "act")
 
     def _act_stream(self):
         """A fresh dropout mask stream for this step's act: every group's act draws from it (rows keyed
@@ -402,15 +388,11 @@ class VecTrainer:
             Bn = self.batch // self.R
             if self.replay.size < self.batch:
                 return None
-            L = _lib.lib()
-            L.evx_replay_sample_agents.argtypes = [C.POINTER(evx_replay), C.c_int64, C.c_int32, C.c_int32, C.c_uint64,
-                                                   C.c_uint64] + [C.c_void_p] * 6
             sp = self.samp
-            fn = L.evx_replay_sample_joint if self.qmix is not None else L.evx_replay_sample_agents
-            fn.argtypes = L.evx_replay_sample_agents.argtypes
-            qcheck(fn(C.byref(self.replay.c), self.replay.size, Bn, self.R, self.seed + 1, self.learn_steps * self.batch,
-                      sp["s"].data_ptr(), sp["s2"].data_ptr(), sp["a"].data_ptr(), sp["r"].data_ptr(),
-                      sp["done"].data_ptr(), _stream()), "replay_sample_agents/joint")
+            fn = lib().evx_replay_sample_joint if self.qmix is not None else lib().evx_replay_sample_agents
+            check(fn(C.byref(self.replay.c), self.replay.size, Bn, self.R, self.seed + 1, self.learn_steps * self.batch,
+                     sp["s"].data_ptr(), sp["s2"].data_ptr(), sp["a"].data_ptr(), sp["r"].data_ptr(),
+                     sp["done"].data_ptr(), _stream()), "replay_sample_agents/joint")
             if self.qmix is not None:  # agent 0's rows carry the team reward / done of the sampled env-steps
                 loss = self.qmix(self.lay.c, sp["s"], sp["a"], sp["r"], sp["done"], sp["s2"], Bn)
             else:

@@ -7,7 +7,8 @@
  * dqn-marl_amd/Louvre_Evacuation binds them through ctypes.
  *
  * Conventions
- *  - every call returns 0 or a negative errno-like code; evx_last_error() has text;
+ *  - every call returns 0 or a negative errno-like code; evx_last_error() has text: the message
+ *    of the calling thread's last failed call (the evx_*_last_error getters return the same buffer);
  *  - every buffer is caller-owned DEVICE memory unless the name says _host;
  *  - no hidden allocations, no internal threads, no host syncs; `stream` is a
  *    hipStream_t passed as void* (0 = the null stream);

@@ -1,25 +1,187 @@
-"""The C-ABI library loads on a CPU-only host and exports every symbol include/evacx.h declares."""
+"""The C-ABI library loads on a CPU-only host, and the one Python description of include/evacx.h
+(evacx._lib: the signature table, the structure mirrors, the mirrored constants) agrees with the header."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
+
+import pytest
 
 from golden_util import ROOT
 
+HEADER = os.path.join(ROOT, "include", "evacx.h")
+
+
+def header_text():
+    """include/evacx.h without its comments."""
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
 
 def declared_symbols():
-    src = open(os.path.join(ROOT, "include", "evacx.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(evx_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(evx_[a-z0-9_]+)\s*\(", header_text())))
 
 
-def test_library_exports_header_symbols():
+# kind of a return or parameter type -> the ctypes types that may stand for it
+RETURN_KINDS = {"int": (ctypes.c_int,), "int32_t": (ctypes.c_int32,), "int64_t": (ctypes.c_int64,),
+                "const char *": (ctypes.c_char_p,)}
+SCALAR_KINDS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+                "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def header_prototypes():
+    """symbol -> (return type, [parameter kind]) for every prototype: a SCALAR_KINDS key, or
+    "pointer:<pointee type>" ("pointer:" for a pointer to pointers); any other parameter or return
+    type raises."""
+    text = header_text()
+    protos = {}
+    for ret, name, params in re.findall(r"([\w ]+?[ *])\s*\b(evx_\w+)\s*\(([^)]*)\)\s*;", text):
+        ret = " ".join(ret.split())
+        assert ret in RETURN_KINDS, f"{name}: return type {ret!r}"
+        kinds = []
+        for p in (" ".join(q.split()) for q in params.split(",")):
+            if p == "void" and "," not in params:
+                continue
+            if "*" in p:
+                m = re.fullmatch(r"(?:const )?(\w+) \*(?:const )?\w+", p)
+                kinds.append("pointer:" + (m.group(1) if m else ""))
+                continue
+            m = re.fullmatch(r"(\w+) \w+", p)
+            assert m and m.group(1) in SCALAR_KINDS, f"{name}: parameter {p!r}"
+            kinds.append(m.group(1))
+        assert name not in protos, name
+        protos[name] = (ret, kinds)
+    return protos
+
+
+def _is_pointer(t):
+    return t is ctypes.c_void_p or isinstance(t, type(ctypes.POINTER(ctypes.c_int)))
+
+
+def test_signature_table_is_the_header():
     from evacx import _lib
     L = _lib.lib()
     syms = declared_symbols()
-    assert len(syms) >= 7
+    protos = header_prototypes()
+    structs = [getattr(_lib, n) for n in STRUCTS]
+    assert sorted(protos) == syms
+    assert sorted(_lib.SIGNATURES) == syms
     for s in syms:
         assert hasattr(L, s), s
-    assert set(_lib.EXPORTS) <= set(syms)
+        ret, kinds = protos[s]
+        restype, argtypes = _lib.SIGNATURES[s]
+        assert restype in RETURN_KINDS[ret], (s, ret, restype)
+        assert len(argtypes) == len(kinds), (s, len(kinds), len(argtypes))
+        for i, (k, t) in enumerate(zip(kinds, argtypes)):
+            if not k.startswith("pointer:"):
+                assert t is SCALAR_KINDS[k], (s, i, k, t)
+            elif k[8:] in STRUCTS:  # a mirrored structure: typed, and as that structure
+                assert t is ctypes.POINTER(getattr(_lib, k[8:])), (s, i, k, t)
+            else:
+                assert _is_pointer(t) and getattr(t, "_type_", None) not in structs, (s, i, k, t)
+        fn = getattr(L, s)  # lib() bound what the table says
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), s
+
+
+def test_earlier_loader_names_are_the_one_loader():
+    """qlib / qcheck, mlib, elib and hlib are what earlier callers import: plain names of lib / check."""
+    from evacx import _lib, episodes, health, qmlp, qnet
+    assert qnet.qlib is _lib.lib and qmlp.mlib is _lib.lib and episodes.elib is _lib.lib and health.hlib is _lib.lib
+    assert qnet.qcheck is _lib.check
+
+
+STRUCTS = ["evx_layout", "evx_state", "evx_replay", "evx_step_out", "evx_qmlp_params", "evx_qmlp_dropout",
+           "evx_qmlp_grads", "evx_qmlp_fwd_out", "evx_td_opts", "evx_gemm_desc", "evx_adam", "evx_prio",
+           "evx_episodes", "evx_health"]
+
+
+def _mirrored_constants(_lib):
+    """header #define or C expression -> the Python mirror"""
+    c = {"EVX_FEAT_PAD": _lib.FEAT_PAD, "EVX_NSTEP_MAX": _lib.NSTEP_MAX,
+         "EVX_EPISODE_REDUCE_SPAN": _lib.EPISODE_REDUCE_SPAN, "EVX_HEALTH_MAX_P": _lib.HEALTH_MAX_P,
+         "EVX_PREC_F32": _lib.PREC["f32"], "EVX_PREC_BF16": _lib.PREC["bf16"], "EVX_PREC_X3": _lib.PREC["x3"],
+         "EVX_GEMM_RELU": _lib.RELU, "EVX_GEMM_ACCUM": _lib.ACCUM, "EVX_GEMM_SPLIT_AB": _lib.SPLIT_AB,
+         "EVX_GEMM_OUT_SPLIT": _lib.OUT_SPLIT, "EVX_CONV_FWD": _lib.CONV_FWD, "EVX_CONV_DX": _lib.CONV_DX,
+         "EVX_CONV_DW": _lib.CONV_DW,
+         "sizeof(evx_obs)": 4 * _lib.OBS_WORDS, "sizeof(evx_episode_row)": 8 * _lib.EPISODE_ROW_WORDS,
+         "sizeof(evx_health_row)": 8 * _lib.HEALTH_ROW_WORDS}
+    assert len(_lib.PREC) == 3
+    return c
+
+
+def test_structure_layouts_and_constants_match_the_header(tmp_path):
+    """A C program that includes the header prints sizeof / offsetof of every mirrored structure and
+    field and every mirrored constant; a field the header lacks does not compile."""
+    from evacx import _lib
+    cc = shutil.which("cc") or shutil.which("clang") or shutil.which("clang", path="/opt/rocm/llvm/bin")
+    assert cc, "no C compiler (cc, clang) to check the structure layouts with"
+    want = {}
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "evacx.h"', "int main(void) {"]
+
+    def emit(key, expr, value):
+        want[key] = value
+        lines.append(f'    printf("{key} %lld\\n", (long long)({expr}));')
+    for name in STRUCTS:
+        S = getattr(_lib, name)
+        emit(f"sizeof({name})", f"sizeof({name})", ctypes.sizeof(S))
+        for field, _ in S._fields_:
+            emit(f"{name}.{field}", f"offsetof({name}, {field})", getattr(S, field).offset)
+    for expr, value in _mirrored_constants(_lib).items():
+        emit(expr, expr, value)
+    lines += ["    return 0;", "}"]
+    src, exe = tmp_path / "abi_layout.c", tmp_path / "abi_layout"
+    src.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, check=True).stdout
+    got = {k: int(v) for k, v in (ln.rsplit(" ", 1) for ln in out.splitlines())}
+    assert len(STRUCTS) == 14 and set(got) == set(want)
+    assert {k: (got[k], want[k]) for k in want if got[k] != want[k]} == {}
+
+
+def _step_without_tables(L):
+    from evacx import _lib
+    return L.evx_env_step(ctypes.byref(_lib.evx_layout(L=36, W=30, P=150, R=1)), None, None, None, None)
+
+
+def _null_layout_push(L):
+    return L.evx_env_orders_push_sample(None, None, None, None, None, None, None, None, None, None, 0, 0, 0, 0, 0, 0, 0,
+                                        None, None, None, None, None, None)
+
+
+# family -> (a call that fails validation before any device is touched, fragment of its message, the family's getter)
+ERROR_CASES = {
+    "env": (_step_without_tables, b"missing table", "evx_last_error"),
+    "q": (lambda L: L.evx_polyak(None, None, 4, .5, .5, None), b"polyak: NULL", "evx_q_last_error"),
+    "qmlp": (lambda L: L.evx_qmlp_polyak_pack3(None, None, .5, .5, *[None] * 10), b"qmlp_polyak_pack3: NULL",
+             "evx_qmlp_last_error"),
+    "qmix": (lambda L: L.evx_qmix_loss(None, None, 5, None, None, None, .99, 1, 0, None, None, None, None, None, None,
+                                       None, 0, None), b"1..16 agents", "evx_qmix_last_error"),
+    "prio": (lambda L: L.evx_prio_init(None, None), b"prio: NULL tree", "evx_prio_last_error"),
+    "floor": (lambda L: L.evx_floor_field(1, 2, 2, *[None] * 6), b"at least 3 x 3", "evx_floor_last_error"),
+    "episode": (lambda L: L.evx_episode_init(None, None), b"NULL episode descriptor", "evx_episode_last_error"),
+    "health": (lambda L: L.evx_health_init(None, None), b"NULL health descriptor", "evx_health_last_error"),
+}
+
+
+@pytest.mark.parametrize("family", sorted(ERROR_CASES))
+def test_every_family_reports_through_the_one_error_text(family):
+    from evacx import _lib
+    L = _lib.lib()
+    assert _null_layout_push(L) == -22 and b"layout is NULL" in L.evx_last_error()  # another family's text first
+    call, fragment, getter = ERROR_CASES[family]
+    assert call(L) == -22
+    text = L.evx_last_error()
+    assert fragment in text, text
+    assert getattr(L, getter)() == text
+
+
+def test_check_carries_the_message_of_a_failed_push_orders_entry():
+    """Replay.push_orders' entry point writes the env family's text; check() shows it."""
+    from evacx import _lib
+    with pytest.raises(_lib.EvacxError, match=r"env_orders_push_sample failed \(-22\): layout is NULL"):
+        _lib.check(_null_layout_push(_lib.lib()), "env_orders_push_sample")
 
 
 def test_host_seeding_matches_reference_vectors():

@@ -129,17 +129,17 @@ def test_conv_act_tags_on_two_streams_match_serial():
 def test_pix_nchw_any_channel_count(C):
     _need_gpu()
     import ctypes as Ct
-    from evacx.qnet import qcheck, qlib
+    from evacx._lib import check, lib
     B = 5
     pix = torch.randn(B, 121, C, device="cuda")
     out = torch.empty(B, C, 121, device="cuda")
-    qcheck(qlib().evx_pix_nchw(pix.data_ptr(), B, C, 1, out.data_ptr(), None), "pix_nchw")
+    check(lib().evx_pix_nchw(pix.data_ptr(), B, C, 1, out.data_ptr(), None), "pix_nchw")
     back = torch.empty_like(pix)
-    qcheck(qlib().evx_pix_nchw(out.data_ptr(), B, C, 0, back.data_ptr(), None), "pix_nchw")
+    check(lib().evx_pix_nchw(out.data_ptr(), B, C, 0, back.data_ptr(), None), "pix_nchw")
     torch.cuda.synchronize()
     assert torch.equal(out, pix.permute(0, 2, 1))
     assert torch.equal(back, pix)
-    _ = Ct  # ctypes loaded by qlib
+    _ = Ct  # ctypes loaded by lib
 
 
 def test_trainer_exact_precision_runs_exact_gemms():

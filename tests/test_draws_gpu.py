@@ -24,13 +24,13 @@ def _need_gpu():
 
 def test_evx_act_matches_restatement():
     _need_gpu()
-    from evacx.qnet import qcheck, qlib
+    from evacx._lib import check, lib
     g = torch.Generator().manual_seed(1)
     Q = torch.randn(100003, 5, generator=g)
     Q[:100, :] = 1.0  # ties: first maximum
     out = torch.empty(Q.shape[0], dtype=torch.int32, device="cuda")
     for eps, seed, off in [(0.0, 3, 0), (0.3, 5, 12345), (1.0, 9, 2**40 + 7)]:
-        qcheck(qlib().evx_act(Q.cuda().data_ptr(), Q.shape[0], 5, eps, seed, off, out.data_ptr(), 0), "act")
+        check(lib().evx_act(Q.cuda().data_ptr(), Q.shape[0], 5, eps, seed, off, out.data_ptr(), 0), "act")
         torch.cuda.synchronize()
         assert np.array_equal(out.cpu().numpy(), orc.epsilon_greedy(Q.numpy(), eps, seed, off)), (eps, seed)
 
@@ -58,7 +58,7 @@ def test_fused_act_epsilon_matches_restatement(precision):
 def test_replay_sampling_matches_restatement(window):
     _need_gpu()
     from evacx.env import OBS_WORDS
-    from evacx.qnet import qcheck
+    from evacx._lib import check
     from evacx.trainer import Replay
     import ctypes as C
     from evacx import _lib
@@ -80,17 +80,14 @@ def test_replay_sampling_matches_restatement(window):
     L = _lib.lib()
     if window is None:
         base, size = 0, cap
-        L.evx_replay_sample.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 7
-        qcheck(L.evx_replay_sample(C.byref(rp.c), cap, B, 17, 4096, out["s"].data_ptr(), out["s2"].data_ptr(),
-                                   out["a"].data_ptr(), out["r"].data_ptr(), out["done"].data_ptr(), idx.data_ptr(),
-                                   None), "sample")
+        check(L.evx_replay_sample(C.byref(rp.c), cap, B, 17, 4096, out["s"].data_ptr(), out["s2"].data_ptr(),
+                                  out["a"].data_ptr(), out["r"].data_ptr(), out["done"].data_ptr(), idx.data_ptr(),
+                                  None), "sample")
     else:
         base, size = window
-        L.evx_replay_sample_window.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64,
-                                               C.c_uint64] + [C.c_void_p] * 7
-        qcheck(L.evx_replay_sample_window(C.byref(rp.c), base, size, B, 17, 4096, out["s"].data_ptr(),
-                                          out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
-                                          out["done"].data_ptr(), idx.data_ptr(), None), "sample_window")
+        check(L.evx_replay_sample_window(C.byref(rp.c), base, size, B, 17, 4096, out["s"].data_ptr(),
+                                         out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
+                                         out["done"].data_ptr(), idx.data_ptr(), None), "sample_window")
     torch.cuda.synchronize()
     ref = orc.replay_indices(base, size, cap, B, 17, 4096)
     assert np.array_equal(idx.cpu().numpy(), ref)
@@ -110,7 +107,7 @@ def test_per_agent_replay_sampling_matches_restatement():
     sampler's restated draws (the permutation keyed by stream g) over its own slots (== g mod nets)."""
     _need_gpu()
     from evacx.env import OBS_WORDS
-    from evacx.qnet import qcheck
+    from evacx._lib import check
     from evacx.trainer import Replay
     import ctypes as C
     from evacx import _lib
@@ -123,11 +120,9 @@ def test_per_agent_replay_sampling_matches_restatement():
                a=torch.empty(nets * B, dtype=torch.int32, device="cuda"), r=torch.empty(nets * B, device="cuda"),
                done=torch.empty(nets * B, dtype=torch.uint8, device="cuda"))
     L = _lib.lib()
-    L.evx_replay_sample_agents.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint64,
-                                           C.c_uint64] + [C.c_void_p] * 6
-    qcheck(L.evx_replay_sample_agents(C.byref(rp.c), size, B, nets, 17, 4096, out["s"].data_ptr(), out["s2"].data_ptr(),
-                                      out["a"].data_ptr(), out["r"].data_ptr(), out["done"].data_ptr(), None),
-           "sample_agents")
+    check(L.evx_replay_sample_agents(C.byref(rp.c), size, B, nets, 17, 4096, out["s"].data_ptr(), out["s2"].data_ptr(),
+                                     out["a"].data_ptr(), out["r"].data_ptr(), out["done"].data_ptr(), None),
+          "sample_agents")
     torch.cuda.synchronize()
     a = out["a"].cpu().numpy().reshape(nets, B)
     for g in range(nets):
@@ -136,10 +131,9 @@ def test_per_agent_replay_sampling_matches_restatement():
     assert torch.equal(out["s"].view(nets * B, OBS_WORDS), rp.s.view(cap, OBS_WORDS)[out["a"].long()])
     assert a.max() < size
     # joint draws (QMIX's memory of env-steps): draw i picks the same env-step for every agent
-    L.evx_replay_sample_joint.argtypes = L.evx_replay_sample_agents.argtypes
-    qcheck(L.evx_replay_sample_joint(C.byref(rp.c), size, B, nets, 17, 4096, out["s"].data_ptr(), out["s2"].data_ptr(),
-                                     out["a"].data_ptr(), out["r"].data_ptr(), out["done"].data_ptr(), None),
-           "sample_joint")
+    check(L.evx_replay_sample_joint(C.byref(rp.c), size, B, nets, 17, 4096, out["s"].data_ptr(), out["s2"].data_ptr(),
+                                    out["a"].data_ptr(), out["r"].data_ptr(), out["done"].data_ptr(), None),
+          "sample_joint")
     torch.cuda.synchronize()
     aj = out["a"].cpu().numpy().reshape(nets, B)
     step = orc.replay_indices(0, size // nets, 1 << 40, B, 17, 4096)

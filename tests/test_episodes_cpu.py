@@ -6,9 +6,9 @@ import pytest
 import torch
 
 
-def _elib():
-    from evacx import episodes
-    return episodes.elib()
+def _loaded():
+    from evacx import _lib
+    return _lib.lib()
 
 
 def _host_descriptor(E=4, leave_out=None):
@@ -27,7 +27,7 @@ def _host_descriptor(E=4, leave_out=None):
 
 
 def test_update_refuses_null_buffers():
-    L = _elib()
+    L = _loaded()
     assert L.evx_episode_update(None, None, None, None, 0, None) < 0
     assert b"NULL episode descriptor" in L.evx_episode_last_error()
     d, keep = _host_descriptor(leave_out="w_ret2")
@@ -45,7 +45,7 @@ def test_update_refuses_null_buffers():
 
 
 def test_discard_and_init_refuse_null_buffers():
-    L = _elib()
+    L = _loaded()
     assert L.evx_episode_discard(None, None, None) < 0
     assert b"episode_discard" in L.evx_episode_last_error()
     d, keep = _host_descriptor(leave_out="len")
@@ -56,7 +56,7 @@ def test_discard_and_init_refuse_null_buffers():
 
 
 def test_reduce_refuses_null_buffers_and_bad_layout_counts():
-    L = _elib()
+    L = _loaded()
     assert L.evx_episode_reduce(None, None, 1, 0, None, 0, None) < 0
     assert b"episode_reduce" in L.evx_episode_last_error()
     d, keep = _host_descriptor(leave_out="n_total")

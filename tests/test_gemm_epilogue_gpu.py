@@ -41,12 +41,13 @@ def test_split_k_epilogue_matches_torch(M, N, K, flags):
     bias = (torch.rand(N, device="cuda", generator=g) - 0.5) if "bias" in flags else None
     mask = (torch.rand(M, N, device="cuda", generator=g) < 0.8).to(torch.uint8) if "mask" in flags else None
     gate = (torch.rand(M, N, device="cuda", generator=g) - 0.3) if "gate" in flags else None
-    from evacx.qnet import _Workspace, evx_gemm_desc, qlib
+    from evacx._lib import lib
+    from evacx.qnet import _Workspace, evx_gemm_desc
     import ctypes as C_
     d = evx_gemm_desc(M=M, N=N, K=K, precision=2, flags=(1 if "relu" in flags else 0) | (2 if "accum" in flags else 0),
                       bias=1 if bias is not None else None, mask=1 if mask is not None else None,
                       gate=1 if gate is not None else None)
-    need = int(qlib().evx_gemm_ws_elems(C_.byref(d)))
+    need = int(lib().evx_gemm_ws_elems(C_.byref(d)))
     assert need >= 2 * M * N, need  # these shapes split
     C0 = torch.rand(M, N, device="cuda", generator=g) if "accum" in flags else None
     outs = []

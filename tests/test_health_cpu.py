@@ -40,7 +40,7 @@ def test_library_exports_the_health_entries():
     names = ["evx_health_init", "evx_health_update", "evx_health_reduce", "evx_health_last_error"]
     for s in names:
         assert hasattr(L, s), s
-        assert s in _lib.EXPORTS, s
+        assert s in _lib.SIGNATURES, s
 
 
 def _host_descriptor(E=4, leave_out=None):
@@ -59,8 +59,8 @@ def _host_descriptor(E=4, leave_out=None):
 
 
 def test_entries_refuse_null_pointers_and_sizes_out_of_range():
-    from evacx import health
-    L = health.hlib()
+    from evacx import _lib
+    L = _lib.lib()
     err = L.evx_health_last_error
     pk, hl, dn = (ctypes.c_int64 * 64)(), (ctypes.c_int64 * 64)(), (ctypes.c_int64 * 8)()
     assert L.evx_health_update(None, pk, hl, 4, dn, 0, None) == -22

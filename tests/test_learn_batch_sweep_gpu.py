@@ -125,8 +125,8 @@ def test_learn_step_keeps_to_its_rows(B):
     torch.cuda.synchronize()
     for k, (_, tail, want) in bufs.items():
         assert torch.equal(tail, want), f"B={B}: {k} written past its {B} rows"
-    from evacx.qmlp import mlib
-    norm = float(lr._ss[:int(mlib().evx_qmlp_norm_parts())].double().sum().sqrt())
+    from evacx._lib import lib
+    norm = float(lr._ss[:int(lib().evx_qmlp_norm_parts())].double().sum().sqrt())
     g1, g2 = lu.device_gates(t["h1"], t["h2"], B)
     bt.td_abs = t["td_abs"][:B]
     ref = lu.float64_reference(env, lr.online.state_dict(), lr.target.state_dict(), bt, g1, g2)

@@ -135,9 +135,8 @@ def _call(L, ring, **kw):
 
 def test_replay_nstep_validates_before_any_launch():
     from evacx import _lib
-    from evacx.qnet import qlib
-    L = qlib()
-    assert _lib.NSTEP_MAX == 32 and "evx_replay_nstep" in _lib.EXPORTS
+    L = _lib.lib()
+    assert _lib.NSTEP_MAX == 32 and "evx_replay_nstep" in _lib.SIGNATURES
     host = dict(s=np.zeros((CAP, 8), np.int32), s2=np.zeros((CAP, 8), np.int32), a=np.zeros(CAP, np.int32),
                 r=np.zeros(CAP, np.float32), done=np.zeros(CAP, np.uint8))
     ring = dict(c=_lib.evx_replay(capacity=CAP, **{k: v.ctypes.data for k, v in host.items()}),

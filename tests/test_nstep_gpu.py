@@ -114,8 +114,8 @@ def test_replay_nstep_keeps_a_slot_outside_the_range(kernel_ring):
 # ------------------------------------------------------------------ 2. n_step = 1 is the identity
 def _run_td(Q, Qt, act, rew, done, B, nets, w, sel, delta, gamma_row, use_opt=True):
     from evacx.qmlp import td_opts
-    from evacx.qnet import qcheck, qlib
-    L = qlib()
+    from evacx._lib import check, lib
+    L = lib()
     A = Q.shape[1]
     dQ = torch.full((nets * B, A), float("nan"), device=DEV)
     loss = torch.full((nets,), float("nan"), device=DEV)
@@ -123,8 +123,8 @@ def _run_td(Q, Qt, act, rew, done, B, nets, w, sel, delta, gamma_row, use_opt=Tr
     ws = torch.zeros(int(L.evx_td_loss_ws_floats(B, nets)), device=DEV)
     p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     o = td_opts(sel, delta, gamma_row)
-    qcheck(L.evx_td_loss_opt(p(Q), p(Qt), A, p(act), p(rew), p(done), GAMMA, B, nets, p(w), p(dQ), p(loss), p(td_abs),
-                             None, 0, p(ws), ws.numel(), C.byref(o) if use_opt else None, None), "td_loss_opt")
+    check(L.evx_td_loss_opt(p(Q), p(Qt), A, p(act), p(rew), p(done), GAMMA, B, nets, p(w), p(dQ), p(loss), p(td_abs),
+                            None, 0, p(ws), ws.numel(), C.byref(o) if use_opt else None, None), "td_loss_opt")
     torch.cuda.synchronize()
     return dQ, loss, td_abs
 

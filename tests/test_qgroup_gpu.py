@@ -121,7 +121,7 @@ def test_grouped_act_equals_single_net_act(eps):
 def test_qmix_kernel_matches_torch_autograd():
     _need_gpu()
     from evacx.qmix import MixingNetwork
-    from evacx.qmlp import mlib
+    from evacx._lib import lib
     n, B, A = 3, 700, 5
     torch.manual_seed(2)
     mix, mix_t = MixingNetwork(n).cuda(), MixingNetwork(n).cuda()
@@ -136,16 +136,16 @@ def test_qmix_kernel_matches_torch_autograd():
     done = (torch.rand(B, device="cuda") < 0.3).to(torch.uint8)
     flat = torch.cat([p.detach().reshape(-1) for p in mix.state_dict().values()])
     flat_t = torch.cat([p.detach().reshape(-1) for p in mix_t.state_dict().values()])
-    nm = int(mlib().evx_qmix_nparams(n))
+    nm = int(lib().evx_qmix_nparams(n))
     assert nm == flat.numel()
     dQ = torch.full((n, B, A), 5.0, device="cuda")
     grad = torch.empty(nm, device="cuda")
     loss = torch.empty(1, device="cuda")
-    part = torch.empty(int(mlib().evx_qmix_part_floats(B, n)), device="cuda")
+    part = torch.empty(int(lib().evx_qmix_part_floats(B, n)), device="cuda")
     zero = torch.ones(1000, device="cuda")
-    rc = mlib().evx_qmix_loss(Q.data_ptr(), Qt.data_ptr(), A, act.data_ptr(), rew.data_ptr(), done.data_ptr(), 0.99, B,
-                              n, flat.data_ptr(), flat_t.data_ptr(), dQ.data_ptr(), grad.data_ptr(), loss.data_ptr(),
-                              part.data_ptr(), zero.data_ptr(), zero.numel(), None)
+    rc = lib().evx_qmix_loss(Q.data_ptr(), Qt.data_ptr(), A, act.data_ptr(), rew.data_ptr(), done.data_ptr(), 0.99, B,
+                             n, flat.data_ptr(), flat_t.data_ptr(), dQ.data_ptr(), grad.data_ptr(), loss.data_ptr(),
+                             part.data_ptr(), zero.data_ptr(), zero.numel(), None)
     assert rc == 0
     q = Q.gather(2, act.long().unsqueeze(2)).squeeze(2).t().contiguous().requires_grad_(True)  # [B][n]
     with torch.no_grad():

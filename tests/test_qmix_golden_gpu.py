@@ -18,13 +18,13 @@ def test_device_mixer_matches_reference_steps():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     import ctypes as C
-    from evacx.qmlp import mlib
-    from evacx.qnet import evx_adam, qcheck, qlib
+    from evacx._lib import check, lib
+    from evacx.qnet import evx_adam
     fx = load("qmix_mixer")
     names = [str(n) for n in fx["names"]]
     n, A, dev = 2, 5, "cuda"
     flat = torch.cat([torch.from_numpy(fx["init_" + k]).reshape(-1) for k in names]).to(dev)
-    nm = int(mlib().evx_qmix_nparams(n))
+    nm = int(lib().evx_qmix_nparams(n))
     assert nm == flat.numel()
     flat_t = flat.clone()
     m, v, grad = torch.zeros_like(flat), torch.zeros_like(flat), torch.zeros_like(flat)
@@ -46,19 +46,19 @@ def test_device_mixer_matches_reference_steps():
         # raw pointers below: [n][B][A] contiguous (the broadcast above may leave Qt's strides permuted)
         Q, Qt, act, rew, done = [t.contiguous().to(dev) for t in (Q, Qt, act, rew, done)]
         dQ = torch.full((n, B, A), 7.0, device=dev)
-        part = torch.empty(int(mlib().evx_qmix_part_floats(B, n)), device=dev)
+        part = torch.empty(int(lib().evx_qmix_part_floats(B, n)), device=dev)
         zero = torch.ones(64, device=dev)
-        rc = mlib().evx_qmix_loss(Q.data_ptr(), Qt.data_ptr(), A, act.data_ptr(), rew.data_ptr(), done.data_ptr(),
-                                  0.99, B, n, flat.data_ptr(), flat_t.data_ptr(), dQ.data_ptr(), grad.data_ptr(),
-                                  loss.data_ptr(), part.data_ptr(), zero.data_ptr(), zero.numel(), None)
+        rc = lib().evx_qmix_loss(Q.data_ptr(), Qt.data_ptr(), A, act.data_ptr(), rew.data_ptr(), done.data_ptr(),
+                                 0.99, B, n, flat.data_ptr(), flat_t.data_ptr(), dQ.data_ptr(), grad.data_ptr(),
+                                 loss.data_ptr(), part.data_ptr(), zero.data_ptr(), zero.numel(), None)
         assert rc == 0
-        L = qlib()
-        qcheck(L.evx_sumsq_norm(grad.data_ptr(), nm, scratch.data_ptr(), scratch.numel(), norm.data_ptr(), None),
-               "sumsq")
+        L = lib()
+        check(L.evx_sumsq_norm(grad.data_ptr(), nm, scratch.data_ptr(), scratch.numel(), norm.data_ptr(), None),
+              "sumsq")
         raw = grad.clone()
         h = evx_adam(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=s + 1)
-        qcheck(L.evx_clip_adam(flat.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), nm, norm.data_ptr(), 1.0,
-                               C.byref(h), None), "clip_adam")
+        check(L.evx_clip_adam(flat.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), nm, norm.data_ptr(), 1.0,
+                              C.byref(h), None), "clip_adam")
         torch.cuda.synchronize()
         ref_loss = float(fx[p + "loss"])
         assert abs(loss.item() - ref_loss) <= 1e-4 * abs(ref_loss), (s, loss.item(), ref_loss)

@@ -85,9 +85,9 @@ def test_fused_forward_matches_torch(p_drop):
     refq = ref2 @ sd["fc3.weight"].t() + sd["fc3.bias"]
     torch.testing.assert_close(q, refq, rtol=1e-3, atol=1e-3)
     # fused epsilon-greedy == evx_act on the same Q
-    from evacx.qnet import qcheck, qlib
+    from evacx._lib import check, lib
     act2 = torch.empty_like(act)
-    qcheck(qlib().evx_act(q.data_ptr(), n, 5, 0.3, 99, 1000, act2.data_ptr(), 0), "act")
+    check(lib().evx_act(q.data_ptr(), n, 5, 0.3, 99, 1000, act2.data_ptr(), 0), "act")
     torch.cuda.synchronize()
     assert torch.equal(act, act2)
 
@@ -115,7 +115,8 @@ def test_fused_backward_matches_torch_autograd():
     the weight-gradient GEMMs: max error <= 3e-2 of each gradient's max magnitude."""
     _need_gpu()
     from evacx.qmlp import HID, K1, K1P, MLPFast, dropout_keep
-    from evacx.qnet import Learner, qcheck, qlib
+    from evacx._lib import check, lib
+    from evacx.qnet import Learner
     lay, env = _env_obs(E=160, R=4)
     B = 256
     dev = "cuda"
@@ -137,9 +138,9 @@ def test_fused_backward_matches_torch_autograd():
     loss = torch.empty(1, device=dev)
     fast.forward(lay.c, obs_s, B, H1, drop=(5, 1, 0.2), x=X, h2=H2, q=Q)
     fast_t.forward(lay.c, obs_s2, B, H1t, drop=(5, 2, 0.2), q=Qt)
-    tw = torch.empty(int(qlib().evx_td_loss_ws_floats(B, 1)), device=dev)
-    qcheck(qlib().evx_td_loss(Q.data_ptr(), Qt.data_ptr(), 5, a.data_ptr(), r.data_ptr(), done.data_ptr(), 0.99, B,
-                              dQ.data_ptr(), loss.data_ptr(), tw.data_ptr(), tw.numel(), 0), "td")
+    tw = torch.empty(int(lib().evx_td_loss_ws_floats(B, 1)), device=dev)
+    check(lib().evx_td_loss(Q.data_ptr(), Qt.data_ptr(), 5, a.data_ptr(), r.data_ptr(), done.data_ptr(), 0.99, B,
+                            dQ.data_ptr(), loss.data_ptr(), tw.data_ptr(), tw.numel(), 0), "td")
     dz2 = torch.empty(B * 256, dtype=torch.int16, device=dev)
     dz1 = torch.empty(B * HID, dtype=torch.int16, device=dev)
     fast.backward(B, dQ, X, H1, H2, 0.2, dz2, dz1, lr.grads)

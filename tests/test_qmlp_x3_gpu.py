@@ -94,7 +94,8 @@ def test_x3_act_matches_forward(eps):
     x3 forward's Q and actions bit for bit (same K order), ragged act-sized batch."""
     _need_gpu()
     from evacx.qmlp import HID, MLPFast
-    from evacx.qnet import Learner, qcheck, qlib
+    from evacx._lib import check, lib
+    from evacx.qnet import Learner
     lay, env = _env_obs(E=700, steps=3, R=16, grid=64, people=500)
     n = env.E * lay.R - 7
     lr = Learner(kind="mlp", precision="f32", seed=31)
@@ -113,7 +114,7 @@ def test_x3_act_matches_forward(eps):
     assert torch.equal(a1, a2[:n])
     assert torch.all(q2[n:] == 9.0) and torch.all(a2[n:] == -1)
     a3 = torch.empty_like(a1)
-    qcheck(qlib().evx_act(q1.data_ptr(), n, 5, eps, 4, 123, a3.data_ptr(), 0), "act")
+    check(lib().evx_act(q1.data_ptr(), n, 5, eps, 4, 123, a3.data_ptr(), 0), "act")
     torch.cuda.synchronize()
     assert torch.equal(a1, a3)
 

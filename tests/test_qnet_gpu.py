@@ -147,24 +147,24 @@ def _relu_flips(lr, params, x):
 
 def test_act_argmax_and_epsilon():
     _need_gpu()
-    from evacx import qnet
+    from evacx import _lib, qnet
     Q = torch.tensor([[0, 1, 3, 3, 2], [5, 5, 5, 5, 5], [-1, -2, -3, -4, -0.5]], dtype=torch.float32).cuda()
     out = torch.zeros(3, dtype=torch.int32, device="cuda")
-    qnet.qcheck(qnet.qlib().evx_act(Q.data_ptr(), 3, 5, 0.0, 1, 0, out.data_ptr(), qnet._stream()), "act")
+    _lib.check(_lib.lib().evx_act(Q.data_ptr(), 3, 5, 0.0, 1, 0, out.data_ptr(), qnet._stream()), "act")
     assert out.cpu().tolist() == [2, 0, 4]  # first maximum, as np.argmax
     Qb = torch.zeros(100000, 5, device="cuda")
     Qb[:, 3] = 1
     ob = torch.zeros(100000, dtype=torch.int32, device="cuda")
-    qnet.qcheck(qnet.qlib().evx_act(Qb.data_ptr(), 100000, 5, 0.25, 7, 0, ob.data_ptr(), qnet._stream()), "act")
+    _lib.check(_lib.lib().evx_act(Qb.data_ptr(), 100000, 5, 0.25, 7, 0, ob.data_ptr(), qnet._stream()), "act")
     frac = (ob != 3).float().mean().item()
     assert abs(frac - 0.25 * 0.8) < 0.01  # random action is 3 one time in five
 
 
 def test_dropout_mask_rate():
     _need_gpu()
-    from evacx import qnet
+    from evacx import _lib, qnet
     m = torch.zeros(1 << 20, dtype=torch.uint8, device="cuda")
-    qnet.qcheck(qnet.qlib().evx_dropout_mask(m.data_ptr(), m.numel(), 0.2, 11, 0, qnet._stream()), "mask")
+    _lib.check(_lib.lib().evx_dropout_mask(m.data_ptr(), m.numel(), 0.2, 11, 0, qnet._stream()), "mask")
     assert abs(m.float().mean().item() - 0.8) < 0.003
 
 

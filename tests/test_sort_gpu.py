@@ -2,7 +2,6 @@
 512-key register blocks with memory passes beyond -- the contested list of a big grid's heavy env
 reaches thousands of movers) through evx_diag_sort_keys, against numpy's sort of the same
 distinct keys (target << pb | person, as the step builds them)."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -17,7 +16,6 @@ def test_step_key_sort_matches_numpy(n):
         pytest.skip("no GPU")
     from evacx import _lib
     L = _lib.lib()
-    L.evx_diag_sort_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     rng = np.random.default_rng(n)
     pb = 14  # person bits of a 9102-person layout
     targets = rng.integers(0, 66564, n, dtype=np.uint64)

@@ -23,10 +23,9 @@ def _td_loss_opt(L, opt, Q=None):
 
 
 def test_new_entries_validate_before_any_launch():
-    from evacx.qmlp import evx_qmlp_grads, evx_qmlp_params, mlib, td_opts
-    from evacx.qnet import qlib
-    L = qlib()
-    mlib()
+    from evacx._lib import lib
+    from evacx.qmlp import evx_qmlp_grads, evx_qmlp_params, td_opts
+    L = lib()
     # a NULL Q
     rc = _td_loss_opt(L, None)
     assert rc < 0 and b"NULL" in L.evx_q_last_error()

@@ -99,8 +99,8 @@ def np_td(Q, Qt, act, rew, done, gamma, B, sel, delta, w):
 def _run_td(entry, Q, Qt, act, rew, done, B, nets, w, sel, delta, nzero=5000):
     """entry: "g" (evx_td_loss_zero_g), "null" (evx_td_loss_opt, opt = NULL) or "opt"."""
     from evacx.qmlp import td_opts
-    from evacx.qnet import qcheck, qlib
-    L = qlib()
+    from evacx._lib import check, lib
+    L = lib()
     A = Q.shape[1]
     dQ = torch.full((nets * B, A), float("nan"), device=DEV)
     loss = torch.full((nets,), float("nan"), device=DEV)
@@ -112,10 +112,10 @@ def _run_td(entry, Q, Qt, act, rew, done, B, nets, w, sel, delta, nzero=5000):
             p(ws), ws.numel())
     if entry == "g":
         assert sel is None and delta == 0
-        qcheck(L.evx_td_loss_zero_g(*head, None), "td_loss_zero_g")
+        check(L.evx_td_loss_zero_g(*head, None), "td_loss_zero_g")
     else:
         o = td_opts(sel, delta)
-        qcheck(L.evx_td_loss_opt(*head, None if entry == "null" else C.byref(o), None), "td_loss_opt")
+        check(L.evx_td_loss_opt(*head, None if entry == "null" else C.byref(o), None), "td_loss_opt")
     torch.cuda.synchronize()
     return dQ, loss, td_abs, zero
 
@@ -447,7 +447,8 @@ def _packed(fast):
 def test_soft_update_without_the_fused_mlp_and_evx_polyak_alone():
     _need_gpu()
     from evacx.qmlp import polyak_coeffs
-    from evacx.qnet import Learner, qcheck, qlib
+    from evacx._lib import check, lib
+    from evacx.qnet import Learner
     lr = Learner(kind="mlp", precision="exact", seed=5, target_tau=0.37)
     assert lr.fast_t is None
     lr.online.flat.mul_(1.25)
@@ -460,7 +461,7 @@ def test_soft_update_without_the_fused_mlp_and_evx_polyak_alone():
     tt = torch.randn(n + 5, generator=g).to(DEV)
     pn, tn = pp.cpu().numpy(), tt.cpu().numpy()
     tf, omt = polyak_coeffs(0.005)
-    qcheck(qlib().evx_polyak(pp.data_ptr(), tt.data_ptr(), n, tf, omt, None), "polyak")
+    check(lib().evx_polyak(pp.data_ptr(), tt.data_ptr(), n, tf, omt, None), "polyak")
     torch.cuda.synchronize()
     out = tt.cpu().numpy()
     assert np.array_equal(out[:n], _np_polyak(0.005, pn[:n], tn[:n]))
