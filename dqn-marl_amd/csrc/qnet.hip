@@ -28,7 +28,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BM = 64, BN = 64, BK = 32;
+constexpr int BK = 32;  // K tile of the 128 x 128 GEMM kernels
 
 // Philox4x32-10, the replay permutation (evx_draws.h)
 using evxd::u4;
@@ -46,71 +46,6 @@ template <>
 __device__ __forceinline__ float to_in<float>(float v) { return v; }
 template <>
 __device__ __forceinline__ __bf16 to_in<__bf16>(float v) { return (__bf16)v; }
-
-template <typename TIn>
-__global__ __launch_bounds__(256) void gemm_kernel(evx_gemm_desc g) {
-    constexpr int PADK = sizeof(TIn) == 4 ? 1 : 8;
-    __shared__ __attribute__((aligned(16))) TIn As[BM][BK + PADK];
-    __shared__ __attribute__((aligned(16))) TIn Bs[BN][BK + PADK];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w >> 1, wn = w & 1;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] = 0.f;
-    const bool a_kc = g.sak == 1, b_nc = g.sbn == 1;
-    for (int k0 = 0; k0 < g.K; k0 += BK) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int idx = tid + 256 * i;
-            int mm, kk;
-            if (a_kc) { mm = idx >> 5; kk = idx & 31; } else { kk = idx >> 6; mm = idx & 63; }
-            const int gm = m0 + mm, gk = k0 + kk;
-            const float v = (gm < g.M && gk < g.K) ? g.A[(int64_t)gm * g.sam + (int64_t)gk * g.sak] : 0.f;
-            As[mm][kk] = to_in<TIn>(v);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int idx = tid + 256 * i;
-            int nn, kk;
-            if (b_nc) { kk = idx >> 6; nn = idx & 63; } else { nn = idx >> 5; kk = idx & 31; }
-            const int gn = n0 + nn, gk = k0 + kk;
-            const float v = (gn < g.N && gk < g.K) ? g.B[(int64_t)gk * g.sbk + (int64_t)gn * g.sbn] : 0.f;
-            Bs[nn][kk] = to_in<TIn>(v);
-        }
-        __syncthreads();
-        const int ar = wm * 32 + (lane & 31), br = wn * 32 + (lane & 31), h = lane >> 5;
-        if constexpr (sizeof(TIn) == 4) {
-#pragma unroll
-            for (int kk = 0; kk < BK / 2; kk++)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[ar][2 * kk + h], Bs[br][2 * kk + h], acc, 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int s = 0; s < BK / 16; s++) {
-                const bf16x8 a = *reinterpret_cast<const bf16x8*>(&As[ar][16 * s + 8 * h]);
-                const bf16x8 b = *reinterpret_cast<const bf16x8*>(&Bs[br][16 * s + 8 * h]);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
-    // epilogue: C/D map of the 32x32 MFMA (col = lane&31, row = (r&3) + 8(r>>2) + 4(lane>>5))
-    const int gn = n0 + wn * 32 + (lane & 31);
-    if (gn >= g.N) return;
-    const float bias = g.bias ? g.bias[gn] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int gm = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (gm >= g.M) continue;
-        float v = g.alpha * acc[r] + bias;
-        if (g.flags & EVX_GEMM_RELU) v = v > 0.f ? v : 0.f;
-        if (g.mask) v = g.mask[(int64_t)gm * g.ldm + gn] ? v * g.mask_scale : 0.f;
-        if (g.gate) v = g.gate[(int64_t)gm * g.ldg + gn] > 0.f ? v : 0.f;
-        float* cp = g.C + (int64_t)gm * g.ldc + gn;
-        if (g.flags & EVX_GEMM_ACCUM) v += *cp;
-        *cp = v;
-    }
-}
 
 // ------------------------------------------------------------- GEMM, big tiles
 // 128x128x32 block tile, 4 waves as 2x2, each wave 64x64 = 2x2 MFMA 32x32 tiles (64 f32
@@ -1511,7 +1446,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x3_kernel(evx_gemm_desc g, int
 // waves of a column tile split the 4 row tiles and (KH > 1) the K steps, the K parts added through
 // LDS in a fixed order; conv2 (NT 2, NTW 2, KH 1): one row tile and all 18 k-steps per wave (act
 // 223 -> 139 us at 8192 images). (conv3 as NT 4, NTW 2, KH 4 -- a quarter of the 36 k-steps per
-// wave -- measured slower than the per-image kernel: see conv_direct.) Row tiles RP at a time. The next image's input is loaded into registers while the current one is
+// wave -- measured slower than the per-image kernel: see gemm_launch.) Row tiles RP at a time. The next image's input is loaded into registers while the current one is
 // computed, then staged as bf16 hi / lo planes over the 13x13 zero-bordered grid (the layout,
 // fragments, x3 products and epilogue of conv3x3_x3_kernel).
 template <int CP, int NT, int NTW, int KH, int RP>
@@ -1736,24 +1671,6 @@ static void conv_wreg_launch(const evx_gemm_desc* g, int cs, __bf16* wp, hipStre
     hipLaunchKernelGGL((evxq::conv3x3_wreg_kernel<CP, NT, NTW, KH, RP>), dim3((unsigned)(nslot * CG)), dim3(512), 0, st,
                        *g, cs, (const __bf16*)wp, nimg, nslot);
 }
-static bool conv_direct(const evx_gemm_desc* g, int mode, int cs, hipStream_t st) {
-    const int cp = conv_direct_cp(g, mode, cs);
-    if (!cp || !g->ws || g->ws_elems < conv_direct_ws(g, mode, cs)) return false;
-    __bf16* wp = reinterpret_cast<__bf16*>(g->ws);
-    if (mode == EVX_CONV_FWD) {
-        if (cp == 16) conv_direct_launch<16, 1, false>(g, cs, wp, st);
-        else if (cp == 32) conv_wreg_launch<32, 2, 2, 1, 1>(g, cs, wp, st);
-        // conv3 keeps the per-image kernel: with its 36 k-steps of weights split over four waves
-        // (conv3x3_wreg_kernel<64, 4, 2, 4, 2>, 254 VGPRs) the K-part reductions and their barriers
-        // per image cost more than the weight re-reads saved (act 654 -> ~1000 us, learn 88 -> 130 us)
-        else conv_direct_launch<64, 4, false>(g, cs, wp, st);
-    } else {
-        if (cp == 64) conv_direct_launch<64, 1, true>(g, cs, wp, st);
-        else conv_direct_launch<128, 2, true>(g, cs, wp, st);
-    }
-    return true;
-}
-
 // tn3_kernel's cases: x3, alpha 1, B n-contiguous (sbn 1) or the conv dW gather (channels a multiple
 // of 4, no epilogue), A m- or k-contiguous, row strides and widths multiples of 4, 16-B aligned
 // returns 0 (not this kernel's case), 1 (A k-major: A[k][m], sam 1) or 2 (A k-contiguous: A[m][k], sak 1;
@@ -1771,74 +1688,165 @@ static int tn3_ok(const evx_gemm_desc* g, int cm, int cs) {
     if (g->sak == 1 && (g->sam & 3) == 0 && (g->K & 3) == 0 && bplain) return 2;
     return 0;
 }
-int gemm_launch(const evx_gemm_desc* g, int cm, int cs, void* stream) {
+
+// The one decision of what a descriptor runs on: the route (EVX_ROUTE_*: the kernel or template
+// instantiation), the K slices with their length, and the split-K reduction. Host arithmetic on the
+// descriptor only. gemm_launch switches on the plan and evx_gemm_plan_query hands it out, so a test
+// that asks for a route is asking the launcher. The argument errors of a launch are reported here.
+int gemm_plan(const evx_gemm_desc* g, int cm, int cs, evx_gemm_plan* p) {
+    p->route = EVX_ROUTE_NONE;
+    p->slices = p->klen = 0;
+    p->reduce = EVX_REDUCE_NONE;
     if (!g || !g->A || !g->B || !g->C) return fail(-22, "gemm: NULL operand");
     if (g->M <= 0 || g->N <= 0 || g->K <= 0) return 0;
     if (g->ws_elems < 0) return fail(-22, "gemm: ws_elems < 0");
     const int TB = evxq::TB;
     int klen = 0;
     const int S = gemm_slices(g, g->ws ? g->ws_elems : 0, &klen);
-    dim3 grid((unsigned)((g->N + TB - 1) / TB), (unsigned)((g->M + TB - 1) / TB), (unsigned)S);
-    if (grid.y > 65535u) return fail(-22, "gemm: M too large for one launch");
+    if ((unsigned)((g->M + TB - 1) / TB) > 65535u) return fail(-22, "gemm: M too large for one launch");
+    int route;
+    if (int cp; (cm == evxq::CV_FWD || cm == evxq::CV_DX) && S == 1 && (cp = conv_direct_cp(g, cm, cs)) != 0 && g->ws &&
+                g->ws_elems >= conv_direct_ws(g, cm, cs)) {
+        // the LDS-staged conv kernels: their packed weights go to the workspace
+        if (cm == evxq::CV_FWD)
+            route = cp == 16 ? EVX_ROUTE_CONV_LDS16_FWD : cp == 32 ? EVX_ROUTE_CONV_WREG32_FWD : EVX_ROUTE_CONV_LDS64_FWD;
+        else
+            route = cp == 64 ? EVX_ROUTE_CONV_LDS64_DX : EVX_ROUTE_CONV_LDS128_DX;
+    } else if (g->flags & EVX_GEMM_OUT_SPLIT) {
+        return fail(-22, "gemm: OUT_SPLIT needs the LDS-staged conv forward (and its workspace)");
+    } else if (const int tk = tn3_ok(g, cm, cs)) {  // B k-major (weight gradients: fc and conv dW; activation gradients)
+        route = tk == 2 ? EVX_ROUTE_TN3_AK : cm == evxq::CV_DW ? EVX_ROUTE_TN3_CONV_DW : EVX_ROUTE_TN3_KMAJOR;
+    } else if (g->flags & EVX_GEMM_SPLIT_AB) {
+        if (cm != evxq::CV_NONE || g->precision != EVX_PREC_X3 || g->sak != 1 || g->sbk != 1 || (g->K & 7) ||
+            (g->sam & 7) || (g->sbn & 7))
+            return fail(-22, "gemm: SPLIT_AB needs x3, k-contiguous operands, K and row strides multiples of 8");
+        route = EVX_ROUTE_X3_SPLIT_AB;
+    } else if (cm == evxq::CV_FWD) {
+        route = EVX_ROUTE_X3_CONV_FWD;
+    } else if (cm == evxq::CV_DX) {
+        route = EVX_ROUTE_X3_CONV_DX;
+    } else if (cm == evxq::CV_DW) {
+        route = EVX_ROUTE_X3_CONV_DW;
+    } else if (g->precision == EVX_PREC_BF16) {
+        route = EVX_ROUTE_GEMM128_BF16;
+    } else if (g->precision == EVX_PREC_X3) {
+        // k-contiguous f32 operands staged from 16-B loads (the fc layers' forward: A and B; dX: A)
+        auto al16 = [](const float* q) { return ((uintptr_t)q & 15) == 0; };
+        const bool ak = g->sak == 1 && (g->sam & 3) == 0 && (g->K & 3) == 0 && al16(g->A);
+        const bool bk = g->sbk == 1 && (g->sbn & 3) == 0 && (g->K & 3) == 0 && al16(g->B);
+        route = ak && bk ? EVX_ROUTE_X3_VEC_AB : ak ? EVX_ROUTE_X3_VEC_A : bk ? EVX_ROUTE_X3_VEC_B : EVX_ROUTE_X3_SCALAR;
+    } else {
+        route = EVX_ROUTE_GEMM128_F32;
+    }
+    p->route = route;
+    p->slices = S;
+    p->klen = klen;
+    if (S > 1)  // the slices' partials summed in slice order, then the epilogue
+        p->reduce = S >= 8 && (((int64_t)g->M * g->N) & 3) == 0 ? EVX_REDUCE_QUARTERS : EVX_REDUCE_GENERIC;
+    return 0;
+}
+
+// evx_conv3x3_gemm's argument checks (before gemm_plan's)
+int conv_args(const evx_gemm_desc* g, int mode, int cs) {
+    if (!g) return fail(-22, "conv3x3: NULL descriptor");
+    if (g->precision != EVX_PREC_X3) return fail(-22, "conv3x3: implicit-GEMM convolution is x3 only");
+    if (mode < EVX_CONV_FWD || mode > EVX_CONV_DW) return fail(-22, "conv3x3: bad mode");
+    if (cs <= 0) return fail(-22, "conv3x3: channels <= 0");
+    const int64_t pix = mode == EVX_CONV_DW ? g->K : g->M;  // rows of the pixel-major activations
+    if (pix % 121 || pix >= (1LL << 26)) return fail(-22, "conv3x3: pixel count not 121*B (< 2^26)");
+    if ((mode == EVX_CONV_DW ? g->N : g->K) != 9 * cs) return fail(-22, "conv3x3: 3x3 taps x channels mismatch");
+    if (mode == EVX_CONV_DW && (g->sam != 1 || g->sak != g->M))
+        return fail(-22, "conv3x3 dW: A must be dY [pixels][M]");
+    return 0;
+}
+
+int gemm_launch(const evx_gemm_desc* g, int cm, int cs, void* stream) {
+    evx_gemm_plan plan;
+    if (const int e = gemm_plan(g, cm, cs, &plan)) return e;
+    if (plan.route == EVX_ROUTE_NONE) return 0;
+    const int TB = evxq::TB, klen = plan.klen;
+    const dim3 grid((unsigned)((g->N + TB - 1) / TB), (unsigned)((g->M + TB - 1) / TB), (unsigned)plan.slices);
     hipStream_t st = (hipStream_t)stream;
-    if ((cm == evxq::CV_FWD || cm == evxq::CV_DX) && S == 1 && conv_direct(g, cm, cs, st)) return hip_status("conv3x3");
-    if (g->flags & EVX_GEMM_OUT_SPLIT) return fail(-22, "gemm: OUT_SPLIT needs the LDS-staged conv forward (and its workspace)");
-    if (const int tk = tn3_ok(g, cm, cs)) {  // B k-major (weight gradients: fc and conv dW; activation gradients)
-        {
+    __bf16* wp = reinterpret_cast<__bf16*>(g->ws);  // the LDS-staged conv kernels' packed weights
+    switch (plan.route) {
+        case EVX_ROUTE_CONV_LDS16_FWD:
+            conv_direct_launch<16, 1, false>(g, cs, wp, st);
+            return hip_status("conv3x3");
+        case EVX_ROUTE_CONV_WREG32_FWD:
+            conv_wreg_launch<32, 2, 2, 1, 1>(g, cs, wp, st);
+            return hip_status("conv3x3");
+        case EVX_ROUTE_CONV_LDS64_FWD:
+            // conv3 keeps the per-image kernel: with its 36 k-steps of weights split over four waves
+            // (conv3x3_wreg_kernel<64, 4, 2, 4, 2>, 254 VGPRs) the K-part reductions and their barriers
+            // per image cost more than the weight re-reads saved (act 654 -> ~1000 us, learn 88 -> 130 us)
+            conv_direct_launch<64, 4, false>(g, cs, wp, st);
+            return hip_status("conv3x3");
+        case EVX_ROUTE_CONV_LDS64_DX:
+            conv_direct_launch<64, 1, true>(g, cs, wp, st);
+            return hip_status("conv3x3");
+        case EVX_ROUTE_CONV_LDS128_DX:
+            conv_direct_launch<128, 2, true>(g, cs, wp, st);
+            return hip_status("conv3x3");
+        case EVX_ROUTE_TN3_KMAJOR:
+        case EVX_ROUTE_TN3_AK:
+        case EVX_ROUTE_TN3_CONV_DW: {
             static std::atomic<uint64_t> attr_done;
             const void* ks[3] = {(const void*)evxq::tn3_kernel<false>, (const void*)evxq::tn3_kernel<true>,
                                  (const void*)evxq::tn3_kernel<false, true>};
             evxh::max_lds_once(attr_done, ks, 3, evxq::TN3_LDS);
+            if (plan.route == EVX_ROUTE_TN3_AK)
+                hipLaunchKernelGGL((evxq::tn3_kernel<false, true>), grid, dim3(256), evxq::TN3_LDS, st, *g, klen, cs);
+            else if (plan.route == EVX_ROUTE_TN3_CONV_DW)
+                hipLaunchKernelGGL(evxq::tn3_kernel<true>, grid, dim3(256), evxq::TN3_LDS, st, *g, klen, cs);
+            else
+                hipLaunchKernelGGL(evxq::tn3_kernel<false>, grid, dim3(256), evxq::TN3_LDS, st, *g, klen, cs);
+            break;
         }
-        const dim3 tg = grid;
-        if (tk == 2)
-            hipLaunchKernelGGL((evxq::tn3_kernel<false, true>), tg, dim3(256), evxq::TN3_LDS, st, *g, klen, cs);
-        else if (cm == evxq::CV_DW)
-            hipLaunchKernelGGL(evxq::tn3_kernel<true>, tg, dim3(256), evxq::TN3_LDS, st, *g, klen, cs);
-        else
-            hipLaunchKernelGGL(evxq::tn3_kernel<false>, tg, dim3(256), evxq::TN3_LDS, st, *g, klen, cs);
-    } else
-    if (g->flags & EVX_GEMM_SPLIT_AB) {
-        if (cm != evxq::CV_NONE || g->precision != EVX_PREC_X3 || g->sak != 1 || g->sbk != 1 || (g->K & 7) ||
-            (g->sam & 7) || (g->sbn & 7))
-            return fail(-22, "gemm: SPLIT_AB needs x3, k-contiguous operands, K and row strides multiples of 8");
-        hipLaunchKernelGGL((evxq::gemm128x3_kernel<evxq::CV_NONE, true>), grid, dim3(256), 0, st, *g, klen, 0);
-    } else
-    if (cm == evxq::CV_FWD)
-        hipLaunchKernelGGL(evxq::gemm128x3_kernel<evxq::CV_FWD>, grid, dim3(256), 0, st, *g, klen, cs);
-    else if (cm == evxq::CV_DX)
-        hipLaunchKernelGGL(evxq::gemm128x3_kernel<evxq::CV_DX>, grid, dim3(256), 0, st, *g, klen, cs);
-    else if (cm == evxq::CV_DW)
-        hipLaunchKernelGGL(evxq::gemm128x3_kernel<evxq::CV_DW>, grid, dim3(256), 0, st, *g, klen, cs);
-    else if (g->precision == EVX_PREC_BF16)
-        hipLaunchKernelGGL(evxq::gemm128_kernel<__bf16>, grid, dim3(256), 0, st, *g, klen);
-    else if (g->precision == EVX_PREC_X3) {
-        // k-contiguous f32 operands staged from 16-B loads (the fc layers' forward: A and B; dX: A)
-        auto al16 = [](const float* p) { return ((uintptr_t)p & 15) == 0; };
-        const bool ak = g->sak == 1 && (g->sam & 3) == 0 && (g->K & 3) == 0 && al16(g->A);
-        const bool bk = g->sbk == 1 && (g->sbn & 3) == 0 && (g->K & 3) == 0 && al16(g->B);
-        if (ak && bk)
+        case EVX_ROUTE_X3_SPLIT_AB:
+            hipLaunchKernelGGL((evxq::gemm128x3_kernel<evxq::CV_NONE, true>), grid, dim3(256), 0, st, *g, klen, 0);
+            break;
+        case EVX_ROUTE_X3_CONV_FWD:
+            hipLaunchKernelGGL(evxq::gemm128x3_kernel<evxq::CV_FWD>, grid, dim3(256), 0, st, *g, klen, cs);
+            break;
+        case EVX_ROUTE_X3_CONV_DX:
+            hipLaunchKernelGGL(evxq::gemm128x3_kernel<evxq::CV_DX>, grid, dim3(256), 0, st, *g, klen, cs);
+            break;
+        case EVX_ROUTE_X3_CONV_DW:
+            hipLaunchKernelGGL(evxq::gemm128x3_kernel<evxq::CV_DW>, grid, dim3(256), 0, st, *g, klen, cs);
+            break;
+        case EVX_ROUTE_GEMM128_BF16:
+            hipLaunchKernelGGL(evxq::gemm128_kernel<__bf16>, grid, dim3(256), 0, st, *g, klen);
+            break;
+        case EVX_ROUTE_X3_VEC_AB:
             hipLaunchKernelGGL((evxq::gemm128x3_kernel<evxq::CV_NONE, false, evxq::VA_K | evxq::VB_K>), grid, dim3(256), 0,
                                st, *g, klen, 0);
-        else if (ak)
+            break;
+        case EVX_ROUTE_X3_VEC_A:
             hipLaunchKernelGGL((evxq::gemm128x3_kernel<evxq::CV_NONE, false, evxq::VA_K>), grid, dim3(256), 0, st, *g,
                                klen, 0);
-        else if (bk)
+            break;
+        case EVX_ROUTE_X3_VEC_B:
             hipLaunchKernelGGL((evxq::gemm128x3_kernel<evxq::CV_NONE, false, evxq::VB_K>), grid, dim3(256), 0, st, *g,
                                klen, 0);
-        else
+            break;
+        case EVX_ROUTE_X3_SCALAR:
             hipLaunchKernelGGL(evxq::gemm128x3_kernel<evxq::CV_NONE>, grid, dim3(256), 0, st, *g, klen, 0);
+            break;
+        case EVX_ROUTE_GEMM128_F32:
+            hipLaunchKernelGGL(evxq::gemm128_kernel<float>, grid, dim3(256), 0, st, *g, klen);
+            break;
+        default:
+            return fail(-22, "gemm: no kernel for the planned route");
     }
-    else
-        hipLaunchKernelGGL(evxq::gemm128_kernel<float>, grid, dim3(256), 0, st, *g, klen);
-    if (S > 1) {  // the slices' partials summed in slice order, then the epilogue
+    if (plan.reduce != EVX_REDUCE_NONE) {  // the slices' partials summed in slice order, then the epilogue
         const int e = hip_status("gemm");
         if (e) return e;
         const int64_t MN = (int64_t)g->M * g->N;
-        if (S >= 8 && (MN & 3) == 0)
-            hipLaunchKernelGGL(evxq::splitk_reduce4_kernel, dim3((unsigned)((MN / 4 + 63) / 64)), dim3(256), 0, st, *g, S);
+        if (plan.reduce == EVX_REDUCE_QUARTERS)
+            hipLaunchKernelGGL(evxq::splitk_reduce4_kernel, dim3((unsigned)((MN / 4 + 63) / 64)), dim3(256), 0, st, *g,
+                               plan.slices);
         else
-            hipLaunchKernelGGL(evxq::splitk_reduce_kernel, dim3(nblk((MN + 3) / 4)), dim3(256), 0, st, *g, S);
+            hipLaunchKernelGGL(evxq::splitk_reduce_kernel, dim3(nblk((MN + 3) / 4)), dim3(256), 0, st, *g, plan.slices);
     }
     return hip_status("gemm");
 }
@@ -1847,6 +1855,16 @@ int gemm_launch(const evx_gemm_desc* g, int cm, int cs, void* stream) {
 extern "C" {
 
 int evx_gemm(const evx_gemm_desc* g, void* stream) { return gemm_launch(g, evxq::CV_NONE, 0, stream); }
+
+int evx_gemm_plan_query(const evx_gemm_desc* g, int32_t mode, int32_t cs, evx_gemm_plan* out) {
+    if (!out) return fail(-22, "gemm_plan_query: NULL plan");
+    if (mode == 0) return gemm_plan(g, evxq::CV_NONE, 0, out);
+    out->route = EVX_ROUTE_NONE;
+    out->slices = out->klen = 0;
+    out->reduce = EVX_REDUCE_NONE;
+    if (const int e = conv_args(g, mode, cs)) return e;
+    return gemm_plan(g, mode, cs, out);
+}
 
 int64_t evx_gemm_ws_elems(const evx_gemm_desc* g) {
     if (!g || g->M <= 0 || g->N <= 0 || g->K <= 0) return 0;
@@ -1864,15 +1882,7 @@ int64_t evx_conv3x3_ws_elems(const evx_gemm_desc* g, int32_t mode, int32_t cs) {
 }
 
 int evx_conv3x3_gemm(const evx_gemm_desc* g, int32_t mode, int32_t cs, void* stream) {
-    if (!g) return fail(-22, "conv3x3: NULL descriptor");
-    if (g->precision != EVX_PREC_X3) return fail(-22, "conv3x3: implicit-GEMM convolution is x3 only");
-    if (mode < EVX_CONV_FWD || mode > EVX_CONV_DW) return fail(-22, "conv3x3: bad mode");
-    if (cs <= 0) return fail(-22, "conv3x3: channels <= 0");
-    const int64_t pix = mode == EVX_CONV_DW ? g->K : g->M;  // rows of the pixel-major activations
-    if (pix % 121 || pix >= (1LL << 26)) return fail(-22, "conv3x3: pixel count not 121*B (< 2^26)");
-    if ((mode == EVX_CONV_DW ? g->N : g->K) != 9 * cs) return fail(-22, "conv3x3: 3x3 taps x channels mismatch");
-    if (mode == EVX_CONV_DW && (g->sam != 1 || g->sak != g->M))
-        return fail(-22, "conv3x3 dW: A must be dY [pixels][M]");
+    if (const int e = conv_args(g, mode, cs)) return e;
     return gemm_launch(g, mode, cs, stream);
 }
 

@@ -33,6 +33,12 @@ OBS_WORDS = 8  # sizeof(evx_obs) / 4
 PREC = {"f32": 0, "bf16": 1, "x3": 2}  # EVX_PREC_*
 RELU, ACCUM, SPLIT_AB, OUT_SPLIT = 1, 2, 4, 8  # EVX_GEMM_*
 CONV_FWD, CONV_DX, CONV_DW = 1, 2, 3  # EVX_CONV_*
+# EVX_ROUTE_*: the kernel a GEMM / conv descriptor runs on (evx_gemm_plan_query)
+ROUTE = {"NONE": 0, "GEMM128_F32": 1, "GEMM128_BF16": 2, "X3_VEC_AB": 3, "X3_VEC_A": 4, "X3_VEC_B": 5,
+         "X3_SCALAR": 6, "X3_SPLIT_AB": 7, "TN3_KMAJOR": 8, "TN3_AK": 9, "TN3_CONV_DW": 10, "X3_CONV_FWD": 11,
+         "X3_CONV_DX": 12, "X3_CONV_DW": 13, "CONV_LDS16_FWD": 14, "CONV_WREG32_FWD": 15, "CONV_LDS64_FWD": 16,
+         "CONV_LDS64_DX": 17, "CONV_LDS128_DX": 18}
+REDUCE = {"NONE": 0, "GENERIC": 1, "QUARTERS": 2}  # EVX_REDUCE_*: the split-K reduction kernel
 EPISODE_REDUCE_SPAN = 1024  # EVX_EPISODE_REDUCE_SPAN: envs one pass of a reduce workgroup covers
 EPISODE_ROW_WORDS = 10  # sizeof(evx_episode_row) / 8
 HEALTH_ROW_WORDS = 6  # sizeof(evx_health_row) / 8
@@ -75,6 +81,10 @@ class evx_gemm_desc(C.Structure):
                 ("C", C.c_void_p), ("ldc", C.c_int64), ("bias", C.c_void_p),
                 ("mask", C.c_void_p), ("ldm", C.c_int64), ("mask_scale", C.c_float),
                 ("gate", C.c_void_p), ("ldg", C.c_int64), ("ws", C.c_void_p), ("ws_elems", C.c_int64)]
+
+
+class evx_gemm_plan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ["route", "slices", "klen", "reduce"]]
 
 
 class evx_adam(C.Structure):
@@ -157,6 +167,7 @@ SIGNATURES = {
     "evx_gemm_ws_elems": (C.c_int64, [_P(evx_gemm_desc)]),
     "evx_conv3x3_gemm": (C.c_int, [_P(evx_gemm_desc), _i32, _i32, _vp]),
     "evx_conv3x3_ws_elems": (C.c_int64, [_P(evx_gemm_desc), _i32, _i32]),
+    "evx_gemm_plan_query": (C.c_int, [_P(evx_gemm_desc), _i32, _i32, _P(evx_gemm_plan)]),
     "evx_colsum": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
     "evx_td_loss_ws_floats": (C.c_int64, [_i32, _i32]),
     "evx_td_loss": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32] + [_vp] * 3 + [_i64, _vp]),

@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from ._lib import (ACCUM, CONV_DW, CONV_DX, CONV_FWD, OUT_SPLIT, PREC, RELU, SPLIT_AB, check,  # noqa: F401
-                   evx_adam, evx_gemm_desc, lib)
+                   evx_adam, evx_gemm_desc, evx_gemm_plan, lib)
 from .env import _stream
 from .qmlp import evx_td_opts, polyak_coeffs, td_opts, validate_td_options  # noqa: F401 (re-exported)
 
@@ -67,27 +67,48 @@ def _attach_ws(d, ws, tag, device, conv=None):
     d.ws, d.ws_elems = buf.data_ptr(), need
 
 
-def gemm(M, N, K, A, sam, sak, B, sbk, sbn, Cm, ldc, precision="f32", bias=None, relu=False, mask=None,
-         ldm=0, mask_scale=1.0, gate=None, ldg=0, accumulate=False, alpha=1.0, ws=None, tag="", split_ab=False):
-    """evx_gemm; split_ab: A and B are bf16 hi / lo planes (int16 tensors, x3, k-contiguous)."""
+def gemm_desc(M, N, K, A, sam, sak, B, sbk, sbn, Cm, ldc, precision="f32", bias=None, relu=False, mask=None,
+              ldm=0, mask_scale=1.0, gate=None, ldg=0, accumulate=False, alpha=1.0, ws=None, tag="", split_ab=False):
+    """The descriptor of an evx_gemm call, its workspace attached (gemm's arguments)."""
     d = evx_gemm_desc(M=M, N=N, K=K, precision=PREC[precision],
                       flags=(RELU if relu else 0) | (ACCUM if accumulate else 0) | (SPLIT_AB if split_ab else 0),
                       alpha=alpha, A=_p(A), sam=sam, sak=sak, B=_p(B), sbk=sbk, sbn=sbn, C=_p(Cm), ldc=ldc,
                       bias=_p(bias), mask=_p(mask), ldm=ldm, mask_scale=mask_scale, gate=_p(gate), ldg=ldg)
     _attach_ws(d, ws, tag, Cm.device)
-    check(lib().evx_gemm(C.byref(d), _stream()), "evx_gemm")
+    return d
 
 
-def conv_gemm(mode, M, N, K, A, B, Cm, cs, sam=0, sak=0, sbk=0, sbn=0, bias=None, relu=False, gate=None,
+def gemm(*args, **kw):
+    """evx_gemm (gemm_desc's arguments); split_ab: A and B are bf16 hi / lo planes (int16 tensors, x3,
+    k-contiguous)."""
+    check(lib().evx_gemm(C.byref(gemm_desc(*args, **kw)), _stream()), "evx_gemm")
+
+
+def conv_desc(mode, M, N, K, A, B, Cm, cs, sam=0, sak=0, sbk=0, sbn=0, bias=None, relu=False, gate=None,
               ldg=0, ws=None, tag="", out_split=False):
-    """evx_conv3x3_gemm (x3): implicit-GEMM 3x3 conv forward / dX / dW on pixel-major activations.
-    out_split: the output as bf16 hi / lo planes (Cm int16 [2][M][N]; the LDS-staged forward)."""
+    """The descriptor of an evx_conv3x3_gemm call, its workspace attached (conv_gemm's arguments)."""
     d = evx_gemm_desc(M=M, N=N, K=K, precision=PREC["x3"], flags=(RELU if relu else 0) | (OUT_SPLIT if out_split else 0),
                       alpha=1.0, A=_p(A),
                       sam=sam, sak=sak, B=_p(B), sbk=sbk, sbn=sbn, C=_p(Cm), ldc=N, bias=_p(bias), mask=None,
                       ldm=0, mask_scale=1.0, gate=_p(gate), ldg=ldg)
     _attach_ws(d, ws, tag + f"cv{mode}_", Cm.device, conv=(mode, cs))
+    return d
+
+
+def conv_gemm(mode, M, N, K, A, B, Cm, cs, **kw):
+    """evx_conv3x3_gemm (x3): implicit-GEMM 3x3 conv forward / dX / dW on pixel-major activations
+    (conv_desc's arguments). out_split: the output as bf16 hi / lo planes (Cm int16 [2][M][N]; the
+    LDS-staged forward)."""
+    d = conv_desc(mode, M, N, K, A, B, Cm, cs, **kw)
     check(lib().evx_conv3x3_gemm(C.byref(d), mode, cs, _stream()), "evx_conv3x3_gemm")
+
+
+def gemm_plan(d, mode=0, cs=0):
+    """evx_gemm_plan_query: the kernel route, K slices, slice length and reduction the launcher would
+    take for descriptor d (mode 0: evx_gemm; CONV_*: evx_conv3x3_gemm(mode, cs)). Host only."""
+    p = evx_gemm_plan()
+    check(lib().evx_gemm_plan_query(C.byref(d), mode, cs, C.byref(p)), "evx_gemm_plan_query")
+    return p
 
 
 def colsum(X, M, N, out, scratch):

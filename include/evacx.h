@@ -260,6 +260,43 @@ int evx_conv3x3_gemm(const evx_gemm_desc *g, int32_t mode, int32_t cs, void *str
    weights there as bf16 hi / lo MFMA fragments; otherwise the split-K partials of
    evx_gemm_ws_elems. Without it the call runs the generic implicit-GEMM kernel. */
 int64_t evx_conv3x3_ws_elems(const evx_gemm_desc *g, int32_t mode, int32_t cs);
+
+/* The kernel a descriptor runs on (evx_gemm_plan.route): one constant per kernel or template
+ * instantiation the launcher can pick. The choice depends on the precision, the strides, the
+ * sizes' divisibility by 4 / 8, the operands' 16-byte alignment, K >= 256 and the workspace. */
+#define EVX_ROUTE_NONE 0              /* M, N or K <= 0: nothing is launched */
+#define EVX_ROUTE_GEMM128_F32 1       /* gemm128_kernel<float>: exact f32 */
+#define EVX_ROUTE_GEMM128_BF16 2      /* gemm128_kernel<__bf16> */
+#define EVX_ROUTE_X3_VEC_AB 3         /* gemm128x3_kernel, A and B staged from 16-B loads along k */
+#define EVX_ROUTE_X3_VEC_A 4          /* gemm128x3_kernel, A only from 16-B loads */
+#define EVX_ROUTE_X3_VEC_B 5          /* gemm128x3_kernel, B only from 16-B loads */
+#define EVX_ROUTE_X3_SCALAR 6         /* gemm128x3_kernel, one element per load */
+#define EVX_ROUTE_X3_SPLIT_AB 7       /* gemm128x3_kernel on pre-split planes (EVX_GEMM_SPLIT_AB) */
+#define EVX_ROUTE_TN3_KMAJOR 8        /* tn3_kernel: A[k][m], B[k][n] */
+#define EVX_ROUTE_TN3_AK 9            /* tn3_kernel: A[m][k] k-contiguous, B[k][n] */
+#define EVX_ROUTE_TN3_CONV_DW 10      /* tn3_kernel gathering the conv input (EVX_CONV_DW) */
+#define EVX_ROUTE_X3_CONV_FWD 11      /* gemm128x3_kernel gathering the taps: forward */
+#define EVX_ROUTE_X3_CONV_DX 12       /* gemm128x3_kernel gathering the taps: dX */
+#define EVX_ROUTE_X3_CONV_DW 13       /* gemm128x3_kernel gathering the taps: dW */
+#define EVX_ROUTE_CONV_LDS16_FWD 14   /* conv3x3_x3_kernel<16, 1>: <= 16 -> 32 channels */
+#define EVX_ROUTE_CONV_WREG32_FWD 15  /* conv3x3_wreg_kernel<32, ...>: 32 -> 64 channels */
+#define EVX_ROUTE_CONV_LDS64_FWD 16   /* conv3x3_x3_kernel<64, 4>: 64 -> 128 channels */
+#define EVX_ROUTE_CONV_LDS64_DX 17    /* conv3x3_x3_kernel<64, 1, dX>: dY 64 -> dX 32 channels */
+#define EVX_ROUTE_CONV_LDS128_DX 18   /* conv3x3_x3_kernel<128, 2, dX>: dY 128 -> dX 64 channels */
+#define EVX_REDUCE_NONE 0
+#define EVX_REDUCE_GENERIC 1          /* splitk_reduce_kernel */
+#define EVX_REDUCE_QUARTERS 2         /* splitk_reduce4_kernel: >= 8 slices, M*N a multiple of 4 */
+typedef struct {
+    int32_t route;   /* EVX_ROUTE_* */
+    int32_t slices;  /* K slices (gridDim.z); 1: one pass */
+    int32_t klen;    /* K rows per slice (a multiple of 32) */
+    int32_t reduce;  /* EVX_REDUCE_* */
+} evx_gemm_plan;
+/* What evx_gemm (mode 0) or evx_conv3x3_gemm(mode = EVX_CONV_*, cs) would launch for g: decided on
+ * the host by the function the launcher itself switches on -- no launch, no device call (the
+ * pointers are only tested for NULL and alignment). An argument error the call would report before
+ * launching comes back as the same negative code with the same evx_q_last_error text. */
+int evx_gemm_plan_query(const evx_gemm_desc *g, int32_t mode, int32_t cs, evx_gemm_plan *out);
 /* out[n] (+)= sum_m X[m*ld+n] (bias gradients), fixed summation order */
 int evx_colsum(const float *X, int64_t ld, int32_t M, int32_t N, float *out, int32_t accum, float *scratch,
                int32_t scratch_elems, void *stream);

@@ -172,7 +172,10 @@ def test_dropout_mask_rate():
 def test_conv3x3_implicit_gemm_vs_torch(cin, cout, B):
     """evx_conv3x3_gemm forward / dX (with the ReLU gate of the layer below) / dW against torch's
     conv2d and autograd in float64 (the same 3x3 padding-1 conv as DQNNetwork's, dqn_agent.py:22-24).
-    x3 precision: error ~2^-17 of the sum of |products| -> atol scales with the tensor."""
+    x3 precision: error ~2^-17 of the sum of |products| -> atol scales with the tensor.
+    No workspace is passed, so this covers the gathering fallback (gemm128x3_kernel<CV_FWD / CV_DX>,
+    and for dW tn3_kernel or gemm128x3_kernel<CV_DW>), not the LDS-staged kernels QNet runs: those
+    are in test_gemm_routes_gpu.py."""
     _need_gpu()
     from evacx import qnet
     g = torch.Generator().manual_seed(cin * 100 + cout)
