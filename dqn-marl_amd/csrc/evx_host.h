@@ -50,6 +50,10 @@ inline int hip_status(const char* what, hipError_t e = hipGetLastError()) {
     return -5;
 }
 
+// 256-row blocks of the TD loss per net (td_loss_kernel: one loss partial each), as td_launch
+// launches them, evx_td_loss_ws_floats sizes them and evx_qmlp_group_plan reports them.
+inline int td_blocks(int B) { return (B + 255) / 256; }
+
 // Compute units of the current device (cached per device; 256 if the query fails).
 inline int cu_count() {
     static std::atomic<int> ncu[64];

@@ -2893,13 +2893,18 @@ static int make_fwd(const evx_layout* lay, const evx_obs* obs, int32_t n, const 
     return 0;
 }
 
+// The launch shape of the grouped learn chain at B rows per net, `pairs` forward problems per net
+// and `nets` nets (defined below, next to the split rules): the one decision launch_fwd's grouped
+// branch, qmlp_backward and launch_tail take theirs from, handed out by evx_qmlp_group_plan.
+static evx_qmlp_plan chain_plan(int32_t B, int nets, int pairs, bool x3);
+
 static int launch_fwd(const evxm::Fwd& a0, const evxm::Fwd& a1, int32_t n, int pairs, bool fc23, hipStream_t st,
                       bool x3 = false, int nets = 1) {
     const unsigned blocks = (unsigned)((n + evxm::RM - 1) / evxm::RM);
     const unsigned big = (unsigned)((n + 127) / 128);
     if (nets > 1) {  // grouped (x3 only): blockIdx.z = net * pairs + problem
         const unsigned z = (unsigned)(pairs * nets);
-        if (big * z >= 384)
+        if (chain_plan(n, nets, pairs, true).fc1_rows == 128)
             hipLaunchKernelGGL((evxm::qfc1_kernel<4, 1, 8, true, true>), dim3(big, 2, z), dim3(512), 0, st, a0, a1, pairs);
         else
             hipLaunchKernelGGL((evxm::qfc1_kernel<2, 1, 4, true, true>), dim3(blocks, 4, z), dim3(256), 0, st, a0, a1, pairs);
@@ -3191,6 +3196,27 @@ static int ksplit_kper(int B, int tiles, int slots, int minrows) {
 static int dw2_kper(int B) { return ksplit_kper(B, 8, 256, 256); }
 // (B <= 4096: one split per 256 rows -- 16 at cfg2's B = 4096, 160 -> 320 workgroups)
 static int dw1_kper(int B, bool x3) { return ksplit_kper(B, x3 ? 20 : 16, 512, B <= 4096 ? 256 : 1024); }
+static evx_qmlp_plan chain_plan(int32_t B, int nets, int pairs, bool x3) {
+    evx_qmlp_plan p;
+    // fc1: 128-row tiles once they fill the chip (384 tiles over the problems of every net), else 64-row
+    p.fc1_rows = (unsigned)((B + 127) / 128) * (unsigned)(pairs * nets) >= 384 ? 128 : evxm::RM;
+    p.qbwd3_rows = evxm::qbwd3_rows(B);
+    p.dw1_kper = dw1_kper(B, x3);
+    p.dw1_gz = (B + p.dw1_kper - 1) / p.dw1_kper;
+    p.dw2_kper = dw2_kper(B);
+    p.dw2_gz = (B + p.dw2_kper - 1) / p.dw2_kper;
+    p.qdz1_tiles = evxm::qdz1_tiles_per_wg(B);
+    p.td_blocks = evxh::td_blocks(B);
+    return p;
+}
+int evx_qmlp_group_plan(int32_t B, int32_t nets, evx_qmlp_plan* out) {
+    if (!out) return fail(-22, "qmlp_group_plan: NULL plan");
+    *out = evx_qmlp_plan{};
+    if (nets < 1 || nets > 1024) return fail(-22, "qmlp_group_plan: nets must be 1..1024");
+    if (B <= 0) return fail(-22, "qmlp_group_plan: B must be > 0");
+    *out = chain_plan(B, nets, 2, true);  // the forward pair (online + target), x3 operands
+    return 0;
+}
 static int qbwd3_blocks(int B) { return (B + evxm::qbwd3_rows(B) - 1) / evxm::qbwd3_rows(B); }
 static int qdz1_wgx(int B) {
     const int qrt = evxm::qdz1_tiles_per_wg(B);
@@ -3228,14 +3254,15 @@ template <bool X3, int AP2, int BP2, int AP1, int BP1>
 static void launch_tail(const evxm::Bwd& a, int32_t B, const evx_qmlp_grads* g, float* ss, hipStream_t st,
                         int nets, int acc, float* loss) {
     // dW2 = dZ2^T H1 (256 x 512); dW1 = dZ1^T X (512 x compact K -> 726); K = B split into S tiles
-    evxm::GemmTN g2{a.dz2, evxm::HID2, a.h1, evxm::HID, B, evxm::HID2, evxm::HID, dw2_kper(B), g->w2, evxm::HID, 0,
+    const evx_qmlp_plan pl = chain_plan(B, nets, 2, X3);
+    evxm::GemmTN g2{a.dz2, evxm::HID2, a.h1, evxm::HID, B, evxm::HID2, evxm::HID, pl.dw2_kper, g->w2, evxm::HID, 0,
                     g->part, X3 ? a.dz2l : nullptr, X3 ? a.h1l : nullptr, evxm::HID / evxm::TT, evxm::HID2 / evxm::TT, 0};
-    g2.gz = (B + g2.kper - 1) / g2.kper;
+    g2.gz = pl.dw2_gz;
     const int KX = X3 ? evxm::K1X : evxm::K1P;
     evxm::GemmTN g1{a.dz1, evxm::HID, a.x, KX, B, evxm::HID, X3 ? evxm::K1X : 4 * evxm::NCELL,
-                    dw1_kper(B, X3), g->w1, evxm::K1, X3 ? 3 : 1, g->part + part2_floats(B),
+                    pl.dw1_kper, g->w1, evxm::K1, X3 ? 3 : 1, g->part + part2_floats(B),
                     X3 ? a.dz1l : nullptr, nullptr, KX / evxm::TT, evxm::HID / evxm::TT, 0};
-    g1.gz = (B + g1.kper - 1) / g1.kper;
+    g1.gz = pl.dw1_gz;
     const int ndzx = qdz1_wgx(B);
     const int64_t pf = evx_qmlp_backward_part_floats(B);
     evxm::Red2 r{g->part, g2.gz, g1.part, g1.gz, g1.gx * evxm::TT, 4 * evxm::NCELL, X3 ? 3 : 1,
@@ -3305,7 +3332,7 @@ static int qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, c
     if (!g->part) return fail(-22, "qmlp_backward: g->part required (evx_qmlp_backward_part_floats(B) floats)");
     if (B <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int rb3 = evxm::qbwd3_rows(B);
+    const int rb3 = chain_plan(B, nets, 2, p->x3 != 0).qbwd3_rows;
     const int acc = zero_grads ? 0 : 1;
     evxm::Bwd a;
     a.B = B;

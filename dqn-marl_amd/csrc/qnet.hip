@@ -1901,7 +1901,7 @@ int evx_colsum(const float* X, int64_t ld, int32_t M, int32_t N, float* out, int
 
 int64_t evx_td_loss_ws_floats(int32_t B, int32_t nets) {
     if (B <= 0 || nets < 1) return 0;
-    return (int64_t)((B + 255) / 256) * nets;
+    return (int64_t)evxh::td_blocks(B) * nets;
 }
 
 static int td_launch(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew,
@@ -1915,7 +1915,7 @@ static int td_launch(const float* Q, const float* Qt, int32_t A, const int32_t* 
     if (B <= 0) return 0;
     if (nets < 1 || nets > 65535) return fail(-22, "td_loss: nets must be 1..65535");
     if (!Q || !Qt || !act || !rew || !done || !dQ || !loss) return fail(-22, "td_loss: NULL argument");
-    const int ntd = (B + 255) / 256;
+    const int ntd = evxh::td_blocks(B);
     if (!ws || ws_floats < (int64_t)ntd * nets) return fail(-22, "td_loss: workspace smaller than evx_td_loss_ws_floats");
     const int nz = zero && nzero > 0 ? (int)std::min<int64_t>((nzero + 256 * 16 - 1) / (256 * 16), 512) : 0;
     hipStream_t st = (hipStream_t)stream;

@@ -124,6 +124,12 @@ class evx_td_opts(C.Structure):
     _fields_ = [("sel", C.c_void_p), ("huber_delta", C.c_float), ("gamma_row", C.c_void_p)]
 
 
+class evx_qmlp_plan(C.Structure):
+    """The grouped learn chain's launch shape at B rows per net (evx_qmlp_group_plan)."""
+    _fields_ = [(n, C.c_int32) for n in ["fc1_rows", "qbwd3_rows", "dw1_kper", "dw1_gz", "dw2_kper", "dw2_gz",
+                                        "qdz1_tiles", "td_blocks"]]
+
+
 class evx_episodes(C.Structure):
     _fields_ = [("E", C.c_int32), ("tab_slots", C.c_int32)] + \
         _ptrs("ret", "len", "w_n", "w_len", "w_evac", "w_dead", "w_ret", "w_ret2", "w_min", "w_max", "last_ret",
@@ -234,6 +240,7 @@ SIGNATURES = {
     "evx_qmlp_polyak_pack3": (C.c_int, [_vp, _vp, _f32, _f32] + [_vp] * 10),
     "evx_qmlp_backward_ss_g": (C.c_int, [_PAR, _i32, _i32] + [_vp] * 4 + [_f32, _vp, _vp, _GRADS, _vp, _vp]),
     "evx_qmlp_adam_pack3_g": (C.c_int, [_vp] * 4 + [_f32, _P(evx_adam)] + [_vp] * 10 + [_i32, _vp, _i32, _vp]),
+    "evx_qmlp_group_plan": (C.c_int, [_i32, _i32, _P(evx_qmlp_plan)]),
     "evx_qmix_nparams": (C.c_int32, [_i32]),
     "evx_qmix_part_floats": (C.c_int64, [_i32, _i32]),
     "evx_qmix_loss": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32, _i32] + [_vp] * 7 + [_i64, _vp]),

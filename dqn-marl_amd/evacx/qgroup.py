@@ -12,7 +12,10 @@ Adam moments, MFMA operand copies, activations -- is one slice of a [G][...] arr
   buffers) uses net g -- one launch for all robots of all envs.
 * ``GroupedLearner.learn_obs``: net g learns on rows [g B, (g + 1) B) of the sampled batch
   (its own transitions): forward pair, TD loss, backward and clip + Adam, each one launch
-  for all nets; per-net results equal G separate ``evacx.qnet.Learner`` steps bit for bit.
+  for all nets; per-net gradients, norms, parameters, Adam moments and operand copies equal G
+  separate ``evacx.qnet.Learner`` steps bit for bit. The reported loss agrees to the last f32 ulps
+  only: evx_td_loss_zero_g adds a net's squared errors per 256-row block in a tree, the single
+  net's TD step (inside its backward's first kernel) per 16- to 128-row block in row order.
 * ``GroupedQMix``: the QMIX learn step -- the agents' forwards, the mixer's loss and backward
   in one kernel (evx_qmix_loss: dQ of every agent at its taken action), the agents' grouped
   backward and per-agent clip + Adam, the mixer's clip_grad_norm_ + Adam.
@@ -24,7 +27,7 @@ from typing import List, Optional
 
 import torch
 
-from ._lib import check, evx_adam, evx_qmlp_fwd_out, evx_qmlp_grads, lib
+from ._lib import check, evx_adam, evx_qmlp_fwd_out, evx_qmlp_grads, evx_qmlp_plan, lib
 from .env import _stream
 from .qmlp import HID, HID2, K1X, NACT, MLPFast, _need
 from .qnet import DROPOUT_P, FlatParams, layer_specs, param_shapes
@@ -32,6 +35,15 @@ from .qnet import DROPOUT_P, FlatParams, layer_specs, param_shapes
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+def group_plan(B: int, nets: int) -> evx_qmlp_plan:
+    """evx_qmlp_group_plan: the launch shape the grouped learn chain takes at B rows per net (fc1_rows,
+    qbwd3_rows, dw1_kper / dw1_gz, dw2_kper / dw2_gz, qdz1_tiles, td_blocks), from the launchers' own
+    decision function; no launch, no device call."""
+    p = evx_qmlp_plan()
+    check(lib().evx_qmlp_group_plan(B, nets, C.byref(p)), "evx_qmlp_group_plan")
+    return p
 
 
 class GroupedMLP:

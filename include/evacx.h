@@ -694,6 +694,23 @@ int evx_qmlp_adam_pack3_g(float *p, float *g, float *m, float *v, float max_norm
                           uint16_t *w1l, float *b1c, uint16_t *w2b, uint16_t *w2l, uint16_t *w2t, uint16_t *w2tl,
                           uint16_t *w1o, uint16_t *w1ol, const float *ss, int32_t nss, float *norm_out, int32_t nets,
                           void *stream);
+/* The launch shape of the grouped x3 learn chain (evx_qmlp_forward2_g, evx_td_loss_zero_g,
+ * evx_qmlp_backward_ss_g) at B rows per net: every figure depends on B and nets alone. */
+typedef struct {
+    int32_t fc1_rows;    /* rows per qfc1 tile of the forward pair: 64 (qfc1_kernel<2, 1, 4>) or 128
+                            (qfc1_kernel<4, 1, 8>, from 384 tiles x problems x nets) */
+    int32_t qbwd3_rows;  /* rows per qbwd3 block: 32, 16, 64 or 128 */
+    int32_t dw1_kper;    /* rows per K split of dW1 = dZ1^T X (a multiple of 64) */
+    int32_t dw1_gz;      /* its splits per net = ceil(B / dw1_kper): the last may be short */
+    int32_t dw2_kper;    /* the same of dW2 = dZ2^T H1 */
+    int32_t dw2_gz;
+    int32_t qdz1_tiles;  /* 64-row dZ1 tiles per workgroup */
+    int32_t td_blocks;   /* 256-row TD-loss blocks (partials) per net */
+} evx_qmlp_plan;
+/* Decided on the host by the function the chain's launchers themselves call: no launch, no device
+ * call. nets = 1: the backward figures are those of the single-net x3 backward
+ * (evx_qmlp_backward_ss, evx_qmlp_td_backward_ss). -22 for nets outside 1..1024, B <= 0 or out = NULL. */
+int evx_qmlp_group_plan(int32_t B, int32_t nets, evx_qmlp_plan *out);
 
 /* ---- QMIX mixer (runners/train_qmix.py:39-54 MixingNetwork, loss :78-104) for n <= 16 agents:
  * Q / Qt [n][B][A] (evx_qmlp_forward2_g), act [n][B], rew / done [B]; mix / mix_t the online /
