@@ -2791,30 +2791,24 @@ int evx_qmlp_pack3(const float* w1, const float* b1, const float* w2, uint16_t* 
     return hip_status("qmlp_pack3");
 }
 
-// the x3 act kernel for the dropout mode of a (fc1_slab_m)
-// SAVE: the learner's online forward (no row permutation; X from x_expand_kernel)
-extern "C++" template <bool GR, bool SAVE = false>
-static void launch_act3(const evxm::Fwd& a, int32_t n, int nets, hipStream_t st) {
-    {
-        static std::atomic<uint64_t> attr_done;
-        const void* kh[3] = {(const void*)evxm::qact3h_kernel<GR, 0, SAVE>, (const void*)evxm::qact3h_kernel<GR, 1, SAVE>,
-                             (const void*)evxm::qact3h_kernel<GR, 2, SAVE>};
-        evxh::max_lds_once(attr_done, kh, 3, evxm::ACT3H_LDS);
-    }
-    const dim3 grid((unsigned)((n + 63) / 64), (unsigned)nets);
-    if (a.drop_mask)
-        hipLaunchKernelGGL((evxm::qact3h_kernel<GR, 2, SAVE>), grid, dim3(256), evxm::ACT3H_LDS, st, a);
-    else if (a.drop_thresh)
-        hipLaunchKernelGGL((evxm::qact3h_kernel<GR, 1, SAVE>), grid, dim3(256), evxm::ACT3H_LDS, st, a);
-    else
-        hipLaunchKernelGGL((evxm::qact3h_kernel<GR, 0, SAVE>), grid, dim3(256), evxm::ACT3H_LDS, st, a);
-}
+}  // extern "C"
 
+// ------------------------------------------------ forwards and acts: record (make_fwd), plan, launch
+// what a Fwd record is built for
+enum FwdMode {
+    FM_FULL,  // a forward that writes H1 (and X / H2 / Q / actions where given)
+    FM_ACT,   // a fused act: H1, X and H2 stay on chip
+    FM_RAW    // fc1's pre-activation table (evx_qmlp_stat / _stat_x): no table path, no permutation
+};
+
+// gn (FM_ACT): nets of a grouped act, 0 for one net; raw / xin (FM_RAW): the table, and its rows' X or NULL
 static int make_fwd(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
-                    const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, evxm::Fwd& a) {
+                    const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, evxm::Fwd& a, FwdMode mode = FM_FULL,
+                    int gn = 0, float* raw = nullptr, const uint16_t* xin = nullptr) {
+    const bool full = mode == FM_FULL;
     if (!lay || !obs || !p || !out) return fail(-22, "qmlp_forward: NULL argument");
     if (!p->w1 || !p->b1c || !p->w2 || !p->b2 || !p->w3 || !p->b3) return fail(-22, "qmlp_forward: missing parameter");
-    if (!out->h1) return fail(-22, "qmlp_forward: h1 buffer required");
+    if (full && !out->h1) return fail(-22, "qmlp_forward: h1 buffer required");
     if (!lay->danger_o32 || !lay->cellinfo || !lay->obs_feat)
         return fail(-22, "qmlp_forward: layout tables missing (obs_feat)");
     a.N = n;
@@ -2846,9 +2840,9 @@ static int make_fwd(const evx_layout* lay, const evx_obs* obs, int32_t n, const 
     a.drop_thresh = dp > 0.f ? (uint32_t)((double)dp * 65536.0) : 0u;  // 16-bit uniforms
     if (dp > 0.f && a.drop_thresh == 0u) a.drop_thresh = 1u;
     a.drop_scale = dp > 0.f ? 1.f / (1.f - dp) : 1.f;
-    a.h1 = reinterpret_cast<__bf16*>(out->h1);
-    a.x = reinterpret_cast<__bf16*>(out->x);
-    a.h2 = out->h2;
+    a.h1 = full ? reinterpret_cast<__bf16*>(out->h1) : nullptr;
+    a.x = full ? reinterpret_cast<__bf16*>(out->x) : nullptr;
+    a.h2 = full ? out->h2 : nullptr;
     a.q = out->q;
     a.actions = out->actions;
     a.epsilon = out->epsilon;
@@ -2861,9 +2855,9 @@ static int make_fwd(const evx_layout* lay, const evx_obs* obs, int32_t n, const 
     a.stat_nx = p->stat_nx > 0 ? p->stat_nx : lay->L + 2;
     if (a.stat && (a.stat_x0 < 0 || a.stat_x0 + a.stat_nx > lay->L + 2))
         return fail(-22, "qmlp: the table's centre range must lie in [0, L + 2)");
-    a.raw = nullptr;
-    a.rest_ws = nullptr;
-    a.xin = nullptr;
+    a.raw = raw;
+    a.rest_ws = (mode == FM_ACT && !gn) ? out->act_ws : nullptr;
+    a.xin = reinterpret_cast<const __bf16*>(xin);
     a.xtab = (p->x3 && a.stat) ? reinterpret_cast<const __bf16*>(p->stat_xin) : nullptr;
     a.drop_mask = drop ? drop->mask : nullptr;
     if (a.drop_mask && !(dp > 0.f)) return fail(-22, "qmlp_forward: an explicit dropout mask needs p > 0 (its scale)");
@@ -2886,70 +2880,455 @@ static int make_fwd(const evx_layout* lay, const evx_obs* obs, int32_t n, const 
     }
     a.perm = out->perm;
     a.rpe = out->rows_per_env > 0 ? out->rows_per_env : 1;
-    a.gn = 0;
+    a.gn = gn;
     a.g = 0;
     // rows_per_env even: dropout row pairs stay together in a tile
     if (a.perm && (a.rpe & 1)) return fail(-22, "qmlp_forward: rows_per_env must be even (dropout row pairs)");
+    if (mode == FM_RAW) a.stat = nullptr;  // (after its range check: a table being rebuilt is still attached)
     return 0;
 }
 
-// The launch shape of the grouped learn chain at B rows per net, `pairs` forward problems per net
-// and `nets` nets (defined below, next to the split rules): the one decision launch_fwd's grouped
-// branch, qmlp_backward and launch_tail take theirs from, handed out by evx_qmlp_group_plan.
-static evx_qmlp_plan chain_plan(int32_t B, int nets, int pairs, bool x3);
-
-static int launch_fwd(const evxm::Fwd& a0, const evxm::Fwd& a1, int32_t n, int pairs, bool fc23, hipStream_t st,
-                      bool x3 = false, int nets = 1) {
-    const unsigned blocks = (unsigned)((n + evxm::RM - 1) / evxm::RM);
-    const unsigned big = (unsigned)((n + 127) / 128);
-    if (nets > 1) {  // grouped (x3 only): blockIdx.z = net * pairs + problem
-        const unsigned z = (unsigned)(pairs * nets);
-        if (chain_plan(n, nets, pairs, true).fc1_rows == 128)
-            hipLaunchKernelGGL((evxm::qfc1_kernel<4, 1, 8, true, true>), dim3(big, 2, z), dim3(512), 0, st, a0, a1, pairs);
-        else
-            hipLaunchKernelGGL((evxm::qfc1_kernel<2, 1, 4, true, true>), dim3(blocks, 4, z), dim3(256), 0, st, a0, a1, pairs);
-        int rc = hip_status("qfc1 grouped");
-        if (rc || !fc23) return rc;
-        hipLaunchKernelGGL((evxm::qfc23_kernel<true, true>), dim3(blocks, 1, z), dim3(256), 0, st, a0, a1, pairs);
-        return hip_status("qfc23 grouped");
+// the dropout instantiation of a record: 0 none, 1 the hash, 2 an explicit mask
+static int drop_mode(const evxm::Fwd& a) { return a.drop_mask ? 2 : a.drop_thresh ? 1 : 0; }
+// f(std::integral_constant<int, dm>): the runtime mode as a template argument
+template <class F>
+static void with_drop_mode(int dm, F&& f) {
+    switch (dm) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        default: return f(std::integral_constant<int, 0>{});
     }
-    if (x3) {  // f32-accurate: 128 x 256 tiles for large batches (register budget), else 64 x 128
-        // one problem (the learner's online forward beside the target through the fused act):
-        // 64 x 256 tiles at any batch (learn 391 -> 382 us at B = 32768 vs 128 x 256)
-        if (pairs == 1 && fc23)
-            hipLaunchKernelGGL((evxm::qfc1_kernel<2, 2, 4, true>), dim3(blocks, 2, pairs), dim3(256), 0, st, a0, a1, pairs);
-        else if (big * pairs >= 384)
-            hipLaunchKernelGGL((evxm::qfc1_kernel<4, 1, 8, true>), dim3(big, 2, pairs), dim3(512), 0, st, a0, a1, pairs);
-        else
-            hipLaunchKernelGGL((evxm::qfc1_kernel<2, 1, 4, true>), dim3(blocks, 4, pairs), dim3(256), 0, st, a0, a1, pairs);
-        int rc = hip_status("qfc1");
-        if (rc || !fc23) return rc;
-        // 32-row tiles while 64-row ones would leave CUs without a workgroup (cfg2's B = 4096: learn
-        // 0.133 -> 0.128 ms; fc1 in 32 x 64 tiles of 2 waves for small problems measured slower)
-        if ((int64_t)blocks * pairs < 256)
-            hipLaunchKernelGGL((evxm::qfc23_kernel<true, false, 1>), dim3((n + 31) / 32, 1, pairs), dim3(256), 0, st, a0, a1,
-                               pairs);
-        else
-            hipLaunchKernelGGL(evxm::qfc23_kernel<true>, dim3(blocks, 1, pairs), dim3(256), 0, st, a0, a1, pairs);
-        return hip_status("qfc23");
-    }
-    if (big * pairs >= 384)  // enough 128-row tiles (all 512 columns each) to fill the chip
-        hipLaunchKernelGGL((evxm::qfc1_kernel<4, 2, 8>), dim3(big, 1, pairs), dim3(512), 0, st, a0, a1, pairs);
-    else
-        hipLaunchKernelGGL((evxm::qfc1_kernel<2, 1, 4>), dim3(blocks, 4, pairs), dim3(256), 0, st, a0, a1, pairs);
-    int rc = hip_status("qfc1");
-    if (rc || !fc23) return rc;
-    hipLaunchKernelGGL(evxm::qfc23_kernel<false>, dim3(blocks, 1, pairs), dim3(256), 0, st, a0, a1, pairs);
-    return hip_status("qfc23");
 }
+
+// The dynamic-LDS limits of the act kernels, raised once per device before the first launch of any of them
+static void raise_lds_limits() {
+    using namespace evxm;
+    auto k = [](auto kernel) { return (const void*)kernel; };
+    static std::atomic<uint64_t> done3h, done3p, done1;
+    const void* k3h[14] = {
+        k(qact3h_kernel<false, 0>),       k(qact3h_kernel<false, 1>),       k(qact3h_kernel<false, 2>),
+        k(qact3h_kernel<false, 0, true>), k(qact3h_kernel<false, 1, true>), k(qact3h_kernel<false, 2, true>),
+        k(qact3h_kernel<true, 0>),        k(qact3h_kernel<true, 1>),        k(qact3h_kernel<true, 2>),
+        k(qfwd2_kernel<0>), k(qfwd2_kernel<1>), k(qfwd2_kernel<2>), k(qact3h_rest_kernel<0>), k(qact3h_rest_kernel<1>)};
+    const void *k3p[2] = {k(qact3p_kernel<0>), k(qact3p_kernel<1>)}, *k1[1] = {k(qact_kernel)};
+    evxh::max_lds_once(done3h, k3h, 14, ACT3H_LDS);
+    evxh::max_lds_once(done3p, k3p, 2, ACT3P_LDS);
+    evxh::max_lds_once(done1, k1, 1, ACT_LDS);
+}
+
+// fc1's rows per tile: 128 once such tiles over every problem fill the chip (384 of them), else 64
+static int fc1_tile_rows(int32_t n, int problems) {
+    return (unsigned)((n + 127) / 128) * (unsigned)problems >= 384 ? 128 : evxm::RM;
+}
+
+// the entry point a plan is made for
+enum FwdEntry {
+    FE_FORWARD,   // qfc1 (+ qfc23) only: evx_qmlp_forward, _stat, _stat_x, _forward2_g
+    FE_FORWARD2,  // evx_qmlp_forward2: the learner's pair, which may go through the act kernels
+    FE_ACT,       // evx_qmlp_act, _act64
+    FE_ACT_G      // evx_qmlp_act_g
+};
+
+// The one decision of what a forward or act call launches: host arithmetic on the records as
+// make_fwd left them (a1 = a0 for one problem), no HIP call. launch_plan switches on the plan and the
+// two queries hand it out, so a test that asks for a route is asking the launcher.
+static evx_qmlp_fwd_plan fwd_plan(const evxm::Fwd& a0, const evxm::Fwd& a1, int32_t n, int pairs, int nets, bool x3,
+                                  bool fc23, FwdEntry entry, bool kernel64, int ncu) {
+    evx_qmlp_fwd_plan p{};
+    p.route = EVX_FWD_NONE;
+    if (n <= 0) return p;
+    const int blocks = (n + evxm::RM - 1) / evxm::RM, ntiles = (n + 127) / 128;
+    p.drop_mode = drop_mode(a0);
+    p.drop_mode1 = drop_mode(a1);
+    // qfc1 + qfc23 over pr problems per net
+    auto fc = [&](int route, int pr) {
+        p.route = route;
+        p.fc23_rows = fc23 ? 64 : 0;
+        if (a0.xin) {  // evx_qmlp_stat_x: the instantiation that reads X exists in this tile only
+            p.fc1_rows = 64, p.fc1_cols = 128;
+        } else if (route == EVX_FWD_FC_GROUPED) {
+            p.fc1_rows = fc1_tile_rows(n, pr * nets);
+            p.fc1_cols = p.fc1_rows == 128 ? 256 : 128;
+        } else if (x3 && pr == 1 && fc23) {
+            // one problem (the learner's online forward beside the target through the fused act):
+            // 64 x 256 tiles at any batch (learn 391 -> 382 us at B = 32768 vs 128 x 256)
+            p.fc1_rows = 64, p.fc1_cols = 256;
+        } else {
+            // 128-row tiles for large batches: x3 over 256 columns (register budget), bf16 over all 512
+            p.fc1_rows = fc1_tile_rows(n, pr);
+            p.fc1_cols = p.fc1_rows == 128 ? (x3 ? 256 : 512) : 128;
+        }
+        // single-net x3: 32-row fc23 tiles while 64-row ones would leave CUs without a workgroup (cfg2's
+        // B = 4096: learn 0.133 -> 0.128 ms; fc1 in 32 x 64 tiles of 2 waves for small problems measured slower)
+        if (fc23 && x3 && route == EVX_FWD_FC && (int64_t)blocks * pr < 256) p.fc23_rows = 32;
+    };
+    // the learner's online net can take the fused act kernel's table path: its own table (rebuilt after
+    // every update, so it matches the weights this forward reads) and every output the backward needs
+    const bool online_table = a0.stat && !a0.perm && !a0.actions && a0.x && a0.h1 && a0.h1l && a0.h2 && a0.q;
+    // the second problem is a target net: Q only, so its H1 / H2 can stay in LDS
+    const bool target_q = x3 && a1.q && !a1.h2 && !a1.actions && !a1.x;
+    switch (entry) {
+        case FE_FORWARD:
+            fc(nets > 1 ? EVX_FWD_FC_GROUPED : EVX_FWD_FC, pairs);
+            break;
+        case FE_FORWARD2:
+            if (target_q && n >= 8192 && n < 32768 && online_table && a1.stat && p.drop_mode == p.drop_mode1) {
+                // both forwards through the act tables in one launch (qfwd2_kernel), X by its own launch
+                p.route = EVX_FWD_PAIRED;
+                p.x_expand = 1;
+            } else if (target_q && n >= 32768) {
+                // the target through the fused act kernel (64-row tiles, two workgroups per CU) instead of
+                // qfc1 + qfc23 writing and re-reading both H1 planes -- at n >= 32768 only: a fused act
+                // workgroup lives ~65 us on the full path, so below a full round of workgroups the
+                // two-kernel forward wins (B = 4096: learn 187 vs 127 us). The target's own act table
+                // (rebuilt at each target sync; evacx.trainer attaches it to both nets): replay rows past
+                // the fire's last step start fc1 from it, the others run the full path per 64-row tile.
+                if (online_table) {
+                    // the online forward through the same kernel's table path, H1 planes / H2 / Q saved
+                    // for the backward, X expanded by its own launch -- instead of qfc1's K = 640
+                    // products over staged A tiles and qfc23 re-reading both H1 planes
+                    p.route = EVX_FWD_TARGET_ACT_TABLE;
+                    p.x_expand = 1;
+                } else {
+                    // (the online forward through the fused kernel on the full path with X saved measured
+                    // no faster than qfc1 + qfc23 at B = 32768: learn 0.420 vs 0.427 ms)
+                    fc(EVX_FWD_FC, 1);
+                    p.route = EVX_FWD_TARGET_ACT_FC;
+                }
+            } else {
+                fc(EVX_FWD_FC, 2);
+            }
+            break;
+        case FE_ACT:
+            // x3: the persistent 128-row kernel when its table path applies (a table attached, the hash
+            // or no dropout) and the launch has >= 4 tiles per CU (its cross-tile pipeline; with one tile
+            // per CU, cfg2's 32 768 rows, the 64-row kernel's two workgroups per CU measured faster:
+            // 16.1 vs 15.3 M env-steps/s); else (or kernel64) the 64-row kernel
+            if (!x3) {
+                p.route = EVX_FWD_ACT_BF16;
+            } else if (!kernel64 && a0.stat && !a0.drop_mask && ntiles >= 4 * ncu) {
+                // the table-path tiles on the persistent kernel, then the others (if any) on the 64-row
+                // body (listed: one workgroup per CU over their halves; else every row re-checked)
+                p.route = EVX_FWD_ACT_PERSISTENT;
+                p.act_grid = std::min(ntiles, ncu);
+                p.rest_listed = a0.rest_ws != nullptr;
+                p.rest_grid = p.rest_listed ? std::min(2 * ntiles, ncu) : (n + 1023) / 1024;
+            } else {
+                p.route = EVX_FWD_ACT_64;
+            }
+            break;
+        case FE_ACT_G:
+            p.route = EVX_FWD_ACT_GROUPED;
+            break;
+    }
+    return p;
+}
+
+// one forward or act call between its checks and its launches
+struct FwdCall {
+    evxm::Fwd a0, a1;  // a1: the second problem of a pair
+    int pairs = 1, nets = 1;
+    bool x3 = false;
+    evx_qmlp_fwd_plan plan{};
+};
+
+static void launch_x_expand(const evxm::Fwd& a, int32_t n, hipStream_t st) {
+    const int64_t nx = (int64_t)n * 20;
+    hipLaunchKernelGGL(evxm::x_expand_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, a);
+}
+
+// the x3 act kernel on 64-row tiles; SAVE: the learner's online forward (no permutation; X from x_expand_kernel)
+template <bool GR, bool SAVE = false>
+static void launch_act3(const evxm::Fwd& a, int32_t n, int nets, int dm, hipStream_t st) {
+    const dim3 grid((unsigned)((n + 63) / 64), (unsigned)nets);
+    with_drop_mode(dm, [&](auto m) {
+        hipLaunchKernelGGL((evxm::qact3h_kernel<GR, decltype(m)::value, SAVE>), grid, dim3(256), evxm::ACT3H_LDS, st, a);
+    });
+}
+
+// qfc1 and (fc23_rows != 0) qfc23 in the plan's tiles over `pairs` problems of `nets` nets
+static int launch_fc(const evx_qmlp_fwd_plan& p, const evxm::Fwd& a0, const evxm::Fwd& a1, int32_t n, int pairs,
+                     int nets, bool x3, hipStream_t st) {
+    const bool grouped = p.route == EVX_FWD_FC_GROUPED, wide = p.fc1_rows == 128;
+    const unsigned z = (unsigned)(grouped ? pairs * nets : pairs);  // grouped: blockIdx.z = net * pairs + problem
+    const dim3 grid1((unsigned)((n + p.fc1_rows - 1) / p.fc1_rows), (unsigned)(evxm::HID / p.fc1_cols), z);
+    auto fc1 = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid1, dim3(wide ? 512 : 256), 0, st, a0, a1, pairs); };
+    if (a0.xin)  // (like x3, the operands' format is the record's, not a decision)
+        fc1(evxm::qfc1_kernel<2, 1, 4, true, false, true>);
+    else if (grouped)
+        wide ? fc1(evxm::qfc1_kernel<4, 1, 8, true, true>) : fc1(evxm::qfc1_kernel<2, 1, 4, true, true>);
+    else if (x3 && p.fc1_cols == 256 && !wide)
+        fc1(evxm::qfc1_kernel<2, 2, 4, true>);
+    else if (x3)
+        wide ? fc1(evxm::qfc1_kernel<4, 1, 8, true>) : fc1(evxm::qfc1_kernel<2, 1, 4, true>);
+    else
+        wide ? fc1(evxm::qfc1_kernel<4, 2, 8>) : fc1(evxm::qfc1_kernel<2, 1, 4>);
+    int rc = hip_status(a0.xin ? "qmlp_stat_x" : grouped ? "qfc1 grouped" : "qfc1");
+    if (rc || !p.fc23_rows) return rc;
+    const dim3 grid23((unsigned)((n + p.fc23_rows - 1) / p.fc23_rows), 1, z);
+    auto fc23 = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid23, dim3(256), 0, st, a0, a1, pairs); };
+    if (grouped)
+        fc23(evxm::qfc23_kernel<true, true>);
+    else if (x3)
+        p.fc23_rows == 32 ? fc23(evxm::qfc23_kernel<true, false, 1>) : fc23(evxm::qfc23_kernel<true>);
+    else
+        fc23(evxm::qfc23_kernel<false>);
+    return hip_status(grouped ? "qfc23 grouped" : "qfc23");
+}
+
+static int launch_plan(FwdCall& c, int32_t n, hipStream_t st) {
+    const evx_qmlp_fwd_plan& p = c.plan;
+    if (p.route == EVX_FWD_NONE) return 0;
+    evxm::Fwd &a0 = c.a0, &a1 = c.pairs == 1 ? c.a0 : c.a1;
+    const int ntiles = (n + 127) / 128;
+    if (p.route != EVX_FWD_FC && p.route != EVX_FWD_FC_GROUPED) raise_lds_limits();  // (qfc1 / qfc23: static LDS)
+    if (p.x_expand) launch_x_expand(a0, n, st);
+    switch (p.route) {
+        case EVX_FWD_FC:
+        case EVX_FWD_FC_GROUPED:
+            return launch_fc(p, a0, a1, n, c.pairs, c.nets, c.x3, st);
+        case EVX_FWD_PAIRED:
+        case EVX_FWD_TARGET_ACT_TABLE:
+        case EVX_FWD_TARGET_ACT_FC:
+            a1.perm = nullptr;  // the target as the act kernels take it: Q only, H1 in LDS
+            a1.actions = nullptr;
+            a1.h1 = a1.h1l = nullptr;
+            if (p.route == EVX_FWD_PAIRED) {
+                with_drop_mode(p.drop_mode, [&](auto m) {
+                    hipLaunchKernelGGL(evxm::qfwd2_kernel<decltype(m)::value>, dim3((unsigned)((n + 63) / 64), 2),
+                                       dim3(256), evxm::ACT3H_LDS, st, a0, a1);
+                });
+                return hip_status("qmlp_forward2 paired");
+            }
+            if (p.route == EVX_FWD_TARGET_ACT_TABLE)
+                launch_act3<false, true>(a0, n, 1, p.drop_mode, st);
+            else if (int rc = launch_fc(p, a0, a0, n, 1, 1, true, st))
+                return rc;
+            launch_act3<false>(a1, n, 1, p.drop_mode1, st);
+            return hip_status("qmlp_forward2 target act");
+        case EVX_FWD_ACT_GROUPED:
+            launch_act3<true>(a0, n, c.nets, p.drop_mode, st);
+            return hip_status("qact_g");
+        case EVX_FWD_ACT_BF16:
+            hipLaunchKernelGGL(evxm::qact_kernel, dim3((unsigned)ntiles), dim3(512), evxm::ACT_LDS, st, a0);
+            break;
+        case EVX_FWD_ACT_64:
+            launch_act3<false>(a0, n, 1, p.drop_mode, st);
+            break;
+        case EVX_FWD_ACT_PERSISTENT: {  // the hash or no dropout: there is no mask instantiation
+            auto persistent = [&](auto main, auto rest) {
+                hipLaunchKernelGGL(main, dim3((unsigned)p.act_grid), dim3(512), evxm::ACT3P_LDS, st, a0, ntiles);
+                hipLaunchKernelGGL(rest, dim3((unsigned)p.rest_grid), dim3(256), evxm::ACT3H_LDS, st, a0);
+            };
+            p.drop_mode ? persistent(evxm::qact3p_kernel<1>, evxm::qact3h_rest_kernel<1>)
+                        : persistent(evxm::qact3p_kernel<0>, evxm::qact3h_rest_kernel<0>);
+            break;
+        }
+        default:
+            return fail(-22, "qmlp: no kernel for the planned route");
+    }
+    return hip_status("qact");
+}
+
+// Grouped nets: every per-net buffer is an array [nets][one net's buffer], the
+// pointers passed are net 0's.
+static int group_check(int32_t nets, const evx_qmlp_params* p) {
+    if (nets < 1 || nets > 1024) return fail(-22, "grouped qmlp: nets must be 1..1024");
+    if (!p || !p->x3) return fail(-22, "grouped qmlp: x3 parameters required (the [nets] operand layout is x3's)");
+    return 0;
+}
+
+// evx_qmlp_forward2's checks, records and plan; pairs = 1: evx_qmlp_forward's (problem 0 alone);
+// grouped: evx_qmlp_forward2_g's over `nets` nets
+static int forward_prepare(const evx_layout* lay, int32_t n, const evx_obs* obs0, const evx_qmlp_params* p0,
+                           const evx_qmlp_dropout* drop0, const evx_qmlp_fwd_out* out0, const evx_obs* obs1,
+                           const evx_qmlp_params* p1, const evx_qmlp_dropout* drop1, const evx_qmlp_fwd_out* out1,
+                           int pairs, bool grouped, int32_t nets, FwdCall& c) {
+    c.plan = evx_qmlp_fwd_plan{};
+    if (grouped) {
+        int rc = group_check(nets, p0);
+        if (!rc) rc = group_check(nets, p1);
+        if (rc) return rc;
+    }
+    if (n <= 0) return 0;
+    if (grouped && (n & 1)) return fail(-22, "qmlp_forward2_g: rows per net must be even (dropout row pairs)");
+    auto wants_fc23 = [](const evx_qmlp_fwd_out* o) { return o->q || o->actions || o->h2; };
+    int rc = make_fwd(lay, obs0, n, p0, drop0, out0, c.a0);
+    if (pairs == 1) {
+        if (rc) return rc;
+        c.x3 = p0->x3 != 0;
+        c.plan = fwd_plan(c.a0, c.a0, n, 1, 1, c.x3, wants_fc23(out0), FE_FORWARD, false, 0);
+        return 0;
+    }
+    if (!rc) rc = make_fwd(lay, obs1, n, p1, drop1, out1, c.a1);
+    if (rc) return rc;
+    if (!grouped) {
+        if (!wants_fc23(out0) || !wants_fc23(out1))
+            return fail(-22, "qmlp_forward2: both problems need an fc2/fc3 output");
+        if ((p0->x3 != 0) != (p1->x3 != 0)) return fail(-22, "qmlp_forward2: both problems in one precision");
+    } else {
+        if (c.a0.stat || c.a1.stat || c.a0.perm || c.a1.perm)
+            return fail(-22, "qmlp_forward2_g: no table path / permutation");
+        if (!(out0->q || out0->h2) || !(out1->q || out1->h2)) return fail(-22, "qmlp_forward2_g: needs fc2/fc3 outputs");
+        if ((int64_t)n * nets * 2 > (int64_t)1 << 31) return fail(-22, "qmlp_forward2_g: too many rows");
+        c.nets = nets;
+    }
+    c.pairs = 2;
+    c.x3 = p0->x3 != 0;
+    c.plan = fwd_plan(c.a0, c.a1, n, 2, c.nets, c.x3, true, grouped ? FE_FORWARD : FE_FORWARD2, false, 0);
+    return 0;
+}
+
+static int forward_run(const evx_layout* lay, int32_t n, const evx_obs* obs0, const evx_qmlp_params* p0,
+                       const evx_qmlp_dropout* drop0, const evx_qmlp_fwd_out* out0, const evx_obs* obs1,
+                       const evx_qmlp_params* p1, const evx_qmlp_dropout* drop1, const evx_qmlp_fwd_out* out1,
+                       int pairs, bool grouped, int32_t nets, void* stream) {
+    FwdCall c;
+    if (int rc = forward_prepare(lay, n, obs0, p0, drop0, out0, obs1, p1, drop1, out1, pairs, grouped, nets, c))
+        return rc;
+    return launch_plan(c, n, (hipStream_t)stream);
+}
+
+// evx_qmlp_act's checks, record and plan; kernel64: evx_qmlp_act64's; grouped: evx_qmlp_act_g's over
+// `nets` nets. ncu <= 0: the current device's CU count
+static int act_prepare(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
+                       const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, bool grouped, int32_t nets,
+                       bool kernel64, int ncu, FwdCall& c) {
+    c.plan = evx_qmlp_fwd_plan{};
+    if (grouped)
+        if (int rc = group_check(nets, p)) return rc;
+    if (n <= 0) return 0;
+    if (!grouped) {
+        if (!out) return fail(-22, "qmlp_act: NULL out");
+        if (!out->q && !out->actions) return fail(-22, "qmlp_act: needs q or actions");
+    } else {
+        if (!out || (!out->q && !out->actions)) return fail(-22, "qmlp_act_g: needs q or actions");
+        if (out->perm) return fail(-22, "qmlp_act_g: no act permutation with grouped nets");
+        if (p->stat) return fail(-22, "qmlp_act_g: the act table path is single-net");
+        if (n & 1) return fail(-22, "qmlp_act_g: rows per net must be even (dropout row pairs)");
+        c.nets = nets;
+    }
+    if (int rc = make_fwd(lay, obs, n, p, drop, out, c.a0, FM_ACT, grouped ? nets : 0)) return rc;
+    c.x3 = p->x3 != 0;
+    if (!grouped && c.x3 && ncu <= 0) ncu = evxh::cu_count();
+    c.plan = fwd_plan(c.a0, c.a0, n, 1, c.nets, c.x3, true, grouped ? FE_ACT_G : FE_ACT, kernel64, ncu);
+    return 0;
+}
+
+static int act_run(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
+                   const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, bool grouped, int32_t nets,
+                   bool kernel64, void* stream) {
+    FwdCall c;
+    if (int rc = act_prepare(lay, obs, n, p, drop, out, grouped, nets, kernel64, 0, c)) return rc;
+    return launch_plan(c, n, (hipStream_t)stream);
+}
+
+// evx_qmlp_stat (x = NULL) and evx_qmlp_stat_x
+static int stat_run(const evx_layout* lay, const evx_obs* obs, const uint16_t* x, int32_t n, const evx_qmlp_params* p,
+                    float* out, void* stream) {
+    if (n <= 0) return 0;
+    if (x) {
+        if (!out || !p) return fail(-22, "qmlp_stat_x: NULL argument");
+        if (!p->x3) return fail(-22, "qmlp_stat_x: the X input is the x3 layout (p->x3)");
+    } else if (!out) {
+        return fail(-22, "qmlp_stat: NULL out");
+    }
+    FwdCall c;
+    const evx_qmlp_fwd_out none{};  // the table is the only output
+    if (int rc = make_fwd(lay, obs, n, p, nullptr, &none, c.a0, FM_RAW, 0, out, x)) return rc;
+    c.x3 = p->x3 != 0;
+    c.plan = fwd_plan(c.a0, c.a0, n, 1, 1, c.x3, false, FE_FORWARD, false, 0);
+    return launch_plan(c, n, (hipStream_t)stream);
+}
+
+extern "C" {
 
 int evx_qmlp_forward(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
                      const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream) {
+    return forward_run(lay, n, obs, p, drop, out, nullptr, nullptr, nullptr, nullptr, 1, false, 1, stream);
+}
+
+int evx_qmlp_forward2(const evx_layout* lay, int32_t n, const evx_obs* obs0, const evx_qmlp_params* p0,
+                      const evx_qmlp_dropout* drop0, const evx_qmlp_fwd_out* out0, const evx_obs* obs1,
+                      const evx_qmlp_params* p1, const evx_qmlp_dropout* drop1, const evx_qmlp_fwd_out* out1,
+                      void* stream) {
+    return forward_run(lay, n, obs0, p0, drop0, out0, obs1, p1, drop1, out1, 2, false, 1, stream);
+}
+
+int evx_qmlp_forward2_g(const evx_layout* lay, int32_t n, int32_t nets, const evx_obs* obs0, const evx_qmlp_params* p0,
+                        const evx_qmlp_dropout* drop0, const evx_qmlp_fwd_out* out0, const evx_obs* obs1,
+                        const evx_qmlp_params* p1, const evx_qmlp_dropout* drop1, const evx_qmlp_fwd_out* out1,
+                        void* stream) {
+    return forward_run(lay, n, obs0, p0, drop0, out0, obs1, p1, drop1, out1, 2, true, nets, stream);
+}
+
+int evx_qmlp_fwd_plan_query(const evx_layout* lay, int32_t n, const evx_obs* obs0, const evx_qmlp_params* p0,
+                            const evx_qmlp_dropout* drop0, const evx_qmlp_fwd_out* out0, const evx_obs* obs1,
+                            const evx_qmlp_params* p1, const evx_qmlp_dropout* drop1, const evx_qmlp_fwd_out* out1,
+                            int32_t nets, evx_qmlp_fwd_plan* plan) {
+    if (!plan) return fail(-22, "qmlp_fwd_plan_query: NULL plan");
+    FwdCall c;
+    const int pairs = nets == 0 && !obs1 && !p1 && !out1 ? 1 : 2;
+    const int rc = forward_prepare(lay, n, obs0, p0, drop0, out0, obs1, p1, drop1, out1, pairs, nets != 0, nets, c);
+    *plan = c.plan;
+    return rc;
+}
+
+int evx_qmlp_stat(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p, float* out,
+                  void* stream) {
+    return stat_run(lay, obs, nullptr, n, p, out, stream);
+}
+
+int evx_qmlp_stat_x(const evx_layout* lay, const evx_obs* obs, const uint16_t* x, int32_t n, const evx_qmlp_params* p,
+                    float* out, void* stream) {
+    return stat_run(lay, obs, x, n, p, out, stream);
+}
+
+int evx_qmlp_expand_x3(const evx_layout* lay, const evx_obs* obs, int32_t n, uint16_t* x, void* stream) {
     if (n <= 0) return 0;
-    evxm::Fwd a;
-    int rc = make_fwd(lay, obs, n, p, drop, out, a);
-    if (rc) return rc;
-    return launch_fwd(a, a, n, 1, out->q || out->actions || out->h2, (hipStream_t)stream, p->x3 != 0);
+    if (!lay || !obs || !x) return fail(-22, "qmlp_expand_x3: NULL argument");
+    if (!lay->obs_feat || !lay->obs_feat_lo || (lay->layout_set && (!lay->obs_feats || !lay->obs_feats_lo)))
+        return fail(-22, "qmlp_expand_x3: layout tables missing (obs_feat, obs_feat_lo)");
+    evxm::Fwd a{};
+    a.N = n;
+    a.obs = obs;
+    a.feat = lay->obs_feat;
+    a.feats = lay->layout_set ? lay->obs_feats : nullptr;
+    a.feat_lo = lay->obs_feat_lo;
+    a.feats_lo = lay->layout_set ? lay->obs_feats_lo : nullptr;
+    a.L = lay->L;
+    a.W = lay->W;
+    a.t_max = lay->t_max;
+    a.x = reinterpret_cast<__bf16*>(x);
+    launch_x_expand(a, n, (hipStream_t)stream);
+    return hip_status("qmlp_expand_x3");
+}
+
+int64_t evx_qmlp_act_ws_ints(int32_t n) { return n > 0 ? 2 + ((int64_t)n + 127) / 128 : 2; }
+
+int evx_qmlp_act(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
+                 const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream) {
+    return act_run(lay, obs, n, p, drop, out, false, 1, false, stream);
+}
+
+int evx_qmlp_act64(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
+                   const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream) {
+    return act_run(lay, obs, n, p, drop, out, false, 1, true, stream);
+}
+
+int evx_qmlp_act_g(const evx_layout* lay, const evx_obs* obs, int32_t n, int32_t nets, const evx_qmlp_params* p,
+                   const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream) {
+    return act_run(lay, obs, n, p, drop, out, true, nets, false, stream);
+}
+
+int evx_qmlp_act_plan_query(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
+                            const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, int32_t nets, int32_t kernel64,
+                            int32_t ncu, evx_qmlp_fwd_plan* plan) {
+    if (!plan) return fail(-22, "qmlp_act_plan_query: NULL plan");
+    FwdCall c;
+    const int rc = act_prepare(lay, obs, n, p, drop, out, nets != 0, nets, kernel64 != 0, ncu, c);
+    *plan = c.plan;
+    return rc;
 }
 
 // diagnostic builds only: copy the act stamps out (-1 when the build has none)
@@ -2975,212 +3354,6 @@ int evx_diag_act_stamps(long long* host, int32_t n) {
 #endif
 }
 
-}  // extern "C"
-
-// the x3 act: the persistent 128-row kernel when its table path applies (a table attached, the hash
-// or no dropout) and the launch has >= 4 tiles per CU (its cross-tile pipeline; with one tile per CU,
-// cfg2's 32 768 rows, the 64-row kernel's two workgroups per CU measured faster: 16.1 vs 15.3 M
-// env-steps/s); else (or kernel64) the 64-row kernel
-static void act_x3(const evxm::Fwd& a, int32_t n, hipStream_t st, bool kernel64) {
-    const int ntiles = (n + 127) / 128, ncu = evxh::cu_count();
-    if (!kernel64 && a.stat && !a.drop_mask && ntiles >= 4 * ncu) {
-        {
-            static std::atomic<uint64_t> attr_done;
-            const void* kp[2] = {(const void*)evxm::qact3p_kernel<0>, (const void*)evxm::qact3p_kernel<1>};
-            evxh::max_lds_once(attr_done, kp, 2, evxm::ACT3P_LDS);
-            static std::atomic<uint64_t> attr_done2;
-            const void* kr[2] = {(const void*)evxm::qact3h_rest_kernel<0>, (const void*)evxm::qact3h_rest_kernel<1>};
-            evxh::max_lds_once(attr_done2, kr, 2, evxm::ACT3H_LDS);
-        }
-        // the table-path tiles on the persistent kernel, then the others (if any) on the 64-row body
-        // (listed: one workgroup per CU over their halves; else every row re-checked)
-        const dim3 grid((unsigned)std::min(ntiles, ncu));
-        const dim3 rgrid(a.rest_ws ? (unsigned)std::min(2 * ntiles, ncu) : (unsigned)((n + 1023) / 1024));
-        if (a.drop_thresh) {
-            hipLaunchKernelGGL(evxm::qact3p_kernel<1>, grid, dim3(512), evxm::ACT3P_LDS, st, a, ntiles);
-            hipLaunchKernelGGL(evxm::qact3h_rest_kernel<1>, rgrid, dim3(256), evxm::ACT3H_LDS, st, a);
-        } else {
-            hipLaunchKernelGGL(evxm::qact3p_kernel<0>, grid, dim3(512), evxm::ACT3P_LDS, st, a, ntiles);
-            hipLaunchKernelGGL(evxm::qact3h_rest_kernel<0>, rgrid, dim3(256), evxm::ACT3H_LDS, st, a);
-        }
-        return;
-    }
-    launch_act3<false>(a, n, 1, st);
-}
-
-static int qmlp_act_impl(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
-                         const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream, bool kernel64) {
-    if (n <= 0) return 0;
-    if (!out) return fail(-22, "qmlp_act: NULL out");
-    if (!out->q && !out->actions) return fail(-22, "qmlp_act: needs q or actions");
-    evx_qmlp_fwd_out o = *out;
-    o.h1 = o.h1 ? o.h1 : reinterpret_cast<uint16_t*>(1);  // unused: H1 stays in LDS
-    o.x = nullptr;
-    o.h2 = nullptr;
-    evxm::Fwd a;
-    int rc = make_fwd(lay, obs, n, p, drop, &o, a);
-    if (rc) return rc;
-    a.h1 = nullptr;
-    a.h1l = nullptr;
-    a.rest_ws = out->act_ws;
-    {
-        static std::atomic<uint64_t> attr_done;
-        const void* ks[1] = {(const void*)evxm::qact_kernel};
-        evxh::max_lds_once(attr_done, ks, 1, evxm::ACT_LDS);
-    }
-    if (p->x3)
-        act_x3(a, n, (hipStream_t)stream, kernel64);
-    else
-        hipLaunchKernelGGL(evxm::qact_kernel, dim3((unsigned)((n + 127) / 128)), dim3(512), evxm::ACT_LDS,
-                           (hipStream_t)stream, a);
-    return hip_status("qact");
-}
-
-extern "C" {
-
-int64_t evx_qmlp_act_ws_ints(int32_t n) { return n > 0 ? 2 + ((int64_t)n + 127) / 128 : 2; }
-
-int evx_qmlp_act(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
-                 const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream) {
-    return qmlp_act_impl(lay, obs, n, p, drop, out, stream, false);
-}
-
-int evx_qmlp_act64(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
-                   const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream) {
-    return qmlp_act_impl(lay, obs, n, p, drop, out, stream, true);
-}
-
-int evx_qmlp_expand_x3(const evx_layout* lay, const evx_obs* obs, int32_t n, uint16_t* x, void* stream) {
-    if (n <= 0) return 0;
-    if (!lay || !obs || !x) return fail(-22, "qmlp_expand_x3: NULL argument");
-    if (!lay->obs_feat || !lay->obs_feat_lo || (lay->layout_set && (!lay->obs_feats || !lay->obs_feats_lo)))
-        return fail(-22, "qmlp_expand_x3: layout tables missing (obs_feat, obs_feat_lo)");
-    evxm::Fwd a{};
-    a.N = n;
-    a.obs = obs;
-    a.feat = lay->obs_feat;
-    a.feats = lay->layout_set ? lay->obs_feats : nullptr;
-    a.feat_lo = lay->obs_feat_lo;
-    a.feats_lo = lay->layout_set ? lay->obs_feats_lo : nullptr;
-    a.L = lay->L;
-    a.W = lay->W;
-    a.t_max = lay->t_max;
-    a.x = reinterpret_cast<__bf16*>(x);
-    const int64_t nx = (int64_t)n * 20;
-    hipLaunchKernelGGL(evxm::x_expand_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return hip_status("qmlp_expand_x3");
-}
-
-int evx_qmlp_stat_x(const evx_layout* lay, const evx_obs* obs, const uint16_t* x, int32_t n, const evx_qmlp_params* p,
-                    float* out, void* stream) {
-    if (!x) return evx_qmlp_stat(lay, obs, n, p, out, stream);
-    if (n <= 0) return 0;
-    if (!out || !p) return fail(-22, "qmlp_stat_x: NULL argument");
-    if (!p->x3) return fail(-22, "qmlp_stat_x: the X input is the x3 layout (p->x3)");
-    evx_qmlp_fwd_out o{};
-    o.h1 = reinterpret_cast<uint16_t*>(out);  // not written in raw mode
-    evxm::Fwd a;
-    int rc = make_fwd(lay, obs, n, p, nullptr, &o, a);
-    if (rc) return rc;
-    a.h1 = nullptr;
-    a.h1l = nullptr;
-    a.stat = nullptr;
-    a.perm = nullptr;
-    a.raw = out;
-    a.xin = reinterpret_cast<const __bf16*>(x);
-    const unsigned blocks = (unsigned)((n + evxm::RM - 1) / evxm::RM);
-    hipLaunchKernelGGL((evxm::qfc1_kernel<2, 1, 4, true, false, true>), dim3(blocks, 4, 1), dim3(256), 0,
-                       (hipStream_t)stream, a, a, 1);
-    return hip_status("qmlp_stat_x");
-}
-
-int evx_qmlp_stat(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p, float* out,
-                  void* stream) {
-    if (n <= 0) return 0;
-    if (!out) return fail(-22, "qmlp_stat: NULL out");
-    evx_qmlp_fwd_out o{};
-    o.h1 = reinterpret_cast<uint16_t*>(out);  // not written in raw mode
-    evxm::Fwd a;
-    int rc = make_fwd(lay, obs, n, p, nullptr, &o, a);
-    if (rc) return rc;
-    a.h1 = nullptr;
-    a.h1l = nullptr;
-    a.stat = nullptr;
-    a.perm = nullptr;
-    a.raw = out;
-    return launch_fwd(a, a, n, 1, false, (hipStream_t)stream, p->x3 != 0);
-}
-
-int evx_qmlp_forward2(const evx_layout* lay, int32_t n, const evx_obs* obs0, const evx_qmlp_params* p0,
-                      const evx_qmlp_dropout* drop0, const evx_qmlp_fwd_out* out0, const evx_obs* obs1,
-                      const evx_qmlp_params* p1, const evx_qmlp_dropout* drop1, const evx_qmlp_fwd_out* out1,
-                      void* stream) {
-    if (n <= 0) return 0;
-    evxm::Fwd a0, a1;
-    int rc = make_fwd(lay, obs0, n, p0, drop0, out0, a0);
-    if (!rc) rc = make_fwd(lay, obs1, n, p1, drop1, out1, a1);
-    if (rc) return rc;
-    if (!(out0->q || out0->actions || out0->h2) || !(out1->q || out1->actions || out1->h2))
-        return fail(-22, "qmlp_forward2: both problems need an fc2/fc3 output");
-    if ((p0->x3 != 0) != (p1->x3 != 0)) return fail(-22, "qmlp_forward2: both problems in one precision");
-    // (at n >= 32768 only: a fused act workgroup lives ~65 us on the full path, so below a full
-    // round of workgroups the two-kernel forward wins -- B = 4096: learn 187 vs 127 us)
-    const int dm0 = a0.drop_mask ? 2 : a0.drop_thresh ? 1 : 0, dm1 = a1.drop_mask ? 2 : a1.drop_thresh ? 1 : 0;
-    if (p0->x3 && out1->q && !out1->h2 && !out1->actions && !out1->x && n >= 8192 && n < 32768 && a0.stat && a1.stat &&
-        !a0.perm && !a0.actions && a0.x && a0.h1 && a0.h1l && a0.h2 && a0.q && dm0 == dm1) {
-        // both forwards through the act tables in one launch (qfwd2_kernel), X by its own launch
-        a1.perm = nullptr;
-        a1.actions = nullptr;
-        a1.h1 = a1.h1l = nullptr;
-        {
-            static std::atomic<uint64_t> attr_done;
-            const void* kf[3] = {(const void*)evxm::qfwd2_kernel<0>, (const void*)evxm::qfwd2_kernel<1>,
-                                 (const void*)evxm::qfwd2_kernel<2>};
-            evxh::max_lds_once(attr_done, kf, 3, evxm::ACT3H_LDS);
-        }
-        const int64_t nx = (int64_t)n * 20;
-        hipLaunchKernelGGL(evxm::x_expand_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a0);
-        const dim3 grid((unsigned)((n + 63) / 64), 2);
-        if (dm0 == 2)
-            hipLaunchKernelGGL(evxm::qfwd2_kernel<2>, grid, dim3(256), evxm::ACT3H_LDS, (hipStream_t)stream, a0, a1);
-        else if (dm0 == 1)
-            hipLaunchKernelGGL(evxm::qfwd2_kernel<1>, grid, dim3(256), evxm::ACT3H_LDS, (hipStream_t)stream, a0, a1);
-        else
-            hipLaunchKernelGGL(evxm::qfwd2_kernel<0>, grid, dim3(256), evxm::ACT3H_LDS, (hipStream_t)stream, a0, a1);
-        return hip_status("qmlp_forward2 paired");
-    }
-    if (p0->x3 && out1->q && !out1->h2 && !out1->actions && !out1->x && n >= 32768) {
-        // x3 learner: the second problem (the target net: Q only) through the fused act kernel
-        // (H1 / H2 stay in LDS, 64-row tiles, two workgroups per CU) instead of qfc1 + qfc23
-        // writing and re-reading both H1 planes; the first problem alone through qfc1 + qfc23
-        // the target net's own act table (static features x W1, rebuilt at each target sync --
-        // evacx.trainer attaches it to both nets): replay rows past the fire's last step (every
-        // row once the fire has stopped spreading: fire_step persists across resets) start fc1
-        // from it, the others run the full path per 64-row tile.
-        a1.perm = nullptr;
-        a1.actions = nullptr;
-        a1.h1 = a1.h1l = nullptr;
-        if (a0.stat && !a0.perm && !a0.actions && a0.x && a0.h1 && a0.h1l && a0.h2 && a0.q) {
-            // the online net's act table too (rebuilt after every update, so it matches the weights
-            // this forward reads): the online forward through the fused act kernel's table path,
-            // H1 planes / H2 / Q saved for the backward, X expanded by its own launch -- instead of
-            // qfc1's K = 640 products over staged A tiles and qfc23 re-reading both H1 planes
-            const int64_t nx = (int64_t)n * 20;
-            hipLaunchKernelGGL(evxm::x_expand_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0,
-                               (hipStream_t)stream, a0);
-            launch_act3<false, true>(a0, n, 1, (hipStream_t)stream);
-        } else {
-            // (the online forward through the fused kernel on the full path with X saved measured no
-            // faster than qfc1 + qfc23 at B = 32768: learn 0.420 vs 0.427 ms)
-            int rc2 = launch_fwd(a0, a0, n, 1, true, (hipStream_t)stream, true);
-            if (rc2) return rc2;
-        }
-        launch_act3<false>(a1, n, 1, (hipStream_t)stream);
-        return hip_status("qmlp_forward2 target act");
-    }
-    return launch_fwd(a0, a1, n, 2, true, (hipStream_t)stream, p0->x3 != 0);
-}
-
 // K splits of a weight-gradient GEMM: the most splits, a multiple of 8 (tn_place), whose
 // tiles x splits fit `slots` workgroups at once (two per CU: 512; dW2 shares its launch with
 // the 256 dZ1 workgroups: 256). dW1 (x3: 20 tiles) at B = 32768 -> 24 splits, 480 workgroups,
@@ -3196,10 +3369,12 @@ static int ksplit_kper(int B, int tiles, int slots, int minrows) {
 static int dw2_kper(int B) { return ksplit_kper(B, 8, 256, 256); }
 // (B <= 4096: one split per 256 rows -- 16 at cfg2's B = 4096, 160 -> 320 workgroups)
 static int dw1_kper(int B, bool x3) { return ksplit_kper(B, x3 ? 20 : 16, 512, B <= 4096 ? 256 : 1024); }
+// The launch shape of the grouped learn chain at B rows per net, `pairs` forward problems per net
+// and `nets` nets: the one decision qmlp_backward and launch_tail take theirs from (the forward's
+// fc1 tile is fwd_plan's, by the same rule), handed out by evx_qmlp_group_plan.
 static evx_qmlp_plan chain_plan(int32_t B, int nets, int pairs, bool x3) {
     evx_qmlp_plan p;
-    // fc1: 128-row tiles once they fill the chip (384 tiles over the problems of every net), else 64-row
-    p.fc1_rows = (unsigned)((B + 127) / 128) * (unsigned)(pairs * nets) >= 384 ? 128 : evxm::RM;
+    p.fc1_rows = fc1_tile_rows(B, pairs * nets);
     p.qbwd3_rows = evxm::qbwd3_rows(B);
     p.dw1_kper = dw1_kper(B, x3);
     p.dw1_gz = (B + p.dw1_kper - 1) / p.dw1_kper;
@@ -3503,61 +3678,10 @@ static int adam_pack3(float* p, float* g, float* m, float* v, float max_norm, co
     return hip_status("qmlp_adam_pack3");
 }
 
-// ------------------------------------------------ grouped nets
-// Every per-net buffer is an array [nets][one net's buffer]: the pointers passed are net 0's.
-static int group_check(int32_t nets, const evx_qmlp_params* p, const char* what) {
-    if (nets < 1 || nets > 1024) return fail(-22, "grouped qmlp: nets must be 1..1024");
-    if (!p || !p->x3) return fail(-22, "grouped qmlp: x3 parameters required (the [nets] operand layout is x3's)");
-    (void)what;
-    return 0;
-}
-
-int evx_qmlp_act_g(const evx_layout* lay, const evx_obs* obs, int32_t n, int32_t nets, const evx_qmlp_params* p,
-                   const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream) {
-    int rc = group_check(nets, p, "act");
-    if (rc) return rc;
-    if (n <= 0) return 0;
-    if (!out || (!out->q && !out->actions)) return fail(-22, "qmlp_act_g: needs q or actions");
-    if (out->perm) return fail(-22, "qmlp_act_g: no act permutation with grouped nets");
-    if (p->stat) return fail(-22, "qmlp_act_g: the act table path is single-net");
-    if (n & 1) return fail(-22, "qmlp_act_g: rows per net must be even (dropout row pairs)");
-    evx_qmlp_fwd_out o = *out;
-    o.h1 = reinterpret_cast<uint16_t*>(1);
-    o.x = nullptr;
-    o.h2 = nullptr;
-    evxm::Fwd a;
-    rc = make_fwd(lay, obs, n, p, drop, &o, a);
-    if (rc) return rc;
-    a.h1 = nullptr;
-    a.h1l = nullptr;
-    a.gn = nets;
-    launch_act3<true>(a, n, nets, (hipStream_t)stream);
-    return hip_status("qact_g");
-}
-
-int evx_qmlp_forward2_g(const evx_layout* lay, int32_t n, int32_t nets, const evx_obs* obs0, const evx_qmlp_params* p0,
-                        const evx_qmlp_dropout* drop0, const evx_qmlp_fwd_out* out0, const evx_obs* obs1,
-                        const evx_qmlp_params* p1, const evx_qmlp_dropout* drop1, const evx_qmlp_fwd_out* out1,
-                        void* stream) {
-    int rc = group_check(nets, p0, "forward2");
-    if (!rc) rc = group_check(nets, p1, "forward2");
-    if (rc) return rc;
-    if (n <= 0) return 0;
-    if (n & 1) return fail(-22, "qmlp_forward2_g: rows per net must be even (dropout row pairs)");
-    evxm::Fwd a0, a1;
-    rc = make_fwd(lay, obs0, n, p0, drop0, out0, a0);
-    if (!rc) rc = make_fwd(lay, obs1, n, p1, drop1, out1, a1);
-    if (rc) return rc;
-    if (a0.stat || a1.stat || a0.perm || a1.perm) return fail(-22, "qmlp_forward2_g: no table path / permutation");
-    if (!(out0->q || out0->h2) || !(out1->q || out1->h2)) return fail(-22, "qmlp_forward2_g: needs fc2/fc3 outputs");
-    if ((int64_t)n * nets * 2 > (int64_t)1 << 31) return fail(-22, "qmlp_forward2_g: too many rows");
-    return launch_fwd(a0, a1, n, 2, true, (hipStream_t)stream, true, nets);
-}
-
 int evx_qmlp_backward_ss_g(const evx_qmlp_params* p, int32_t B, int32_t nets, const float* dq, const uint16_t* x,
                            const uint16_t* h1, const float* h2, float drop_p, uint16_t* dz2, uint16_t* dz1,
                            const evx_qmlp_grads* g, float* ss, void* stream) {
-    int rc = group_check(nets, p, "backward");
+    int rc = group_check(nets, p);
     if (rc) return rc;
     if (!g || !g->part) return fail(-22, "qmlp_backward_ss_g: split-K partials required ([nets][part floats(B)])");
     if (!ss) return fail(-22, "qmlp_backward_ss_g: NULL ss");

@@ -39,6 +39,9 @@ ROUTE = {"NONE": 0, "GEMM128_F32": 1, "GEMM128_BF16": 2, "X3_VEC_AB": 3, "X3_VEC
          "X3_CONV_DX": 12, "X3_CONV_DW": 13, "CONV_LDS16_FWD": 14, "CONV_WREG32_FWD": 15, "CONV_LDS64_FWD": 16,
          "CONV_LDS64_DX": 17, "CONV_LDS128_DX": 18}
 REDUCE = {"NONE": 0, "GENERIC": 1, "QUARTERS": 2}  # EVX_REDUCE_*: the split-K reduction kernel
+# EVX_FWD_*: what an MLP forward or act call launches (evx_qmlp_fwd_plan_query, evx_qmlp_act_plan_query)
+FWD = {"NONE": 0, "FC": 1, "FC_GROUPED": 2, "PAIRED": 3, "TARGET_ACT_TABLE": 4, "TARGET_ACT_FC": 5, "ACT_BF16": 6,
+       "ACT_64": 7, "ACT_PERSISTENT": 8, "ACT_GROUPED": 9}
 EPISODE_REDUCE_SPAN = 1024  # EVX_EPISODE_REDUCE_SPAN: envs one pass of a reduce workgroup covers
 EPISODE_ROW_WORDS = 10  # sizeof(evx_episode_row) / 8
 HEALTH_ROW_WORDS = 6  # sizeof(evx_health_row) / 8
@@ -128,6 +131,12 @@ class evx_qmlp_plan(C.Structure):
     """The grouped learn chain's launch shape at B rows per net (evx_qmlp_group_plan)."""
     _fields_ = [(n, C.c_int32) for n in ["fc1_rows", "qbwd3_rows", "dw1_kper", "dw1_gz", "dw2_kper", "dw2_gz",
                                         "qdz1_tiles", "td_blocks"]]
+
+
+class evx_qmlp_fwd_plan(C.Structure):
+    """Every launch of one MLP forward or act call (evx_qmlp_fwd_plan_query, evx_qmlp_act_plan_query)."""
+    _fields_ = [(n, C.c_int32) for n in ["route", "fc1_rows", "fc1_cols", "fc23_rows", "drop_mode", "drop_mode1",
+                                        "x_expand", "act_grid", "rest_grid", "rest_listed"]]
 
 
 class evx_episodes(C.Structure):
@@ -241,6 +250,8 @@ SIGNATURES = {
     "evx_qmlp_backward_ss_g": (C.c_int, [_PAR, _i32, _i32] + [_vp] * 4 + [_f32, _vp, _vp, _GRADS, _vp, _vp]),
     "evx_qmlp_adam_pack3_g": (C.c_int, [_vp] * 4 + [_f32, _P(evx_adam)] + [_vp] * 10 + [_i32, _vp, _i32, _vp]),
     "evx_qmlp_group_plan": (C.c_int, [_i32, _i32, _P(evx_qmlp_plan)]),
+    "evx_qmlp_fwd_plan_query": (C.c_int, [_LAY, _i32, _vp, *_NET, _vp, *_NET, _i32, _P(evx_qmlp_fwd_plan)]),
+    "evx_qmlp_act_plan_query": (C.c_int, [_LAY, _vp, _i32, *_NET, _i32, _i32, _i32, _P(evx_qmlp_fwd_plan)]),
     "evx_qmix_nparams": (C.c_int32, [_i32]),
     "evx_qmix_part_floats": (C.c_int64, [_i32, _i32]),
     "evx_qmix_loss": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32, _i32] + [_vp] * 7 + [_i64, _vp]),

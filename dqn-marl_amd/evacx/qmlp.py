@@ -17,8 +17,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import (check, evx_qmlp_dropout, evx_qmlp_fwd_out, evx_qmlp_grads, evx_qmlp_params,  # noqa: F401
-                   evx_td_opts, lib)
+from ._lib import (check, evx_qmlp_dropout, evx_qmlp_fwd_out, evx_qmlp_fwd_plan, evx_qmlp_grads,  # noqa: F401
+                   evx_qmlp_params, evx_td_opts, lib)
 from .env import _stream
 
 HID, HID2, NACT, K1, K1P = 512, 256, 5, 726, 512
@@ -191,8 +191,9 @@ class MLPFast:
         (Map.robot_range, envs/map.py:75: a robot never leaves it), default every x.
         The table (like the operand copies) follows the fp32 parameters only through repack() and
         adam_step(): after any other write of the weights (load_state_dict, a broadcast) call
-        repack() (Learner.weights_written) -- the act and, at B >= 32768, the learner's online
-        forward read fc1 from this table."""
+        repack() (Learner.weights_written) -- the act and, on the routes that go through the act
+        tables (forward_pair_plan / act_plan say which a call takes), the learner's forwards read fc1
+        from this table."""
         x0, x1 = (0, L + 1) if x_range is None else (int(x_range[0]), int(x_range[1]))
         if not 0 <= x0 <= x1 <= L + 1:
             raise ValueError("attach_static: x_range must lie in [0, L + 1]")
@@ -265,12 +266,27 @@ class MLPFast:
                                  or n % rows_per_env or perm.numel() < n // rows_per_env):
             raise ValueError("qmlp act: perm needs an even rows_per_env dividing n and n / rows_per_env "
                              "entries")
+        fn = lib().evx_qmlp_act64 if kernel64 else lib().evx_qmlp_act
+        check(fn(*self._act_args(lay_c, obs, n, drop, q, actions, epsilon, act_seed, act_offset, perm, rows_per_env, ws),
+                 _stream()), "qmlp_act")
+
+    def _act_args(self, lay_c, obs, n, drop, q, actions, epsilon, act_seed, act_offset, perm, rows_per_env, ws):
+        """evx_qmlp_act's arguments up to the stream, as act() passes and act_plan() asks about them."""
         d = self._drop(drop) if drop else None
         o = evx_qmlp_fwd_out(q=_p(q), actions=_p(actions), epsilon=float(epsilon), act_seed=act_seed,
                              act_offset=act_offset, perm=_p(perm), rows_per_env=int(rows_per_env), act_ws=_p(ws))
-        fn = lib().evx_qmlp_act64 if kernel64 else lib().evx_qmlp_act
-        check(fn(C.byref(lay_c), obs.data_ptr(), n, C.byref(self.c), C.byref(d) if d is not None else None,
-                 C.byref(o), _stream()), "qmlp_act")
+        return C.byref(lay_c), obs.data_ptr(), n, C.byref(self.c), C.byref(d) if d is not None else None, C.byref(o)
+
+    def act_plan(self, lay_c, obs: torch.Tensor, n: int, drop=None, q=None, actions=None, epsilon=0.0, act_seed=0,
+                 act_offset=0, perm=None, rows_per_env=0, kernel64: bool = False, ws=None,
+                 ncu: int = 0) -> evx_qmlp_fwd_plan:
+        """What act() with these arguments launches (evx_qmlp_act_plan_query: the launcher's own plan,
+        nothing launched): route (evacx._lib.FWD), dropout mode, the persistent kernel's grids.
+        ncu: the CU count to plan for; 0 asks the current device."""
+        plan = evx_qmlp_fwd_plan()
+        args = self._act_args(lay_c, obs, n, drop, q, actions, epsilon, act_seed, act_offset, perm, rows_per_env, ws)
+        check(lib().evx_qmlp_act_plan_query(*args, 0, int(kernel64), int(ncu), C.byref(plan)), "qmlp_act_plan_query")
+        return plan
 
     @staticmethod
     def _drop(drop):
@@ -293,11 +309,26 @@ class MLPFast:
         _need("forward_pair obs1", obs1, n, 8)
         for o in (out0, out1):
             _need("forward_pair q", o.get("q"), n, NACT)
+        args = MLPFast._pair_args(lay_c, n, net0, obs0, drop0, out0, net1, obs1, drop1, out1)
+        check(lib().evx_qmlp_forward2(*args, _stream()), "qmlp_forward2")
+
+    @staticmethod
+    def _pair_args(lay_c, n, net0, obs0, drop0, out0, net1, obs1, drop1, out1):
+        """evx_qmlp_forward2's arguments up to the stream, as forward_pair passes and forward_pair_plan
+        asks about them."""
         d0, d1 = MLPFast._drop(drop0), MLPFast._drop(drop1)
         o0, o1 = MLPFast._out(**out0), MLPFast._out(**out1)
-        check(lib().evx_qmlp_forward2(C.byref(lay_c), n, obs0.data_ptr(), C.byref(net0.c), C.byref(d0), C.byref(o0),
-                                      obs1.data_ptr(), C.byref(net1.c), C.byref(d1), C.byref(o1), _stream()),
-              "qmlp_forward2")
+        return (C.byref(lay_c), n, obs0.data_ptr(), C.byref(net0.c), C.byref(d0), C.byref(o0),
+                obs1.data_ptr(), C.byref(net1.c), C.byref(d1), C.byref(o1))
+
+    @staticmethod
+    def forward_pair_plan(lay_c, n, net0, obs0, drop0, out0: dict, net1, obs1, drop1, out1: dict) -> evx_qmlp_fwd_plan:
+        """What forward_pair with these arguments launches (evx_qmlp_fwd_plan_query: the launcher's own
+        plan, nothing launched): route (evacx._lib.FWD), fc1 / fc23 tiles, dropout modes."""
+        plan = evx_qmlp_fwd_plan()
+        args = MLPFast._pair_args(lay_c, n, net0, obs0, drop0, out0, net1, obs1, drop1, out1)
+        check(lib().evx_qmlp_fwd_plan_query(*args, 0, C.byref(plan)), "qmlp_fwd_plan_query")
+        return plan
 
     def _grads(self, B, grads):
         g = evx_qmlp_grads(**{k: grads[f"fc{k[1]}.{'weight' if k[0] == 'w' else 'bias'}"].data_ptr()

@@ -485,6 +485,30 @@ class Learner:
         self.step_optimizer()
         return self.loss
 
+    def _pair_args(self, lay_c, s_obs, s2_obs, B, mask_online, mask_target, drop_row0):
+        """The arguments of learn_obs's forward pair (MLPFast.forward_pair / forward_pair_plan): the
+        online net saves X, H1, H2 and Q in the workspace, the target Q; dropout on the current stream
+        and the next. drop_row0 (even): the dropout hash rows start there (evacx.qgroup keys net g's
+        batch rows g * B + i)."""
+        from .qmlp import HID, HID2
+        f = self.fast
+
+        def buf(name, per_row, dt):
+            return self.net.ws.get(name, (B * per_row,), dt, self.device)
+        out0 = dict(h1=buf("fh1", f.planes * HID, torch.int16), x=buf("fx", f.kx, torch.int16),
+                    h2=buf("fh2", HID2, torch.float32), q=buf("fq", self.actions, torch.float32))
+        out1 = dict(h1=buf("fh1t", f.planes * HID, torch.int16), q=buf("fqt", self.actions, torch.float32))
+        d_on = (self.seed, self.drop_stream, DROPOUT_P, mask_online, drop_row0)
+        d_tg = (self.seed, self.drop_stream + 1, DROPOUT_P, mask_target, drop_row0)
+        return (lay_c, B, f, s_obs, d_on, out0, self.fast_t, s2_obs, d_tg, out1), out0, out1
+
+    def learn_plan(self, lay_c, s_obs, s2_obs, B, mask_online=None, mask_target=None, drop_row0: int = 0):
+        """What learn_obs's forward pair launches with these arguments (MLPFast.forward_pair_plan: the
+        launcher's own plan, nothing launched; the dropout stream, which learn_obs advances first,
+        does not bear on the plan)."""
+        pair, _, _ = self._pair_args(lay_c, s_obs, s2_obs, B, mask_online, mask_target, drop_row0)
+        return type(self.fast).forward_pair_plan(*pair)
+
     def learn_obs(self, lay_c, s_obs, a, r, done, s2_obs, B, update: bool = True, weights=None, td_abs=None,
                   mask_online=None, mask_target=None, drop_row0: int = 0, mask_select=None, gamma_row=None):
         """DQNAgent.learn on compact observations with the fused kernels (x3 = f32-accurate,
@@ -502,23 +526,17 @@ class Learner:
             if t.numel() < B * 8:
                 raise ValueError(f"learn_obs: {name} holds {t.numel() // 8} observations, B = {B}")
         ws, dev = self.net.ws, self.device
-        pl, kx = self.fast.planes, self.fast.kx
+        pl = self.fast.planes
 
         def buf(name, per_row, dt):
             return ws.get(name, (B * per_row,), dt, dev)
-        X = buf("fx", kx, torch.int16)
-        H1 = buf("fh1", pl * HID, torch.int16)
-        H2 = buf("fh2", HID2, torch.float32).view(B, HID2)
-        Q = buf("fq", self.actions, torch.float32).view(B, self.actions)
-        H1t = buf("fh1t", pl * HID, torch.int16)
-        Qt = buf("fqt", self.actions, torch.float32).view(B, self.actions)
         dQ = buf("fdq", self.actions, torch.float32).view(B, self.actions)
         dz2 = buf("fdz2", pl * HID2, torch.int16)
         dz1 = buf("fdz1", pl * HID, torch.int16)
         self.drop_stream += 3 if self.double_q else 2
-        # drop_row0 (even): the dropout hash rows start there (evacx.qgroup keys net g's batch rows g * B + i)
-        d_on = (self.seed, self.drop_stream, DROPOUT_P, mask_online, drop_row0)
-        d_tg = (self.seed, self.drop_stream + 1, DROPOUT_P, mask_target, drop_row0)
+        pair, on, tg = self._pair_args(lay_c, s_obs, s2_obs, B, mask_online, mask_target, drop_row0)
+        X, H1 = on["x"], on["h1"]
+        H2, Q, Qt = on["h2"].view(B, HID2), on["q"].view(B, self.actions), tg["q"].view(B, self.actions)
         sel = None
         if self.double_q:
             # the learner's own buffers: in the lagged schedule this runs on the learn stream beside the
@@ -530,8 +548,7 @@ class Learner:
             self.fast.act(lay_c, s2_obs, B, drop=(self.seed, self.drop_stream + 2, DROPOUT_P, mask_select, drop_row0),
                           actions=sel, epsilon=0.0, ws=sws)
             self.last_sel = sel
-        type(self.fast).forward_pair(lay_c, B, self.fast, s_obs, d_on, dict(h1=H1, x=X, h2=H2, q=Q), self.fast_t,
-                                     s2_obs, d_tg, dict(h1=H1t, q=Qt))
+        type(self.fast).forward_pair(*pair)
         if self.fused_opt:
             # the TD step inside the backward's first kernel, the gradients overwritten by its ordered
             # reductions, which also leave the norm partials unless an all-reduce will change the gradients

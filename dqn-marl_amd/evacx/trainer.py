@@ -331,9 +331,9 @@ class VecTrainer:
             lc = self.lay.c  # centres only where robots can be (Map.robot_range): 55 of 130 columns at cfg3
             xr = (max(lc.rx_lo, 0), min(lc.rx_hi, lc.L + 1))
             self.fast.attach_static(lc, lc.L, lc.W, lc.t_max, x_range=xr)
-            # the target net's table too (rebuilt at each target sync): the learner's target
-            # forward (the fused act kernel at B >= 32768) starts fc1 from it for replay rows
-            # past the fire's last step
+            # the target net's table too (rebuilt at each target sync): on the learner's routes
+            # through the act kernels (MLPFast.forward_pair_plan says which batch takes which) the
+            # target forward starts fc1 from it for replay rows past the fire's last step
             self.learner.fast_t.attach_static(lc, lc.L, lc.W, lc.t_max, x_range=xr)
             # the act's env order, per group (each group's act visits its own envs)
             self._perm = torch.zeros(E, dtype=torch.int32, device=self.device)

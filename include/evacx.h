@@ -708,9 +708,51 @@ typedef struct {
     int32_t td_blocks;   /* 256-row TD-loss blocks (partials) per net */
 } evx_qmlp_plan;
 /* Decided on the host by the function the chain's launchers themselves call: no launch, no device
- * call. nets = 1: the backward figures are those of the single-net x3 backward
- * (evx_qmlp_backward_ss, evx_qmlp_td_backward_ss). -22 for nets outside 1..1024, B <= 0 or out = NULL. */
+ * call. nets = 1 describes the backward only: its figures are those of the single-net x3 backward
+ * (evx_qmlp_backward_ss, evx_qmlp_td_backward_ss), while fc1_rows is evx_qmlp_forward2_g's with one
+ * net -- what evx_qmlp_forward2 runs is evx_qmlp_fwd_plan_query's to say.
+ * -22 for nets outside 1..1024, B <= 0 or out = NULL. */
 int evx_qmlp_group_plan(int32_t B, int32_t nets, evx_qmlp_plan *out);
+
+/* What a forward or act entry point launches (evx_qmlp_fwd_plan.route). */
+#define EVX_FWD_NONE 0              /* n <= 0: nothing is launched */
+#define EVX_FWD_FC 1                /* qfc1_kernel, then qfc23_kernel if fc23_rows: one problem or two
+                                       (evx_qmlp_stat, _stat_x: fc1 alone, writing the table) */
+#define EVX_FWD_FC_GROUPED 2        /* the same on the grouped instantiations (blockIdx.z = net x problem) */
+#define EVX_FWD_PAIRED 3            /* x_expand_kernel + qfwd2_kernel: both nets through their act tables */
+#define EVX_FWD_TARGET_ACT_TABLE 4  /* x_expand_kernel + qact3h_kernel SAVE (online), qact3h_kernel (target) */
+#define EVX_FWD_TARGET_ACT_FC 5     /* qfc1_kernel + qfc23_kernel (online), qact3h_kernel (target) */
+#define EVX_FWD_ACT_BF16 6          /* qact_kernel: 128-row tiles */
+#define EVX_FWD_ACT_64 7            /* qact3h_kernel: 64-row tiles */
+#define EVX_FWD_ACT_PERSISTENT 8    /* qact3p_kernel on act_grid workgroups, then qact3h_rest_kernel */
+#define EVX_FWD_ACT_GROUPED 9       /* qact3h_kernel's grouped instantiation (blockIdx.y = net) */
+/* Every launch of one evx_qmlp_forward / _forward2 / _forward2_g / _stat / _stat_x / _act / _act64 /
+ * _act_g call. The tile and grid fields are 0 where the route has no such launch. */
+typedef struct {
+    int32_t route;        /* EVX_FWD_* */
+    int32_t fc1_rows;     /* rows per qfc1 tile: 64 or 128 (0: no qfc1 launch) */
+    int32_t fc1_cols;     /* fc1 columns per workgroup: 128, 256 or 512 */
+    int32_t fc23_rows;    /* rows per qfc23 tile: 32 or 64 (0: no qfc23 launch) */
+    int32_t drop_mode;    /* the dropout instantiation: 0 none, 1 the hash, 2 an explicit mask */
+    int32_t drop_mode1;   /* the same of the second problem (the routes with a target act) */
+    int32_t x_expand;     /* 1: x_expand_kernel writes the first problem's X by its own launch */
+    int32_t act_grid;     /* persistent act: workgroups of qact3p_kernel */
+    int32_t rest_grid;    /* persistent act: workgroups of qact3h_rest_kernel */
+    int32_t rest_listed;  /* persistent act: 1 when the rest runs the tiles listed in act_ws, 0: every row */
+} evx_qmlp_fwd_plan;
+/* The plan of evx_qmlp_forward2 with these arguments (obs1 = p1 = out1 = NULL: of evx_qmlp_forward;
+ * nets >= 1: of evx_qmlp_forward2_g; nets = 0: the single-net entry points), decided by the function
+ * the launchers themselves switch on: no launch, no device call (pointers are only tested for NULL).
+ * An argument error the call would report comes back as the same code with the same text. */
+int evx_qmlp_fwd_plan_query(const evx_layout *lay, int32_t n, const evx_obs *obs0, const evx_qmlp_params *p0,
+                            const evx_qmlp_dropout *drop0, const evx_qmlp_fwd_out *out0, const evx_obs *obs1,
+                            const evx_qmlp_params *p1, const evx_qmlp_dropout *drop1, const evx_qmlp_fwd_out *out1,
+                            int32_t nets, evx_qmlp_fwd_plan *plan);
+/* The same of evx_qmlp_act (kernel64 != 0: evx_qmlp_act64; nets >= 1: evx_qmlp_act_g) on a device of
+ * ncu compute units; ncu <= 0 asks the current device (the only device call). */
+int evx_qmlp_act_plan_query(const evx_layout *lay, const evx_obs *obs, int32_t n, const evx_qmlp_params *p,
+                            const evx_qmlp_dropout *drop, const evx_qmlp_fwd_out *out, int32_t nets,
+                            int32_t kernel64, int32_t ncu, evx_qmlp_fwd_plan *plan);
 
 /* ---- QMIX mixer (runners/train_qmix.py:39-54 MixingNetwork, loss :78-104) for n <= 16 agents:
  * Q / Qt [n][B][A] (evx_qmlp_forward2_g), act [n][B], rew / done [B]; mix / mix_t the online /

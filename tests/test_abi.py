@@ -92,7 +92,7 @@ def test_earlier_loader_names_are_the_one_loader():
 
 STRUCTS = ["evx_layout", "evx_state", "evx_replay", "evx_step_out", "evx_qmlp_params", "evx_qmlp_dropout",
            "evx_qmlp_grads", "evx_qmlp_fwd_out", "evx_td_opts", "evx_gemm_desc", "evx_gemm_plan", "evx_adam",
-           "evx_prio", "evx_episodes", "evx_health", "evx_qmlp_plan"]
+           "evx_prio", "evx_episodes", "evx_health", "evx_qmlp_plan", "evx_qmlp_fwd_plan"]
 
 
 def _mirrored_constants(_lib):
@@ -107,8 +107,9 @@ def _mirrored_constants(_lib):
          "sizeof(evx_health_row)": 8 * _lib.HEALTH_ROW_WORDS}
     c.update({"EVX_ROUTE_" + k: v for k, v in _lib.ROUTE.items()})
     c.update({"EVX_REDUCE_" + k: v for k, v in _lib.REDUCE.items()})
+    c.update({"EVX_FWD_" + k: v for k, v in _lib.FWD.items()})
     # every route and reduction the header defines is mirrored, each under its own value
-    for prefix, mirror in (("EVX_ROUTE_", _lib.ROUTE), ("EVX_REDUCE_", _lib.REDUCE)):
+    for prefix, mirror in (("EVX_ROUTE_", _lib.ROUTE), ("EVX_REDUCE_", _lib.REDUCE), ("EVX_FWD_", _lib.FWD)):
         assert sorted(re.findall(r"#define (%s\w+)" % prefix, header_text())) == sorted(prefix + k for k in mirror)
         assert len(set(mirror.values())) == len(mirror)
     assert len(_lib.PREC) == 3
@@ -142,7 +143,7 @@ def test_structure_layouts_and_constants_match_the_header(tmp_path):
     assert r.returncode == 0, r.stderr
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, check=True).stdout
     got = {k: int(v) for k, v in (ln.rsplit(" ", 1) for ln in out.splitlines())}
-    assert len(STRUCTS) == 16 and set(got) == set(want)
+    assert len(STRUCTS) == 17 and set(got) == set(want)
     assert {k: (got[k], want[k]) for k in want if got[k] != want[k]} == {}
 
 

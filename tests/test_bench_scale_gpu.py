@@ -19,7 +19,7 @@ says nothing about the variant the bench runs:
 * learn: the x3 learn chain at the bench's batches: the online forward alone through
   qfc1_kernel<2,2,4,true> (64 x 256 tiles) + qfc23, the target through the fused act kernel
   at B >= 32768 (qact3h_kernel), multi-tile qdz1 workgroups (8 tiles at B = 32768, 2 at 8192;
-  csrc/qmlp.hip: qdz1_tiles_per_wg, launch_fwd, evx_qmlp_forward2). One DQNAgent.learn step
+  csrc/qmlp.hip: qdz1_tiles_per_wg, fwd_plan, evx_qmlp_forward2). One DQNAgent.learn step
   (agents/dqn_agent.py:126-168) from compact observations of a 128x128 R16 env, explicit
   dropout keep masks, against torch fp32 autograd + clip_grad_norm_ + Adam on the expanded
   observations -- the same restatement tests/test_dqn_golden_cpu.py pins to the reference's
@@ -144,6 +144,7 @@ def test_x3_learn_at_bench_batch(B, table):
     (rtol 2e-4) and the norm (rtol 1e-3)."""
     _need_gpu()
     from evacx.env import DeviceLayout, VecEnv
+    from evacx._lib import FWD
     from evacx.layout import build_tables, synthetic
     from evacx.qmlp import HID, HID2, K1
     from evacx.qnet import Learner
@@ -191,6 +192,12 @@ def test_x3_learn_at_bench_batch(B, table):
         d = (torch.rand(B, generator=gh) < 0.05).to(torch.uint8).to(dev)
         m1 = (torch.rand(B, HID, generator=gh) >= 0.2).to(torch.uint8).to(dev)
         m2 = (torch.rand(B, HID, generator=gh) >= 0.2).to(torch.uint8).to(dev)
+        # the forward pair this case is here for, asked of the launcher's own plan
+        plan = lr.learn_plan(lay.c, s_obs, s2_obs, B, mask_online=m1, mask_target=m2)
+        assert (plan.route, plan.fc1_rows, plan.fc1_cols, plan.fc23_rows, plan.x_expand) == {
+            (8192, False): (FWD["FC"], 64, 128, 64, 0), (8192, True): (FWD["PAIRED"], 0, 0, 0, 1),
+            (32768, False): (FWD["TARGET_ACT_FC"], 64, 256, 64, 0),
+            (32768, True): (FWD["TARGET_ACT_TABLE"], 0, 0, 0, 1)}[(B, table)]
         loss = lr.learn_obs(lay.c, s_obs, a, r, d, s2_obs, B, mask_online=m1, mask_target=m2)
         torch.cuda.synchronize()
         # the device's branch pattern, from the forward it saved for the backward

@@ -69,11 +69,18 @@ def test_x3_learn_step_matches_float64_at_B(B, table, weights):
     if table:
         lu.attach_tables(lr, lay)
     # which forward pair ran: qfwd2_kernel keeps the target's H1 in LDS, qfc1 + qfc23 write its planes
+    from evacx._lib import FWD
     from evacx.qmlp import HID
     h1t = lr.net.ws.get("fh1t", (B * 2 * HID,), torch.int16, lr.device).fill_(0x7fc0)
     gen = torch.Generator().manual_seed(1000 + B)
     for it in range(2):
         bt = lu.make_batch(env, lay, B, gen, table=table, weights=weights, td_abs=weights)
+        # the forward pair this case names (the module docstring's bands), asked of the launcher's own plan
+        plan = lr.learn_plan(lay.c, bt.s_obs, bt.s2_obs, B, mask_online=bt.m1, mask_target=bt.m2)
+        assert (plan.route, plan.x_expand) == ((FWD["PAIRED"], 1) if table and B >= 8192 else (FWD["FC"], 0)), \
+            f"B={B} table={table}: this case no longer runs the forward pair it names"
+        assert plan.fc1_rows == (0 if table and B >= 8192 else 64)  # every B here is below 384 128-row tiles
+        assert plan.fc23_rows == (0 if table and B >= 8192 else 32 if -(-B // 64) * 2 < 256 else 64)
         dev, ref = lu.learn_step_and_reference(lr, lay, env, bt)
         what = f"B={B} table={table} weights={weights} step {it}"
         lu.check_flips(ref, what)

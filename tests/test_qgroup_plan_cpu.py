@@ -1,5 +1,5 @@
-"""The grouped learn chain's launch plan (evx_qmlp_group_plan: the function launch_fwd's grouped
-branch, qmlp_backward and launch_tail take their decisions from) pinned at every band edge, and the
+"""The grouped learn chain's launch plan (evx_qmlp_group_plan: the function qmlp_backward and
+launch_tail take their decisions from, fc1's rows by the forward plan's rule) pinned at every band edge, and the
 argument refusals of the grouped act and of the mixer -- all on a host without a GPU: none of these
 calls launches or touches a device.
 

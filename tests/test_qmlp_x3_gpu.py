@@ -470,6 +470,7 @@ def test_x3_persistent_act_matches_64_row_kernel(case):
         n = E0 * rep * R
         obs = env.obs.view(-1, 8).repeat(rep, 1).contiguous()
         obs[:, 6] = torch.clamp(obs[:, 6], max=t_max - 1)
+    from evacx._lib import FWD
     from evacx.qmlp import act_ws_ints
     ws = torch.zeros(act_ws_ints(n), dtype=torch.int32, device="cuda")
     out = {}
@@ -479,8 +480,13 @@ def test_x3_persistent_act_matches_64_row_kernel(case):
     for key, k64, w in (("p", False, None), ("pw", False, ws), ("pw2", False, ws), ("k64", True, None)):
         q = torch.full((n, 5), float("nan"), device="cuda")
         a = torch.full((n,), -1, dtype=torch.int32, device="cuda")
-        fast.act(lc, obs.view(-1), n, drop=drop, q=q, actions=a, epsilon=eps, act_seed=6, act_offset=33,
-                 kernel64=k64, ws=w, **kw)
+        args = dict(drop=drop, q=q, actions=a, epsilon=eps, act_seed=6, act_offset=33, kernel64=k64, ws=w, **kw)
+        # the kernels compared are two: the launcher's own plan for these arguments on this device
+        plan = fast.act_plan(lc, obs.view(-1), n, **args)
+        assert plan.route == (FWD["ACT_64"] if k64 else FWD["ACT_PERSISTENT"]), (key, plan.route)
+        assert k64 or (plan.act_grid > 0 and plan.rest_grid > 0 and plan.rest_listed == (w is not None))
+        assert plan.drop_mode == (1 if drop[2] > 0 else 0)
+        fast.act(lc, obs.view(-1), n, **args)
         torch.cuda.synchronize()
         out[key] = (q, a)
         if w is not None:
