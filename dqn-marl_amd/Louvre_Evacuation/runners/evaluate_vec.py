@@ -12,6 +12,12 @@ network shared by every robot; ``--per-robot PATH...`` one network per robot (th
 (``qmix_agent{1,2}.pth``; the mixer plays no part in acting). A checkpoint is the reference's
 dict (its ``q_network``) or a bare state_dict, conv or MLP.
 
+``--curves``, ``--track N`` and ``--plot`` add how the evacuation went over time
+(``evaluate(timeline=True)``): per strategy ``curves_<strategy>.csv`` (one row per step: newly
+evacuated and dead, episodes running, mean evacuated / dead / remaining, average health),
+``tracked_<strategy>.npz`` (the first N persons of env 0, step by step) and
+``evaluation_<strategy>.png`` (``utils.visualization.plot_evaluation``; needs matplotlib).
+
 The reference's "no robot" strategy is not offered: it parks the robot at (1000, 1000), and
 the vector kernels' tables are padded by 6 cells only, so they must not be fed off-grid
 positions.
@@ -31,6 +37,8 @@ import torch  # noqa: E402
 import yaml  # noqa: E402
 
 CSV_COLUMNS = ["strategy", "avg_health", "death_rate", "evac_rate", "avg_time", "episodes"]
+CURVE_COLUMNS = ["step", "time_s", "new_evacuated", "new_dead", "ended", "running", "evacuated_mean", "dead_mean",
+                 "remaining_mean", "avg_health"]
 STATIC_ACTION = 4
 
 
@@ -48,6 +56,11 @@ def build_parser():
     ap.add_argument("--out", default=None, help="output directory (default: the config's save_path)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--seed-base", type=int, default=1234, help="env e is seeded seed_base + e under every strategy")
+    ap.add_argument("--curves", action="store_true",
+                    help="write curves_<strategy>.csv: one row per step (evacuated, dead, remaining, avg health ...)")
+    ap.add_argument("--track", type=int, default=0, metavar="N",
+                    help="write tracked_<strategy>.npz: the first N persons of env 0, step by step")
+    ap.add_argument("--plot", action="store_true", help="write evaluation_<strategy>.png (needs matplotlib)")
     return ap
 
 
@@ -106,6 +119,47 @@ def _fmt(v, spec):
     return "n/a" if v is None else format(v, spec)
 
 
+def write_curves(path, curves):
+    """One row per step up to the last one at which an episode ran; floats as repr, NaN empty."""
+    run = curves["running"]
+    n = max((int(i) + 1 for i in run.nonzero()[0]), default=0)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(CURVE_COLUMNS)
+        for s in range(n):
+            row = []
+            for k in CURVE_COLUMNS:
+                v = curves[k][s].item()
+                row.append("" if v != v else repr(v))
+            w.writerow(row)
+    return n
+
+
+def write_outputs(args, out_dir, name, ev, spec):
+    """The per-strategy files --curves / --track / --plot ask for."""
+    import numpy as np
+    cv = ev["curves"]
+    if args.curves:
+        path = os.path.join(out_dir, f"curves_{name}.csv")
+        n = write_curves(path, cv)
+        print(f"{name}: {n} steps written to {path}" +
+              (f" ({int(cv['late'][3])} steps beyond the table)" if cv["late"][3] else ""))
+    if args.track:
+        path = os.path.join(out_dir, f"tracked_{name}.npz")
+        np.savez(path, **cv["tracked"])
+        print(f"{name}: {len(cv['tracked']['len'])} tracked persons written to {path}")
+    if args.plot:
+        try:
+            import matplotlib  # noqa: F401
+        except ImportError:
+            print(f"{name}: --plot needs matplotlib, which is not installed; no figure written")
+            return
+        from Louvre_Evacuation.utils.visualization import plot_evaluation
+        path = plot_evaluation(ev, os.path.join(out_dir, f"evaluation_{name}.png"), layout=spec,
+                               title=f"{name}: {ev['episodes']} episodes")
+        print(f"{name}: figure written to {path}")
+
+
 def evaluate_vec(args):
     from evacx.env import DeviceLayout
     from evacx.evaluate import evaluate
@@ -124,11 +178,17 @@ def evaluate_vec(args):
     lay = DeviceLayout(build_tables(spec), int(ec["num_people"]), device=device)
     print(f"env {spec.L}x{spec.W}, {lay.P} people, {lay.R} robots, exit {tuple(spec.exit)}; {args.envs} envs x "
           f"{args.episodes} episodes per strategy on {device}")
+    if not 0 <= args.track <= lay.P:
+        raise ValueError(f"--track must be 0..{lay.P}")
+    timeline = bool(args.curves or args.track or args.plot)
+    extra = dict(timeline=True, track=args.track or None) if timeline else {}
     rows = []
     for name, policy, learner in strategies(args, lay.R, device):
         ev = evaluate(lay, args.envs, args.episodes, policy, learner=learner, seed_base=args.seed_base,
-                      seed=args.seed, metrics=True)
+                      seed=args.seed, metrics=True, **extra)
         rows.append(table_row(name, ev))
+        if timeline:
+            write_outputs(args, out_dir, name, ev, spec)
     print(f"{'strategy':<10} {'avg health':>10} {'death rate':>10} {'evac rate':>10} {'avg time':>9} {'episodes':>9}")
     for name, health, death, evac, time, n in rows:
         print(f"{name:<10} {_fmt(health, '10.2f')} {_fmt(death, '10.2%')} {_fmt(evac, '10.2%')} "

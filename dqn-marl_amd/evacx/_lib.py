@@ -151,6 +151,12 @@ class evx_health(C.Structure):
               "tab_avg", "tab_min", "tab_alive")
 
 
+class evx_timeline(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ["E", "T", "n_rows", "n_trk"]] + \
+        _ptrs("t", "p_evac", "p_dead", "n_total", "evac", "dead", "ended", "seen", "alive", "health_q", "late",
+              "bad_health", "trk_env", "trk_person", "trk_pk", "trk_health", "trk_len")
+
+
 # ---------------------------------------------------------------- signatures
 # symbol -> (restype, argtypes), one entry per prototype of the header, in its order. A pointer to a
 # structure mirrored above is typed; _vp is a `void *` (streams) or a plain data pointer (device and
@@ -265,6 +271,10 @@ SIGNATURES = {
     "evx_health_update": (C.c_int, [_P(evx_health), _vp, _vp, _i32, _vp, _i64, _vp]),
     "evx_health_reduce": (C.c_int, [_P(evx_health), _vp, _i32, _vp, _i32, _vp]),
     "evx_health_last_error": (C.c_char_p, []),
+    "evx_timeline_init": (C.c_int, [_P(evx_timeline), _vp]),
+    "evx_timeline_update": (C.c_int, [_P(evx_timeline)] + [_vp] * 5 + [_i32, _i64, _vp]),
+    "evx_timeline_trace0": (C.c_int, [_P(evx_timeline), _vp, _vp, _i32, _vp]),
+    "evx_timeline_last_error": (C.c_char_p, []),
 }
 
 _lib = None

@@ -8,7 +8,9 @@ over-represented), and looks at the device only every ``check_every`` steps.
 
 ``metrics=True`` adds the reference's per-episode health metrics
 (EvacuationEnv.get_performance_metrics, envs/evacuation_env.py:290-309) through
-``evacx.health.HealthStats``; ``policy="greedy"`` also takes one network per robot (a
+``evacx.health.HealthStats``; ``timeline=True`` adds the per-step evacuation curves and tracked
+persons of the reference's recorded evaluation episode (``evacx.timeline.Timeline``);
+``policy="greedy"`` also takes one network per robot (a
 GroupedLearner, a GroupedQMix, or a sequence of Learners).
 """
 from __future__ import annotations
@@ -106,7 +108,7 @@ class _EachRobot:
 
 def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_base: int = 1234, seed: int = 0,
              check_every: int = 16, max_steps: Optional[int] = None, layout_of: Optional[Sequence[int]] = None,
-             metrics: bool = False) -> dict:
+             metrics: bool = False, timeline: bool = False, track=None) -> dict:
     """Run E envs of ``layout`` (a DeviceLayout, or a LayoutSet with ``layout_of``) under
     ``policy`` until every env has finished ``episodes_per_env`` episodes, and return the
     EpisodeStats summary over exactly E * episodes_per_env episodes, with ``per_env`` = the
@@ -132,8 +134,19 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
     ``avg_health`` (mean over the episodes with somebody alive; None without one),
     ``min_health`` (the smallest), ``min_health_mean``, ``alive_mean``, ``health_episodes``,
     ``total_time_mean`` (= ``length_mean`` * 0.5, the env's time_per_step), and ``per_env`` the
-    table ``tab_avg_health`` / ``tab_min_health`` / ``tab_alive``. No host sync is added."""
+    table ``tab_avg_health`` / ``tab_min_health`` / ``tab_alive``. No host sync is added.
+
+    timeline=True: the same reset-apart path, with an ``evacx.timeline.Timeline`` (T = 1200, the
+    env's step limit; cap = episodes_per_env) counting every step between the step and the reset,
+    after the health update where both are asked for. The result gains ``curves``
+    (``Timeline.curves()``: per-step evacuated / dead / remaining / avg_health curves, the
+    evacuation-time and death-time distributions, per layout and summed). ``track`` = a person
+    count n (the first n persons of env 0) or (env_ids, person_ids) also keeps those persons'
+    positions and health over their env's first episode (``curves["tracked"]``); it needs
+    ``timeline=True`` (ValueError). No host sync is added."""
     _check_policy(policy, learner)
+    if track is not None and not timeline:
+        raise ValueError("evaluate: track needs timeline=True")
     E, K, check_every = int(E), int(episodes_per_env), int(check_every)
     if E < 1 or K < 1 or check_every < 1:
         raise ValueError("evaluate: E, episodes_per_env and check_every must be >= 1")
@@ -152,6 +165,12 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
         from .health import HealthStats
         health = HealthStats(E, layout.device, layout.P, layout_idx=env.layout_idx, n_layouts=n_layouts, cap=K,
                              record=K)
+    tline = None
+    if timeline:
+        from .timeline import Timeline
+        tline = Timeline(E, layout.device, layout.P, T=EPISODE_MAX_STEPS, layout_idx=env.layout_idx,
+                         n_layouts=n_layouts, cap=K, track=track)
+        tline.trace0(env)
     n = E * layout.R
     actions = torch.full((n,), policy if isinstance(policy, int) else 0, dtype=torch.int32, device=layout.device)
     q0 = torch.zeros(n, N_ACTIONS, dtype=torch.float32, device=layout.device) if policy == "random" else None
@@ -176,12 +195,15 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
             Q = learner.q_values(x.view(n, 11, 11, 6), train=False, tag="eval")
             _lib.check(_lib.lib().evx_act(Q.data_ptr(), n, learner.actions, 0.0, seed, steps * n, actions.data_ptr(),
                                           _stream()), "act")
-        if health is None:
+        if health is None and tline is None:
             env.step(actions, auto_reset=True)
             stats.update(env.reward, env.done, env.counts)
-        else:  # the terminal state is read between the step and the reset
+        else:  # the state the step left is read between the step and the reset
             env.step(actions, auto_reset=False)
-            health.update(env, env.done)
+            if health is not None:
+                health.update(env, env.done)
+            if tline is not None:
+                tline.update(env, env.done, env.counts)
             stats.update(env.reward, env.done, env.counts)
             env.reset(mask=env.done)
         steps += 1
@@ -203,6 +225,8 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
                 k[name] = hl[name]
         out["per_env"].update(tab_avg_health=health.tab_avg, tab_min_health=health.tab_min,
                               tab_alive=health.tab_alive)
+    if tline is not None:
+        out["curves"] = tline.curves()
     return out
 
 

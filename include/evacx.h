@@ -892,6 +892,62 @@ int evx_health_reduce(const evx_health *h, const int32_t *layout_idx, int32_t n_
                       int32_t clear, void *stream);
 const char *evx_health_last_error(void);
 
+/* ---- Evacuation timelines and tracked persons (csrc/timeline.hip): what the reference's recorded
+ * evaluation episode keeps (DQNTrainingVisualizer, utils/visualization.py) -- evacuated, dead and
+ * avg_health after every step, the evacuation-time and death-time distributions from the per-step
+ * count deltas, and selected persons step by step -- over every episode of every env. All arrays
+ * are the caller's device arrays. Everything added across envs is an integer (health in fixed
+ * point at 2^-20), so the result does not depend on the order of the adds; no float atomics. */
+typedef struct {
+    int32_t E;
+    int32_t T;             /* slots per row: slot s holds episode step s + 1 */
+    int32_t n_rows;        /* layout rows (an env's row is layout_idx[e], 0 without layout_idx) */
+    int32_t n_trk;         /* tracked persons (0: no trace, the trk_* pointers may be NULL) */
+    /* per env [E] */
+    int32_t *t;            /* steps of the episode in progress */
+    int32_t *p_evac, *p_dead; /* counts after that episode's previous step */
+    int64_t *n_total;      /* episodes finished since evx_timeline_init (the timeline's own count) */
+    /* per row and slot [n_rows][T] */
+    int64_t *evac, *dead;  /* persons newly evacuated / newly dead at that step */
+    int64_t *ended;        /* episodes that ended at that step */
+    int64_t *seen;         /* episodes recorded at that step */
+    int64_t *alive;        /* sum over those episodes of the persons whose dead bit (pk bit 25) is clear */
+    int64_t *health_q;     /* sum over those persons of llrint(health * 2^20), round half even */
+    int64_t *late;         /* [n_rows][4]: evac, dead, ended, steps at episode steps beyond T */
+    int64_t *bad_health;   /* [1]: not-dead persons with |health| > 128 (or NaN), left out of alive and health_q */
+    /* optional trace of n_trk persons over their env's first episode */
+    int32_t *trk_env, *trk_person; /* [n_trk], input; clamped into 0..E-1 and 0..P-1 */
+    uint32_t *trk_pk;      /* [T + 1][n_trk]: slot 0 the state after the reset, slot t after step t */
+    double *trk_health;    /* [T + 1][n_trk] */
+    int32_t *trk_len;      /* [n_trk]: slots written */
+} evx_timeline;
+
+/* Zeroes every array of tl but trk_env / trk_person (one launch). */
+int evx_timeline_init(const evx_timeline *tl, void *stream);
+/* One step of every env of tl from the step's counts[2e], counts[2e + 1] (evacuated, dead so far)
+ * and done[e] (evx_step_out). With s = t[e] the env's slot and row = layout_idx[e] (NULL: 0;
+ * clamped into 0..n_rows-1), an episode whose lifetime index n_total[e] is < cap (cap <= 0: every
+ * episode; evx_episode_update's rule) adds to [row][s]: evac += counts[2e] - p_evac[e],
+ * dead += counts[2e + 1] - p_dead[e], ended += done[e] != 0, seen += 1 and, with pk / health
+ * ([E][P] as the step left them, before any reset; P 1..EVX_HEALTH_MAX_P), alive and health_q over
+ * the persons whose dead bit is clear and whose |health| <= 128; the others of them are counted in
+ * bad_health. s >= T: the first four go to late[row] instead. Then t, p_evac, p_dead take the step,
+ * or, where done[e], start again from 0 and n_total[e] is bumped. pk = health = NULL (callers whose
+ * resets are fused into the step) leaves alive and health_q alone.
+ * n_trk > 0 (needs pk / health): a first launch of the same call writes every tracked person's pk
+ * and health to trace slot t[e] + 1 (<= T) while n_total[e] == 0. The update launch runs one wave
+ * per env, 8 envs per workgroup; envs of a workgroup on the same (row, slot) are combined in LDS
+ * before one returnless 64-bit integer atomic add per field and destination. -22 with a message,
+ * before any launch: a NULL descriptor, required array, counts or done; E < 1 or T < 1;
+ * n_rows < 1; P out of range; pk without health or health without pk; n_trk > 0 with a NULL trace
+ * array or without pk. */
+int evx_timeline_update(const evx_timeline *tl, const int32_t *counts, const uint8_t *done, const int32_t *layout_idx,
+                        const int32_t *pk, const double *health, int32_t P, int64_t cap, void *stream);
+/* Trace slot 0 of the tracked persons whose env has not finished an episode: the state after the
+ * first reset. Nothing is launched with n_trk == 0. */
+int evx_timeline_trace0(const evx_timeline *tl, const int32_t *pk, const double *health, int32_t P, void *stream);
+const char *evx_timeline_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
