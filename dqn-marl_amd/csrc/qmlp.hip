@@ -72,6 +72,15 @@ __device__ __forceinline__ void split2(float v, __bf16& hi, __bf16& lo) {
     hi = (__bf16)v;
     lo = (__bf16)(v - (float)hi);
 }
+// split2 of two values, each plane's pair packed (v0 in the low half): one conversion per plane
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split2x2(float v0, float v1, uint32_t& hi, uint32_t& lo) {
+    const f32x2 v = {v0, v1};
+    hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+    const f32x2 r = {v0 - __builtin_bit_cast(float, hi << 16), v1 - __builtin_bit_cast(float, hi & 0xffff0000u)};
+    lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf16x2));
+}
 
 __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
     h ^= h >> 16;
@@ -839,7 +848,13 @@ __device__ __forceinline__ void fc3p_partials(const f32x16 (&acc)[2][2], const f
 // 10-round Philox per row, and two waves carrying all 128 rows held the next slot back
 // rowS: the tile rows' output rows (orow), recorded when the rows were set up
 __device__ __forceinline__ void fc3p_rows(const Fwd& a, const float* red, int m0, const int* rowS) {
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+    // the thread index and the epsilon draw's seed, opaque per call: the partials' addresses and Philox's
+    // key schedule (20 uniform words) are formed here -- hoisted out of the caller's tile loop they were
+    // live across it, the addresses spilled to scratch and the keys to lanes
+    int tid = threadIdx.x;
+    uint32_t s0 = (uint32_t)a.act_seed, s1 = (uint32_t)(a.act_seed >> 32);
+    asm volatile("" : "+v"(tid), "+s"(s0), "+s"(s1));
+    const int w = tid >> 6, l = tid & 63;
     auto R = reinterpret_cast<const float (*)[NACT][128]>(red);
     if (w < 4 && l < 32) {
         const int r = 32 * w + l, rt = m0 + r;
@@ -847,7 +862,9 @@ __device__ __forceinline__ void fc3p_rows(const Fwd& a, const float* red, int m0
             float qv[NACT];
 #pragma unroll
             for (int k = 0; k < NACT; k++) qv[k] = ((R[0][k][r] + R[1][k][r]) + R[2][k][r]) + R[3][k][r];
-            q_out(a, qv, rowS[r]);
+            Fwd b = a;  // (kernel arguments: only the two seed words get registers of their own)
+            b.act_seed = (uint64_t)s1 << 32 | s0;
+            q_out(b, qv, rowS[r]);
         }
     }
 }
@@ -1231,6 +1248,9 @@ __global__ __launch_bounds__(256, 2) void qact3h_kernel(Fwd a0) {
 // ds_write_b64 (16 lanes = 16 k rows: distinct banks), and fc2 reads its B operand (rows x 8 k) with
 // ds_read_b64_tr_b16 (4 k rows x 64 B per 32 lanes: distinct banks). A tile with a row off the table
 // path (fire step < the table's, or a centre outside it) runs act3h_tile on its two halves.
+// The kernel is bound by vector issue beside its MFMAs (about five other
+// instructions hide per MFMA), so addresses are formed once per quarter or tile and reached by
+// immediates, and nothing uniform is kept live across the tile loop (it would be spilled to lanes).
 typedef const __attribute__((address_space(1))) char gbyte;  // global-memory views (explicit: the
 typedef const __attribute__((address_space(1))) float gfloat;  // bases pass through asm, which would
 typedef const __attribute__((address_space(1))) bf16x8 gbf16x8;  // leave generic pointers -> flat loads)
@@ -1359,29 +1379,47 @@ __global__ __launch_bounds__(512, 2) void qact3p_kernel(Fwd a, int ntiles) {
         for (int j = 0; j < 4; j++) v[j] = ((bits >> (2 * j)) & 1u) * one | (((bits >> (2 * j + 1)) & 1u) * one) << 16;
         reinterpret_cast<uint4*>(dsm + A3P_OCC)[tid] = make_uint4(v[0], v[1], v[2], v[3]);
     }
-    const gbyte *w2p = (const gbyte*)a.w2, *w2lp = (const gbyte*)a.w2l;
-    const gbyte *w1op = (const gbyte*)a.w1o, *w1olp = (const gbyte*)a.w1ol, *statp = (const gbyte*)a.stat;
+    // the weight bases of the wave's column group (both tile orders are linear in the tile index), opaque:
+    // a fragment's address is base + (lane's 16 B + a literal). Folded with c instead, the ~100 fragment
+    // offsets of a tile were uniform values live across the tile loop, spilled to lanes and read back
+    const size_t cw2 = w2_tile(2, 0, 0) * 2 * (size_t)c, cw1 = w1o_tile(1, 0, 0) * 2 * (size_t)c;
+    const gbyte *w2p = (const gbyte*)a.w2 + cw2, *w2lp = (const gbyte*)a.w2l + cw2;
+    const gbyte *w1op = (const gbyte*)a.w1o + cw1, *w1olp = (const gbyte*)a.w1ol + cw1, *statp = (const gbyte*)a.stat;
+    asm volatile("" : "+s"(w2p), "+s"(w2lp), "+s"(w1op), "+s"(w1olp));
     // tile-uniform table path of tile tt's row tid (< 128): every row at the table's fire step with its
     // centre inside the table; its table row into posS[buf], the row-pair hashes into phS[buf]
-    // pre: row tid's observation and output row, loaded (else loaded here); the output rows go to rowS[buf]
-    auto setup_rows = [&](int tt, int buf, bool& ok, const evx_obs* pre, int prow) {
+    // pre: row t's centre, fire step (the three words the test reads: a whole observation held across a
+    // slot spilled) and output row, loaded (else loaded here); the output rows go to rowS[buf]
+    // t: the thread index (the caller's opaque copy: nothing derived from it lives across the tile loop)
+    // orow with the rows-per-env count opaque: its reciprocal is formed at the call, not kept across the loop
+    auto orowp = [&](int row) {
+        Fwd b = a;  // (a copy of kernel arguments costs nothing: only rpe gets a register of its own)
+        asm volatile("" : "+s"(b.rpe));
+        return orow(b, row);
+    };
+    auto setup_rows = [&](int t, int tt, int buf, bool& ok, bool pre, int pcx, int pcy, int pfs, int prow) {
         ok = true;
         const int mm = tt * 128;
-        if (tid < 128) {
+        if (t < 128) {
             int pos = 0;
-            if (mm + tid < a.N) {
-                const int orw = pre ? prow : orow(a, mm + tid);
-                rowS[buf * 128 + tid] = orw;
-                const evx_obs ob = pre ? *pre : a.obs[orw];
-                ok = min(max(ob.fire_step, 0), a.t_max) == a.stat_fs && ob.cx >= a.stat_x0 &&
-                     ob.cx < a.stat_x0 + a.stat_nx && ob.cy >= 0 && ob.cy <= a.W + 1;
-                pos = ok ? (ob.cx - a.stat_x0) * (a.W + 2) + ob.cy : 0;
+            if (mm + t < a.N) {
+                const int orw = pre ? prow : orowp(mm + t);
+                rowS[buf * 128 + t] = orw;
+                int cx = pcx, cy = pcy, fs = pfs;
+                if (!pre) {
+                    const evx_obs* ob = &a.obs[orw];
+                    cx = ob->cx, cy = ob->cy, fs = ob->fire_step;
+                }
+                ok = min(max(fs, 0), a.t_max) == a.stat_fs && cx >= a.stat_x0 && cx < a.stat_x0 + a.stat_nx &&
+                     cy >= 0 && cy <= a.W + 1;
+                pos = ok ? (cx - a.stat_x0) * (a.W + 2) + cy : 0;
             }
-            posS[buf * 128 + tid] = pos;
-        } else if (DM == 1 && tid < 192) {
-            const int r2 = mm + 2 * (tid - 128);
-            phS[buf * 64 + tid - 128] =
-                r2 < a.N ? drop_row(a.drop_seed, a.drop_stream, (a.drop_row0 + (uint32_t)krow(a, r2)) >> 1) : 0u;
+            // the table row's byte offset (32-bit, unsigned as load_tab adds the column's to it)
+            posS[buf * 128 + t] = (int)((uint32_t)pos * (uint32_t)(HID * 4));
+        } else if (DM == 1 && t < 192) {
+            const int r2 = mm + 2 * (t - 128);
+            phS[buf * 64 + t - 128] =
+                r2 < a.N ? drop_row(a.drop_seed, a.drop_stream, (a.drop_row0 + (uint32_t)(a.gn ? r2 : orowp(r2))) >> 1) : 0u;
         }
     };
     int it_ = -1;
@@ -1405,13 +1443,18 @@ __global__ __launch_bounds__(512, 2) void qact3p_kernel(Fwd a, int ntiles) {
         A3P_ST(0);
         // the lane index, opaque per iteration: the per-lane offsets derived from it are formed inside
         // it (hoisted out of the tile loop, a few hundred of them were live across it and spilled)
-        int lane = tid & 63;
-        asm volatile("" : "+v"(lane));
+        int tl = tid;  // (the thread index likewise: the row set-up's addresses)
+        asm volatile("" : "+v"(tl));
+        const int lane = tl & 63;
         const int h = lane >> 5, j32 = lane & 31;
         const uint32_t l16 = (uint32_t)lane * 16u;  // a lane's 16 B of a 1-KB operand fragment
         // fc2's transposed B reads: lane l takes k rows 8 h + (l >> 2 & 3) (+ 4) of a k-step, rows
         // r0 + 32 mt + 16 (l >> 4 & 1) + 4 (l & 3) .. + 3 (tr_frag's addressing on the swizzled image)
         const int kq = 8 * h + ((lane >> 2) & 3), rq = r0 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+        // the epilogue's H1^T byte offset of the lane's column 32 c + j32 at rows r0 + 4 h; the row groups
+        // + 32 mt + 8 g flip bits 6 and 4-5 of it: the swizzle XORs the 8-B piece index (r >> 1), in which
+        // r0 / 2 + 2 h, 16 mt and 4 g occupy disjoint bits, so the sum is an XOR with a constant
+        const uint32_t epo = (uint32_t)h1t_off(32 * c + j32, r0 + 4 * h) * 2u;
         auto trf = [&](const __bf16* plane, int ks, int mt) -> bf16x8 {
             const __bf16* b = plane + ks * 16 * 128;
             const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(b + h1t_off(kq, 32 * mt + rq)));
@@ -1424,7 +1467,7 @@ __global__ __launch_bounds__(512, 2) void qact3p_kernel(Fwd a, int ntiles) {
             for (int mt = 0; mt < 2; mt++) {
                 const int row = mm + r0 + mt * 32 + j32;
                 uint4 o = make_uint4(0u, 0u, 0u, 0u);
-                if (row < a.N) o = *reinterpret_cast<const uint4*>(&a.obs[orow(a, row)].occ[0]);
+                if (row < a.N) o = *reinterpret_cast<const uint4*>(&a.obs[orowp(row)].occ[0]);
                 occ[mt][0] = o.x;
                 occ[mt][1] = o.y;
                 occ[mt][2] = o.z;
@@ -1443,36 +1486,63 @@ __global__ __launch_bounds__(512, 2) void qact3p_kernel(Fwd a, int ntiles) {
                     const int pp[4] = {p4.x, p4.y, p4.z, p4.w};
 #pragma unroll
                     for (int i = 0; i < 4; i++)  // 32-bit byte offsets from the uniform base
-                        tab[mt][4 * g + i] = *(const gfloat*)(statp + ((uint32_t)pp[i] * (uint32_t)(HID * 4) + cofs));
+                        tab[mt][4 * g + i] = *(const gfloat*)(statp + ((uint32_t)pp[i] + cofs));  // posS: byte offsets
                 }
         };
         auto load_w2 = [&](int q, int ks, int slot) {
 #pragma unroll
-            for (int nt = 0; nt < 2; nt++) {  // uniform base + (fragment offset + the lane's 16 B)
-                const uint32_t o = (uint32_t)w2_tile(c * 2 + nt, 4 * q + (ks >> 1), ks & 1) * 2u + l16;
+            for (int nt = 0; nt < 2; nt++) {  // the column group's base + (fragment offset + the lane's 16 B)
+                const uint32_t o = (uint32_t)w2_tile(nt, 4 * q + (ks >> 1), ks & 1) * 2u + l16;
                 wb[slot][nt] = *(const gbf16x8*)(w2p + o);
                 wl[slot][nt] = *(const gbf16x8*)(w2lp + o);
             }
         };
+        // A quarter's 8 weight fragments of one column tile (k-steps 0 .. 7) are 8 KB in a row, so one
+        // per-lane offset to their middle reaches each with the load's 13-bit immediate (-4096 .. 3072):
+        // one address instruction per quarter, not one per k-step. frag0: the quarter's first fragment
+        // (bytes). Opaque: the compiler would fold the constants back into one literal per load.
+        auto qbase = [&](uint32_t frag0) {
+            uint32_t v = l16 + frag0 + 4096u;
+            asm volatile("" : "+v"(v));
+            return v;
+        };
+        auto load_w2b = [&](const uint32_t (&vb)[2], int ks, int slot) {  // load_w2 of k-step ks from qbase
+#pragma unroll
+            for (int nt = 0; nt < 2; nt++) {
+                wb[slot][nt] = *(const gbf16x8*)(w2p + (size_t)vb[nt] + (ptrdiff_t)(ks * 1024 - 4096));
+                wl[slot][nt] = *(const gbf16x8*)(w2lp + (size_t)vb[nt] + (ptrdiff_t)(ks * 1024 - 4096));
+            }
+        };
+        auto ldwb = [&](uint32_t vw, int ks) {  // ldw of k-step ks from qbase
+            bh[ks % 3] = *(const gbf16x8*)(w1op + (size_t)vw + (ptrdiff_t)(ks * 1024 - 4096));
+            bl[ks % 3] = *(const gbf16x8*)(w1olp + (size_t)vw + (ptrdiff_t)(ks * 1024 - 4096));
+        };
         // fc1 of quarter q: acc1 = tab + occupancy columns x bits (ks ascending, hi then lo per
         // fragment, as act3h_tile); at ks 5, behind every fc1 weight load (tab was read at ks 0), the
         // table loads of the quarter after (tbuf, tq; tq < 0: none)
-        // fc1 weight fragments of k-step ks of quarter q (column tile 4 q + c) into ring slot ks % 3
+        // fc1 weight fragments of k-step ks of quarter q (column tile 4 q + c: c is in the base) into ring slot ks % 3
         auto ldw = [&](int q, int ks) {
-            const uint32_t o = (uint32_t)w1o_tile(4 * q + c, ks >> 1, ks & 1) * 2u + l16;
+            const uint32_t o = (uint32_t)w1o_tile(4 * q, ks >> 1, ks & 1) * 2u + l16;
             bh[ks % 3] = *(const gbf16x8*)(w1op + o);
             bl[ks % 3] = *(const gbf16x8*)(w1olp + o);
         };
         // (its first two k-steps' fragments were loaded by the phase before: fc2q's last k-steps)
+        // the A fragment of k-step ks (cells 16 ks + 8 h .. + 7, in word ks >> 1) for row slab mt
+        auto occ_av = [&](int ks, int mt) -> bf16x8 {
+            const int c0 = ks * 16 + 8 * h;
+            return __builtin_bit_cast(bf16x8, occT[(occ[mt][ks >> 1] >> (c0 & 31)) & 0xffu]);
+        };
         auto fc1q = [&](int q, int tbuf, int tq) {
+            bf16x8 avn = occ_av(0, 0);  // one fragment ahead: its LDS read under the MFMAs before it
+            const uint32_t vw = qbase((uint32_t)w1o_tile(4 * q, 0, 0) * 2u);
 #pragma unroll
             for (int ks = 0; ks < 8; ks++) {
-                if (ks + 2 < 8) ldw(q, ks + 2);
+                if (ks + 2 < 8) ldwb(vw, ks + 2);
                 if (ks == 5 && tq >= 0) load_tab(tbuf, tq);
-                const int c0 = ks * 16 + 8 * h;  // cells c0 .. c0 + 7, in word ks >> 1
 #pragma unroll
                 for (int mt = 0; mt < 2; mt++) {
-                    const bf16x8 av = __builtin_bit_cast(bf16x8, occT[(occ[mt][ks >> 1] >> (c0 & 31)) & 0xffu]);
+                    const bf16x8 av = avn;
+                    if (2 * ks + mt + 1 < 16) avn = occ_av((2 * ks + mt + 1) >> 1, (2 * ks + mt + 1) & 1);
                     acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bh[ks % 3], ks == 0 ? tab[mt] : acc1[mt], 0, 0, 0);
                     acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bl[ks % 3], acc1[mt], 0, 0, 0);
                 }
@@ -1484,36 +1554,47 @@ __global__ __launch_bounds__(512, 2) void qact3p_kernel(Fwd a, int ntiles) {
             float v[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float x = acc1[mt][4 * g + i];
+                // DM 1: the scale first, ReLU on the product -- relu(x) * s = relu(x * s) bit for bit for the
+                // positive s = 1 / (1 - p) (x <= 0 or NaN: 0 both ways; x > 0: the same product), and a product
+                // is canonical, so the ReLU is one v_max_f32; on the MFMA's own sum the compiler puts a
+                // canonicalising v_max(x, x) in front of it (one more instruction per H1 value)
+                const float x = DM == 1 ? acc1[mt][4 * g + i] * a.drop_scale : acc1[mt][4 * g + i];
                 v[i] = x > 0.f ? x : 0.f;
             }
             if constexpr (DM == 1) {
                 const uint2 ph = *reinterpret_cast<const uint2*>(&phS[cur * 64 + (rb >> 1)]);
                 const uint32_t col = (uint32_t)(128 * q + k);
                 const uint32_t h0 = drop_pair(ph.x, col), h1 = drop_pair(ph.y, col);
-                v[0] = (h0 & 0xffffu) >= a.drop_thresh ? v[0] * a.drop_scale : 0.f;
-                v[1] = (h0 >> 16) >= a.drop_thresh ? v[1] * a.drop_scale : 0.f;
-                v[2] = (h1 & 0xffffu) >= a.drop_thresh ? v[2] * a.drop_scale : 0.f;
-                v[3] = (h1 >> 16) >= a.drop_thresh ? v[3] * a.drop_scale : 0.f;
+                v[0] = (h0 & 0xffffu) >= a.drop_thresh ? v[0] : 0.f;
+                v[1] = (h0 >> 16) >= a.drop_thresh ? v[1] : 0.f;
+                v[2] = (h1 & 0xffffu) >= a.drop_thresh ? v[2] : 0.f;
+                v[3] = (h1 >> 16) >= a.drop_thresh ? v[3] : 0.f;
             }
-            __bf16 hi[4], lo[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) split2(v[i], hi[i], lo[i]);
-            const int o = h1t_off(k, rb);
-            *reinterpret_cast<uint2*>(Hb + o) = __builtin_bit_cast(uint2, hi);
-            *reinterpret_cast<uint2*>(Hb + A3P_PL + o) = __builtin_bit_cast(uint2, lo);
+            uint2 hi, lo;
+            split2x2(v[0], v[1], hi.x, lo.x);
+            split2x2(v[2], v[3], hi.y, lo.y);
+            char* const Hc = reinterpret_cast<char*>(Hb) + (epo ^ (uint32_t)(64 * mt + 16 * g));  // h1t_off(k, rb)
+            *reinterpret_cast<uint2*>(Hc) = hi;
+            *reinterpret_cast<uint2*>(Hc + A3P_PL * 2) = lo;
         };
         // fc2 over quarter qq's K from buffer Hb (k-step ks: fc2 K 128 qq + 16 ks; kc, s order as
         // act3h_tile); EPI: quarter eq's epilogue into buffer He, one row group per k-step; the last
         // k-step loads the first fragments of quarter (qq + 1) & 3 (the next tile's 0 after 3)
         // wq >= 0: the next fc1's quarter -- its first two k-steps' weight fragments (k-steps 5, 6)
         auto fc2q = [&](int qq, const __bf16* Hb, auto epi_on, int eq, __bf16* He, int wq) {
+            const uint32_t vb[2] = {qbase((uint32_t)w2_tile(0, 4 * qq, 0) * 2u), qbase((uint32_t)w2_tile(1, 4 * qq, 0) * 2u)};
+            uint32_t vw = 0;  // the next fc1 quarter's qbase, formed at k-step 5 and used again at 6 (wq >= 0 only)
 #pragma unroll
             for (int ks = 0; ks < 8; ks++) {
-                if (ks + 1 < 8) load_w2(qq, ks + 1, (ks + 1) & 1);
+                // k-steps 1 .. 7 by immediates from vb; the wrap to the next quarter's fragment 0 is 4096 B past
+                // the immediate's reach, so it (and the tile prologue) keeps load_w2's literal offset
+                if (ks + 1 < 8) load_w2b(vb, ks + 1, (ks + 1) & 1);
                 else load_w2((qq + 1) & 3, 0, 0);
-                if (ks == 5 && wq >= 0) ldw(wq, 0);
-                if (ks == 6 && wq >= 0) ldw(wq, 1);
+                if (ks == 5 && wq >= 0) {
+                    vw = qbase((uint32_t)w1o_tile(4 * wq, 0, 0) * 2u);
+                    ldwb(vw, 0);
+                }
+                if (ks == 6 && wq >= 0) ldwb(vw, 1);
                 const int sl = ks & 1;
 #pragma unroll
                 for (int mt = 0; mt < 2; mt++) {
@@ -1549,7 +1630,7 @@ __global__ __launch_bounds__(512, 2) void qact3p_kernel(Fwd a, int ntiles) {
             for (; tile < ntiles; tile += gridDim.x) {
                 __syncthreads();  // the last readers of posS / phS / H1 / the partials are done
                 bool ok;
-                setup_rows(tile, cur, ok, nullptr, 0);
+                setup_rows(tl, tile, cur, ok, false, 0, 0, 0, 0);
                 fast = __syncthreads_and(ok);
                 if (fast) break;  // else qact3h_rest_kernel's: listed for it
                 if (tid == 0 && a.rest_ws) {  // (a count past ntiles: a workspace not zeroed -- nothing written)
@@ -1594,17 +1675,17 @@ __global__ __launch_bounds__(512, 2) void qact3p_kernel(Fwd a, int ntiles) {
         // slot 2, and the next tile's rows checked (posS / phS of the other buffer; its observations
         // loaded at the slot's start)
         const int nt2 = tile + (int)gridDim.x;
-        evx_obs obn{{0u, 0u, 0u, 0u}, 0, 0, 0, 0};
-        int orn = 0;
-        if (tid < 128 && nt2 < ntiles && nt2 * 128 + tid < a.N) {
-            orn = orow(a, nt2 * 128 + tid);
-            obn = a.obs[orn];
+        int cxn = 0, cyn = 0, fsn = 0, orn = 0;
+        if (tl < 128 && nt2 < ntiles && nt2 * 128 + tl < a.N) {
+            orn = orowp(nt2 * 128 + tl);
+            const evx_obs* ob = &a.obs[orn];
+            cxn = ob->cx, cyn = ob->cy, fsn = ob->fire_step;
         }
         fc1q(2, cur, 3);
         A3P_ST(8);
         fc2q(1, H1b, std::true_type{}, 2, H, 3);
         bool okn = true;
-        if (nt2 < ntiles) setup_rows(nt2, cur ^ 1, okn, &obn, orn);
+        if (nt2 < ntiles) setup_rows(tl, nt2, cur ^ 1, okn, true, cxn, cyn, fsn, orn);
         A3P_ST(9);
         const bool fast_next = __syncthreads_and(okn) && nt2 < ntiles;
         A3P_ST(10);
