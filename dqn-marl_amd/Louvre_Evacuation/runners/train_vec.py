@@ -16,6 +16,9 @@ learner's Double-Q targets, Huber loss and soft target updates (defaults from th
 ``agent:`` keys ``double_dqn``, ``loss``, ``huber_delta``, ``target_tau`` of the config).
 ``--n-step N`` (default: the optional ``agent:`` key ``n_step``, else 1) trains on n-step
 returns gathered from the replay ring.
+``--learn-stats`` turns on the learner diagnostics: at every log line one more
+line and a row of ``learn_log.csv`` with the window's Q / target / TD-error statistics, gradient
+norm and clipping, non-finite counts, and the value probe's bias, RMSE and correlation.
 
 Usage: python -m Louvre_Evacuation.runners.train_vec --envs 4096 --steps 2000   (from dqn-marl_amd/)
 """
@@ -33,6 +36,10 @@ import torch  # noqa: E402
 import yaml  # noqa: E402
 
 CSV_COLUMNS = ["step", "episodes", "reward", "evac_rate", "death_rate", "length", "loss", "epsilon"]
+# learn_log.csv (--learn-stats): the learn statistics' window, then the value probe's
+LEARN_COLUMNS = ["step", "learn_steps", "q_mean", "qmax_mean", "target_mean", "td_abs_mean", "td_rms", "td_p50",
+                 "td_p90", "td_p99", "td_abs_max", "greedy_frac", "grad_norm_mean", "grad_norm_max", "clipped_frac",
+                 "rows_bad", "steps_bad", "probes", "q0_mean", "return_mean", "bias", "rmse", "corr"]
 
 
 def parse_args(argv=None):
@@ -56,6 +63,9 @@ def parse_args(argv=None):
                     help="soft target update rate per learn step; 0: the periodic hard copy (config: agent.target_tau)")
     ap.add_argument("--n-step", type=int, default=None,
                     help="n-step returns from the replay ring, 1..32 (config: agent.n_step; 1: one-step targets)")
+    ap.add_argument("--learn-stats", action="store_true",
+                    help="learner diagnostics on the device: learn-batch statistics and the value probe "
+                         "(learn_log.csv)")
     return ap.parse_args(argv)
 
 
@@ -97,6 +107,13 @@ def _fmt(v, spec):
     return "n/a" if v is None else format(v, spec)
 
 
+def learn_row(step: int, learn_steps: int, ls: dict, vs: dict) -> list:
+    """One learn_log.csv row (LEARN_COLUMNS) from learn_summary() and value_summary(); None: empty."""
+    vals = [ls[k] for k in LEARN_COLUMNS[2:15]] + [ls["rows_bad"], ls["steps_bad"], vs["probes"]] + \
+           [vs[k] for k in LEARN_COLUMNS[18:]]
+    return [step, learn_steps] + ["" if v is None else repr(v) for v in vals]
+
+
 def train_vec(args):
     from evacx.env import DeviceLayout
     from evacx.layout import LayoutSpec, build_tables
@@ -126,7 +143,8 @@ def train_vec(args):
                     epsilon=float(ac.get("epsilon", 1.0)), epsilon_min=float(ac.get("epsilon_min", 0.02)),
                     epsilon_decay=float(ac.get("epsilon_decay", 0.9995)),
                     target_every=int(ac.get("target_update_freq", 200)), learner_seed=args.seed,
-                    act_table=lay.R % 2 == 0, episode_stats=True, n_step=n_step, **opts)
+                    act_table=lay.R % 2 == 0, episode_stats=True, n_step=n_step, learn_stats=args.learn_stats,
+                    value_probe=args.learn_stats, **opts)
     tgt = f"soft tau {opts['target_tau']:g}" if opts["target_tau"] > 0 else f"hard copy every {tr.target_every}"
     print(f"env {spec.L}x{spec.W}, {lay.P} people, exit {tuple(spec.exit)}; {args.envs} envs, {args.qnet} Q-network "
           f"({tr.q_arith}), batch {batch}, replay {capacity} on {device}; "
@@ -134,9 +152,13 @@ def train_vec(args):
           f"{'huber(%g)' % opts['huber_delta'] if opts['loss'] == 'huber' else 'mse'} loss, target {tgt}, "
           f"n_step {n_step}")
     best = float("-inf")
-    with open(os.path.join(out_dir, "training_log.csv"), "w", newline="") as f:
+    with open(os.path.join(out_dir, "training_log.csv"), "w", newline="") as f, \
+            open(os.path.join(out_dir, "learn_log.csv") if args.learn_stats else os.devnull, "w", newline="") as lf:
         log = csv.writer(f)
         log.writerow(CSV_COLUMNS)
+        llog = csv.writer(lf)
+        if args.learn_stats:
+            llog.writerow(LEARN_COLUMNS)
         for step in range(1, args.steps + 1):
             tr.step()
             if step % args.log_every and step != args.steps:
@@ -150,6 +172,17 @@ def train_vec(args):
             print(f"step {step:7d}: episodes={s['episodes']:6d}, reward={_fmt(s['return_mean'], '9.2f')}, "
                   f"evac={_fmt(s['evac_rate'], '.2%')}, death={_fmt(s['death_rate'], '.2%')}, "
                   f"len={_fmt(s['length_mean'], '.1f')}, loss={_fmt(loss, '.4f')}, eps={tr.epsilon:.4f}")
+            if args.learn_stats:
+                ls, vs = tr.learn_summary(), tr.value_summary()
+                llog.writerow(learn_row(step, tr.learn_steps, ls, vs))
+                lf.flush()
+                print(f"              learn: q={_fmt(ls['q_mean'], '.4g')}, target={_fmt(ls['target_mean'], '.4g')}, "
+                      f"|td|={_fmt(ls['td_abs_mean'], '.4g')} (p50 {_fmt(ls['td_p50'], '.3g')}, p99 "
+                      f"{_fmt(ls['td_p99'], '.3g')}, max {_fmt(ls['td_abs_max'], '.3g')}), greedy="
+                      f"{_fmt(ls['greedy_frac'], '.2%')}, norm={_fmt(ls['grad_norm_mean'], '.4g')}, clipped="
+                      f"{_fmt(ls['clipped_frac'], '.2%')}, bad rows/steps={ls['rows_bad']}/{ls['steps_bad']}; "
+                      f"probe: n={vs['probes']}, q0={_fmt(vs['q0_mean'], '.4g')}, G={_fmt(vs['return_mean'], '.4g')}, "
+                      f"bias={_fmt(vs['bias'], '.4g')}, rmse={_fmt(vs['rmse'], '.4g')}, corr={_fmt(vs['corr'], '.3f')}")
             if s["episodes"] >= 1 and s["return_mean"] > best:
                 best = s["return_mean"]
                 torch.save(checkpoint(tr), os.path.join(out_dir, "best_model.pth"))

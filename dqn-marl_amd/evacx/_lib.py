@@ -46,6 +46,10 @@ EPISODE_REDUCE_SPAN = 1024  # EVX_EPISODE_REDUCE_SPAN: envs one pass of a reduce
 EPISODE_ROW_WORDS = 10  # sizeof(evx_episode_row) / 8
 HEALTH_ROW_WORDS = 6  # sizeof(evx_health_row) / 8
 HEALTH_MAX_P = 16383  # EVX_HEALTH_MAX_P
+LSTATS_MAX_A = 8  # EVX_LSTATS_MAX_A
+LSTATS_TD_BUCKETS = 48  # EVX_LSTATS_TD_BUCKETS
+LSTATS_WS_FIELDS = 10  # EVX_LSTATS_WS_FIELDS
+VPROBE_ROW_WORDS = 12  # sizeof(evx_vprobe_row) / 8
 
 
 # ---------------------------------------------------------------- structures
@@ -155,6 +159,19 @@ class evx_timeline(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ["E", "T", "n_rows", "n_trk"]] + \
         _ptrs("t", "p_evac", "p_dead", "n_total", "evac", "dead", "ended", "seen", "alive", "health_q", "late",
               "bad_health", "trk_env", "trk_person", "trk_pk", "trk_health", "trk_len")
+
+
+class evx_lstats(C.Structure):
+    _fields_ = [("nets", C.c_int32), ("A", C.c_int32)] + \
+        _ptrs("steps", "steps_bad", "rows", "rows_bad", "n_done", "n_greedy", "n_clipped", "act_hist", "td_hist",
+              "s_q", "s_qmax", "s_y", "s_d", "s_absd", "s_d2", "s_rew", "s_loss", "s_norm",
+              "max_absd", "max_q", "min_q", "max_loss", "max_norm")
+
+
+class evx_vprobe(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ["E", "R", "A", "pad0"]] + \
+        _ptrs("open", "q0", "g", "disc", "len", "w_n", "w_bad", "w_q", "w_g", "w_e", "w_e2", "w_q2", "w_g2", "w_qg",
+              "w_emin", "w_emax")
 
 
 # ---------------------------------------------------------------- signatures
@@ -275,6 +292,15 @@ SIGNATURES = {
     "evx_timeline_update": (C.c_int, [_P(evx_timeline)] + [_vp] * 5 + [_i32, _i64, _vp]),
     "evx_timeline_trace0": (C.c_int, [_P(evx_timeline), _vp, _vp, _i32, _vp]),
     "evx_timeline_last_error": (C.c_char_p, []),
+    "evx_lstats_ws_doubles": (C.c_int64, [_i32, _i32]),
+    "evx_lstats_init": (C.c_int, [_P(evx_lstats), _vp]),
+    "evx_lstats_update": (C.c_int, [_P(evx_lstats)] + [_vp] * 5 + [_f32, _i32, _OPTS, _vp, _vp, _f32, _vp, _vp, _i64,
+                                                                   _vp]),
+    "evx_lstats_last_error": (C.c_char_p, []),
+    "evx_vprobe_init": (C.c_int, [_P(evx_vprobe), _vp]),
+    "evx_vprobe_update": (C.c_int, [_P(evx_vprobe)] + [_vp] * 4 + [_f64, _vp]),
+    "evx_vprobe_discard": (C.c_int, [_P(evx_vprobe), _vp, _vp]),
+    "evx_vprobe_reduce": (C.c_int, [_P(evx_vprobe), _vp, _i32, _vp, _i32, _vp]),
 }
 
 _lib = None

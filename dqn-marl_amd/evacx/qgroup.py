@@ -67,9 +67,15 @@ class GroupedLearner:
     """G independent DQN learners (MLP, x3 f32-accurate) stepping together."""
 
     def __init__(self, nets: int, device="cuda", lr=1e-4, gamma=0.99, max_norm=1.0, seed=0, betas=(0.9, 0.999),
-                 eps=1e-8, init_seeds: Optional[List[int]] = None):
+                 eps=1e-8, init_seeds: Optional[List[int]] = None, stats=None):
+        """stats: an evacx.lstats.LearnStats of `nets` nets, or None: every step_optimizer() that
+        follows a learn_obs ends with one stats.update of the step's batches on its stream."""
         if not 1 <= nets <= 64:
             raise ValueError("GroupedLearner: 1..64 nets")
+        if stats is not None and (getattr(stats, "nets", None) != int(nets) or stats.A != NACT):
+            raise ValueError(f"GroupedLearner: stats must be a LearnStats of {nets} nets and A = {NACT}")
+        self.stats = stats
+        self.stat_batch = None  # stats: (Q, Qt, a, r, done, sel, gamma_row, B) of the last learn_obs
         self.G, self.device = int(nets), torch.device(device)
         self.shapes = param_shapes(layer_specs("mlp"))
         self.npar = sum(int(torch.Size(s).numel()) for s in self.shapes.values())
@@ -153,6 +159,8 @@ class GroupedLearner:
                                        self.gamma, B, G, None, dQ.data_ptr(), self.loss.data_ptr(), None,
                                        self.gflat.data_ptr(), self.gflat.numel(), tw.data_ptr(), tw.numel(),
                                        _stream()), "td_loss_zero_g")
+        if self.stats is not None:
+            self.stat_batch = (Q, Qt, a, r, done, None, None, B)
         self._backward(B, dQ, X, H1, H2)
         if update:
             self.step_optimizer()
@@ -184,6 +192,11 @@ class GroupedLearner:
                                           b["w2tl"].data_ptr(), b["w1o"].data_ptr(), b["w1ol"].data_ptr(),
                                           self._ss.data_ptr(), self.nss, self.norm.data_ptr(), self.G, _stream()),
               "qmlp_adam_pack3_g")
+        if self.stats is not None and self.stat_batch is not None:  # after Adam has written norm
+            Q, Qt, a, r, done, sel, gamma_row, B = self.stat_batch
+            n = self.G * B
+            self.stats.update(Q, Qt, a[:n], r[:n], done[:n], self.gamma, B, sel=sel, gamma_row=gamma_row,
+                              loss=self.loss, norm=self.norm, max_norm=float(self.max_norm or 0.0))
 
     def sync_target(self, nets: Optional[List[int]] = None):
         """agent.update_target_network() of the given nets (all by default)."""

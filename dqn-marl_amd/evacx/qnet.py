@@ -367,8 +367,10 @@ class Learner:
 
     def __init__(self, kind="mlp", device="cuda", lr=1e-4, gamma=0.99, max_norm=1.0, precision="f32",
                  hidden=512, actions=5, seed=0, betas=(0.9, 0.999), eps=1e-8, double_q=False, loss="mse",
-                 huber_delta=1.0, target_tau=0.0):
-        """double_q: the target bootstraps from the target net's value of the online net's greedy
+                 huber_delta=1.0, target_tau=0.0, stats=None):
+        """stats: an evacx.lstats.LearnStats of 1 net, or None: every step_optimizer() ends with one
+        stats.update of the learn step's batch on its stream (the learner's numbers do not change).
+        double_q: the target bootstraps from the target net's value of the online net's greedy
         action at s' (one more online forward per learn step); loss: "mse" or "huber" (with
         huber_delta); target_tau > 0: soft_update() blends the target towards the online net.
         None of them is the reference's; all off is DQNAgent.learn."""
@@ -377,6 +379,10 @@ class Learner:
         self.huber_delta, self.target_tau = float(huber_delta), float(target_tau)
         self.last_sel = None  # double_q: the last learn step's bootstrap actions (int32 [B], device)
         self._sel_ws = {}     # the selection act's workspaces by batch size
+        if stats is not None and (getattr(stats, "nets", None) != 1 or stats.A != actions):
+            raise ValueError(f"Learner: stats must be a LearnStats of 1 net and A = {actions}")
+        self.stats = stats
+        self.stat_batch = None  # stats: (Q, Qt, a, r, done, sel, gamma_row, B) of the last learn step
         if precision not in ("f32", "bf16", "x3", "exact"):
             raise ValueError(f"precision must be 'f32', 'bf16', 'x3' or 'exact', not {precision!r}")
         # "exact": every product on the exact-f32 MFMA GEMMs (evx_gemm f32), no fused MLP kernels
@@ -479,6 +485,8 @@ class Learner:
         dQ = self.net.ws.get("dq", (B, self.actions), torch.float32, self.device)
         tw = td_workspace(self.net.ws, B, 1, self.device)
         self._td_loss(Q, Qt, a, r, done, B, weights, dQ, td_abs, tw, sel, gamma_row)
+        if self.stats is not None:
+            self.stat_batch = (Q, Qt, a, r, done, sel, gamma_row, B)
         self.net.backward(dQ, self.grads)
         if self.grad_hook is not None:
             self.grad_hook(self.grads.flat)
@@ -548,6 +556,8 @@ class Learner:
             self.fast.act(lay_c, s2_obs, B, drop=(self.seed, self.drop_stream + 2, DROPOUT_P, mask_select, drop_row0),
                           actions=sel, epsilon=0.0, ws=sws)
             self.last_sel = sel
+        if self.stats is not None:
+            self.stat_batch = (Q, Qt, a, r, done, sel, gamma_row, B)
         type(self.fast).forward_pair(*pair)
         if self.fused_opt:
             # the TD step inside the backward's first kernel, the gradients overwritten by its ordered
@@ -579,6 +589,8 @@ class Learner:
                          step=self.adam_step)
             self.fast.adam_step(self.online.flat, self.grads.flat, self.m, self.v, float(self.max_norm or 0.0), h,
                                 self._ss, self.norm)
+            if self.stats is not None:
+                self._stats_update()
             return
         check(L.evx_sumsq_norm(_p(self.grads.flat), n, _p(self.scratch), self.scratch.numel(), _p(self.norm),
                                _stream()), "sumsq")
@@ -590,6 +602,18 @@ class Learner:
                               _stream()), "clip_adam")
         if self.fast is not None:
             self.fast.repack()  # bf16 copies follow the fp32 master parameters
+        if self.stats is not None:
+            self._stats_update()
+
+    def _stats_update(self):
+        """The learn step's batch into the statistics, after Adam has written norm: the buffers the
+        step used are the learner's own until the next learn on this stream."""
+        if self.stat_batch is None:
+            return
+        Q, Qt, a, r, done, sel, gamma_row, B = self.stat_batch
+        self.stats.update(Q, Qt, a[:B], r[:B], done[:B], self.gamma, B, sel=sel,
+                          gamma_row=None if gamma_row is None else gamma_row[:B], loss=self.loss, norm=self.norm,
+                          max_norm=float(self.max_norm or 0.0))
 
     def m_view(self, name: str) -> torch.Tensor:
         """Adam first moment of one parameter (torch's optimizer.state[p]["exp_avg"])."""

@@ -139,6 +139,8 @@ class _Group:
         self.perm = None  # the act's env order over this group's envs (x3 table path), or None
         self.act_ws = None  # the x3 act's workspace (evx_qmlp_fwd_out.act_ws), made at the first act
         self.ep = None  # this group's envs of the trainer's EpisodeStats (episode_stats=True), or None
+        self.probe = None  # this group's envs of the trainer's ValueProbe (value_probe=True), or None
+        self.q = None  # value_probe: this group's rows of the act's Q output [n][5]
 
 
 class VecTrainer:
@@ -151,7 +153,7 @@ class VecTrainer:
                  prio_eps: float = 1e-6, groups: int = 1, layout_of=None, world_envs: Optional[int] = None,
                  nets: str = "shared", act_table: Optional[bool] = None, episode_stats: bool = False,
                  double_q: bool = False, loss: str = "mse", huber_delta: float = 1.0, target_tau: float = 0.0,
-                 n_step: int = 1):
+                 n_step: int = 1, learn_stats: bool = False, value_probe: bool = False):
         """groups: the envs are split into this many parts, each stepping on its own
         stream chain (see _Group), group g's act after group g - 1's (it overlaps that
         group's env.step); neither the env results nor the act's dropout masks (one stream
@@ -178,7 +180,17 @@ class VecTrainer:
         launch after the sampler's, on its stream: r = the discounted return of up to n_step
         rewards of the same env and robot, s2 / done the chain's last slot's, the discount per row
         in samp["gamma_row"], the chain lengths in samp["nlen"]); under every sampler and both
-        schedules. nets="shared", groups=1 and no step(extra_reset=...). 1: nothing of it runs."""
+        schedules. nets="shared", groups=1 and no step(extra_reset=...). 1: nothing of it runs.
+        learn_stats: the learner folds every learn step's batch into an evacx.lstats.LearnStats (two
+        launches after clip + Adam, on its stream) for learn_summary(); nets="shared" (1 net) or
+        "per_robot" (R nets), not "qmix" (the target there is the mixer's).
+        value_probe: the act also writes its Q rows, and an evacx.lstats.ValueProbe pairs the Q of
+        the actions taken at every episode's first step with the episode's discounted return (one
+        more launch per group and step, where the episode statistics' runs) for value_summary();
+        every nets mode. Both off: nothing is allocated or launched for them; on, the training
+        itself is the same bit for bit."""
+        if learn_stats and nets == "qmix":
+            raise ValueError("learn_stats needs nets='shared' or 'per_robot': the QMIX target is the mixer's")
         validate_td_options(loss, huber_delta, target_tau)
         self.target_tau = float(target_tau)
         if not (isinstance(n_step, int) and 1 <= n_step <= NSTEP_MAX):
@@ -218,7 +230,12 @@ class VecTrainer:
             if batch % (2 * self.R) or replay_capacity % self.R:
                 raise ValueError("per_robot nets: batch a multiple of 2 R, replay capacity a multiple of R")
             from .qgroup import GroupedLearner, GroupedQMix
-            self.glearner = GroupedLearner(self.R, self.device, lr=lr, gamma=gamma, seed=learner_seed)
+            self.learn_stats = None
+            if learn_stats:
+                from .lstats import LearnStats
+                self.learn_stats = LearnStats(self.R, self.device)
+            self.glearner = GroupedLearner(self.R, self.device, lr=lr, gamma=gamma, seed=learner_seed,
+                                           stats=self.learn_stats)
             # qmix: the R robots of an env are the agents of runners/train_qmix.py -- joint samples
             # (the same env-steps for every agent), the mixer's loss over the team reward
             self.qmix = GroupedQMix(self.glearner, seed=learner_seed) if nets == "qmix" else None
@@ -226,9 +243,14 @@ class VecTrainer:
         # convolutions, bf16 hi/lo operand pairs); "bf16"; "exact" -- every product on the exact-f32
         # MFMA GEMMs (evx_gemm f32, no fused kernels: the golden-test path, either kind)
         lprec = "x3" if (kind == "conv" and precision == "f32") else precision
+        if not self.per_robot:
+            self.learn_stats = None
+            if learn_stats:
+                from .lstats import LearnStats
+                self.learn_stats = LearnStats(1, self.device)
         self.learner = Learner(kind=kind, device=self.device, lr=lr, gamma=gamma, precision=lprec,
                                seed=learner_seed, double_q=double_q, loss=loss, huber_delta=huber_delta,
-                               target_tau=target_tau) if not self.per_robot else None
+                               target_tau=target_tau, stats=self.learn_stats) if not self.per_robot else None
         # the arithmetic the Q-network actually runs: "x3" (f32 operands as bf16 hi + lo pairs on the
         # bf16 MFMA, f32 accumulation: f32 within the tests' stated tolerances), "f32" (exact f32
         # MFMA) or "bf16" -- read from what the learner built
@@ -277,6 +299,18 @@ class VecTrainer:
                                          n_layouts=len(layout) if isinstance(layout, LayoutSet) else 1)
             for grp in self.groups:
                 grp.ep = self.episodes.view(grp.g * grp.env.E, grp.env.E) if len(parts) > 1 else self.episodes
+        # the value probe (evacx.lstats.ValueProbe) and the act's Q rows it reads, or None
+        self.probe = self.act_q = None
+        if value_probe:
+            from .env import LayoutSet
+            from .lstats import ValueProbe
+            self.probe = ValueProbe(E, self.R, self.device, gamma, layout_idx=self.env.layout_idx,
+                                    n_layouts=len(layout) if isinstance(layout, LayoutSet) else 1)
+            self.act_q = torch.zeros(E * self.R * 5, dtype=torch.float32, device=self.device)
+        for grp in self.groups:
+            if self.probe is not None:
+                grp.probe = self.probe.view(grp.g * grp.env.E, grp.env.E) if len(parts) > 1 else self.probe
+                grp.q = self.act_q[grp.row0 * 5:(grp.row0 + grp.n) * 5]
         self.samp = dict(s=torch.zeros(batch * OBS_WORDS, dtype=torch.int32, device=self.device),
                          s2=torch.zeros(batch * OBS_WORDS, dtype=torch.int32, device=self.device),
                          a=torch.zeros(batch, dtype=torch.int32, device=self.device),
@@ -348,22 +382,24 @@ class VecTrainer:
         g0 = self.agent0 + grp.row0  # global agent id of the group's first robot
         off = self.t * self.n_world + g0
         if self.per_robot:  # robot r of every env through net r, one launch
-            self.glearner.act(self.lay.c, grp.env.obs, grp.env.E, actions=grp.actions, epsilon=float(self.epsilon),
-                              act_seed=self.act_seed, act_offset=off)
+            self.glearner.act(self.lay.c, grp.env.obs, grp.env.E, actions=grp.actions, q=grp.q,
+                              epsilon=float(self.epsilon), act_seed=self.act_seed, act_offset=off)
             return
         if self.fast is not None:  # one mask stream per step (act_streams), rows keyed by global agent id
             if grp.act_ws is None and act_ws_ints(grp.n) > 0:  # the persistent act's list of tiles off the table path
                 grp.act_ws = torch.zeros(act_ws_ints(grp.n), dtype=torch.int32, device=self.device)
             self.fast.act(self.lay.c, grp.env.obs, grp.n,
                           drop=(self.learner.seed, self.learner.drop_stream, DROPOUT_P, None, g0),
-                          actions=grp.actions, epsilon=float(self.epsilon), act_seed=self.act_seed, act_offset=off,
-                          perm=grp.perm, rows_per_env=0 if grp.perm is None else self.R, ws=grp.act_ws)
+                          q=grp.q, actions=grp.actions, epsilon=float(self.epsilon), act_seed=self.act_seed,
+                          act_offset=off, perm=grp.perm, rows_per_env=0 if grp.perm is None else self.R, ws=grp.act_ws)
             return
         x = grp.env.expand_obs(torch.float32)  # [E/G, R, 11, 11, 6]
         # per-group scratch: the groups' acts run concurrently on their own streams
         Q = self.learner.q_values(x.view(grp.n, 11, 11, 6), train=True, tag=f"act{grp.g}" if grp.g else "act")
         check(lib().evx_act(Q.data_ptr(), grp.n, self.learner.actions, float(self.epsilon), self.act_seed, off,
                             grp.actions.data_ptr(), _stream()), "act")
+        if grp.q is not None:  # the probe's Q rows (the forward's scratch is rewritten by the next act)
+            grp.q.copy_(Q.reshape(-1))
 
     def _act_stream(self):
         """A fresh dropout mask stream for this step's act: every group's act draws from it (rows keyed
@@ -550,6 +586,8 @@ class VecTrainer:
                     ev_env[1].record(grp.main)
                 if grp.ep is not None:  # before this stream's next step overwrites reward / done / counts
                     grp.ep.update(grp.env.reward, grp.env.done, grp.env.counts)
+                if grp.probe is not None:  # before this stream's next act overwrites its Q rows
+                    grp.probe.update(grp.q, grp.actions, grp.env.reward, grp.env.done)
                 if fused:
                     # the strict schedule's learn batch drawn in the same launch (the ring after this push;
                     # not with n_step > 1: that draw leaves no slot indices)
@@ -580,6 +618,8 @@ class VecTrainer:
                 self.env.reset(mask=mask)
                 if self.episodes is not None:  # after every group's update (ev_push): their partial episodes end here
                     self.episodes.discard(mask)
+                if self.probe is not None:  # their probes close without a pair
+                    self.probe.discard(mask)
                 if len(G) > 1:
                     for grp in G:  # the orders again, with the reset envs' new classes
                         grp.env.compute_orders(perm=grp.perm)
@@ -622,6 +662,22 @@ class VecTrainer:
             raise RuntimeError("episode_summary: the trainer was made with episode_stats=False")
         self.sync()
         return self.episodes.summary(clear=clear)
+
+    def learn_summary(self, clear: bool = True) -> dict:
+        """sync(), then the learn-batch statistics of the learn steps since the last clearing call
+        (LearnStats.summary). Waits for the device; not part of a step."""
+        if self.learn_stats is None:
+            raise RuntimeError("learn_summary: the trainer was made with learn_stats=False")
+        self.sync()
+        return self.learn_stats.summary(clear=clear)
+
+    def value_summary(self, clear: bool = True) -> dict:
+        """sync(), then the value probe's window (ValueProbe.summary: probes, bad, open, q0_mean,
+        return_mean, bias, rmse, corr, err_min, err_max, per_layout). Waits for the device."""
+        if self.probe is None:
+            raise RuntimeError("value_summary: the trainer was made with value_probe=False")
+        self.sync()
+        return self.probe.summary(clear=clear)
 
     def sync(self):
         """Make the current stream wait for all work of the steps so far. step() runs on

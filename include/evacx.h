@@ -948,6 +948,133 @@ int evx_timeline_update(const evx_timeline *tl, const int32_t *counts, const uin
 int evx_timeline_trace0(const evx_timeline *tl, const int32_t *pk, const double *health, int32_t P, void *stream);
 const char *evx_timeline_last_error(void);
 
+/* ---- Learner diagnostics (csrc/lstats.hip): what Double-Q, the Huber loss and the soft target
+ * exist to control -- the Q-values, targets and TD errors of the sampled batches, the loss and the
+ * pre-clip gradient norm -- accumulated on the device over a window of learn steps, and a value
+ * probe that pairs the act's Q at an episode's first step with the discounted return the episode
+ * then obtains. Neither has a counterpart in the reference (its loop prints the episode reward).
+ * Both only read the learner's and the env's buffers. All arrays are the caller's device arrays. */
+#define EVX_LSTATS_MAX_A 8
+#define EVX_LSTATS_TD_BUCKETS 48
+/* doubles one 256-row block leaves in the workspace: the sums of q, qmax, y, d, |d|, d d, rew,
+ * then the largest |d|, the largest qmax and the smallest Q */
+#define EVX_LSTATS_WS_FIELDS 10
+typedef struct {
+    int32_t nets;          /* 1..64 */
+    int32_t A;             /* actions per row, 1..EVX_LSTATS_MAX_A */
+    /* per net [nets] */
+    int64_t *steps;        /* updates (learn steps) in the window */
+    int64_t *steps_bad;    /* those whose loss or norm was not finite */
+    int64_t *rows;         /* batch rows seen */
+    int64_t *rows_bad;     /* those with a non-finite q, qmax or y: counted here and nowhere else */
+    int64_t *n_done;       /* good rows with done != 0 */
+    int64_t *n_greedy;     /* good rows whose action is the first maximum of their Q row */
+    int64_t *n_clipped;    /* good steps with max_norm > 0 and norm > max_norm */
+    int64_t *act_hist;     /* [nets][EVX_LSTATS_MAX_A]: good rows by (clamped) action */
+    int64_t *td_hist;      /* [nets][EVX_LSTATS_TD_BUCKETS]: good rows by the octave of |d| */
+    double *s_q, *s_qmax, *s_y, *s_d, *s_absd, *s_d2, *s_rew; /* sums over good rows */
+    double *s_loss, *s_norm;                                  /* sums over good steps */
+    double *max_absd, *max_q, *min_q, *max_loss, *max_norm;   /* -inf (min_q: +inf) when empty */
+} evx_lstats;
+
+/* doubles of workspace one evx_lstats_update of B rows per net needs:
+ * nets * ceil(B / 256) * EVX_LSTATS_WS_FIELDS (0 when B < 1 or nets < 1) */
+int64_t evx_lstats_ws_doubles(int32_t B, int32_t nets);
+/* Empties the window: counts 0, sums 0.0, max_* -inf, min_q +inf (one launch). */
+int evx_lstats_init(const evx_lstats *ls, void *stream);
+/* One learn step's batch folded into the window. Net g's rows are [g B, (g + 1) B) of Q / Qt
+ * ([.][A] f32), act, rew, done, opt->sel, opt->gamma_row and d_out (the blocked layout of
+ * evx_qmlp_forward2_g and evx_td_loss_opt). Per row, all f32 and not contracted -- the TD kernels'
+ * expressions (above evx_td_opts), without the importance weights; opt = NULL: no options,
+ * opt->huber_delta is ignored:
+ *   a    = clamp(act[i], 0, A - 1);  q = Q[i][a]
+ *   qmax, jmax = the first maximum of Q[i][0..A-1] (strict > while scanning j = 1..A-1);
+ *   qmin likewise the first minimum (strict <)
+ *   j*   = sel ? clamp(sel[i], 0, A - 1) : the first maximum's index of Qt[i][.]
+ *   y    = rew[i] + ((gamma_row ? gamma_row[i] : gamma) * Qt[i][j*]) * (done[i] ? 0 : 1)
+ *   d    = q - y;   bad = !(isfinite(q) && isfinite(qmax) && isfinite(y))
+ * Every row counts in rows; a bad row in rows_bad and nowhere else; a good row adds the f64 values
+ * of q, qmax, y, d, |d|, d d (the f64 product of the f64 values) and rew to the sums, done != 0 to
+ * n_done, act[i] == jmax to n_greedy, 1 to act_hist[a], 1 to td_hist[k] with
+ * k = min(max((bits(|d|) >> 23) - 103, 0), 47) (bucket k >= 1: 2^(k-24) <= |d| < 2^(k-23); bucket 0:
+ * everything below 2^-23; bucket 47: everything from 2^23), and |d|, qmax, qmin to max_absd, max_q,
+ * min_q. d_out (optional, [nets][B]): the row's d, NaN for a bad row.
+ * Summation order of every f64 sum: net g's rows are cut into blocks of 256; thread t of a block
+ * holds row t's value, 0.0 for a bad row or a row beyond B; s[t] = s[t] + s[t + h] for h = 128, 64,
+ * ..., 1; the block sums are added in ascending block order onto 0.0 and that step total is added
+ * to the window's accumulator. No float atomics; the integer counts are added with integer atomics.
+ * Two launches: the rows kernel leaves each block's EVX_LSTATS_WS_FIELDS doubles in ws
+ * (ws_doubles >= evx_lstats_ws_doubles(B, nets)), then one workgroup per net adds them in order.
+ * That second launch also takes the step: steps += 1; with l = loss[g], n = norm[g] (f32 device
+ * scalars per net, each optional; a NULL one leaves its fields alone and counts as finite): both
+ * finite: s_loss += l, s_norm += n, max_loss, max_norm, n_clipped += (max_norm > 0 && n > max_norm);
+ * otherwise steps_bad += 1.
+ * -22 with a message, before any launch: a NULL descriptor, descriptor array, Q, Qt, act, rew, done
+ * or ws; nets outside 1..64; A outside 1..EVX_LSTATS_MAX_A; B < 1; nets * B beyond 2^31 - 1; ws_doubles
+ * too small; gamma not finite. */
+int evx_lstats_update(const evx_lstats *ls, const float *Q, const float *Qt, const int32_t *act, const float *rew,
+                      const uint8_t *done, float gamma, int32_t B, const evx_td_opts *opt, const float *loss,
+                      const float *norm, float max_norm, float *d_out, double *ws, int64_t ws_doubles, void *stream);
+const char *evx_lstats_last_error(void);
+
+/* The value probe, per env [E] like evx_episodes (a part of the envs is a descriptor whose pointers
+ * are offset to its first env): at the first step of every episode the mean over the env's R robots
+ * of the Q-value the act computed for the action taken is kept with the discounted return the
+ * episode goes on to obtain; at done the pair is folded into the window. */
+typedef struct {
+    int32_t E;
+    int32_t R;             /* robots (act rows) per env */
+    int32_t A;             /* actions per Q row, 1..EVX_LSTATS_MAX_A */
+    int32_t pad0;
+    /* the probe in progress */
+    uint8_t *open;         /* 1 while the env's episode has a probe */
+    double *q0;            /* the act's value at the episode's first step */
+    double *g;             /* the discounted return so far */
+    double *disc;          /* gamma^len */
+    int32_t *len;          /* steps so far */
+    /* the window: probes folded since the last clear */
+    int64_t *w_n;          /* probes with a finite q0 */
+    int64_t *w_bad;        /* probes whose q0 was not finite (counted here and nowhere else) */
+    double *w_q, *w_g;     /* sums of q0, of g */
+    double *w_e, *w_e2;    /* sums of err = q0 - g, of err err */
+    double *w_q2, *w_g2, *w_qg; /* sums of q0 q0, g g, q0 g */
+    double *w_emin, *w_emax;    /* smallest / largest err (+inf / -inf when empty) */
+} evx_vprobe;
+
+/* One row of evx_vprobe_reduce: the window summed over a set of envs. */
+typedef struct {
+    int64_t probes, bad;
+    int64_t open;          /* envs of the row whose probe is in progress */
+    double q_sum, g_sum, e_sum, e2_sum, q2_sum, g2_sum, qg_sum, e_min, e_max;
+} evx_vprobe_row;
+
+/* No probe in progress, empty window (one launch). */
+int evx_vprobe_init(const evx_vprobe *vp, void *stream);
+/* One step of every env of vp, one launch, one thread per env. Q [E R][A] f32 and act [E R] are
+ * those of the step whose reward [E] f64 and done [E] are passed (the act's Q of the observation the
+ * action was chosen from). Per env e, all f64 and not contracted:
+ *   if !open[e]:  s = 0.0; for r = 0..R-1: s = s + (double)Q[e R + r][clamp(act[e R + r], 0, A - 1)]
+ *                 q0 = s / R;  g = 0;  disc = 1;  len = 0;  open = 1
+ *   g = g + disc * reward[e];  disc = disc * gamma;  len += 1
+ *   if done[e]:   !isfinite(q0): w_bad += 1
+ *                 else: err = q0 - g; w_n += 1; w_q += q0; w_g += g; w_e += err; w_e2 += err * err;
+ *                       w_q2 += q0 * q0; w_g2 += g * g; w_qg += q0 * g; w_emin, w_emax take err
+ *                 open = 0
+ * -22 with a message, before any launch: a NULL descriptor, descriptor array, Q, act, reward or done;
+ * E, R or A < 1; A > EVX_LSTATS_MAX_A; gamma not finite or outside [0, 1]. */
+int evx_vprobe_update(const evx_vprobe *vp, const float *Q, const int32_t *act, const double *reward,
+                      const uint8_t *done, double gamma, void *stream);
+/* Closes the probes of the envs with mask[e] != 0 (NULL: all) without folding them: for envs reset
+ * from outside the step. */
+int evx_vprobe_discard(const evx_vprobe *vp, const uint8_t *mask, void *stream);
+/* The window summed over envs into out[0 .. n_layouts] (rows as in evx_episode_reduce) in
+ * evx_episode_reduce's fixed order: thread t of EVX_EPISODE_REDUCE_SPAN adds the row's envs t,
+ * t + SPAN, ... ascending onto 0.0 (envs of other layouts are skipped), then the thread sums are added
+ * pairwise, s[t] = s[t] + s[t + h] for h = SPAN/2, ..., 1. Integer fields are exact. clear != 0: the
+ * window arrays are emptied by a second launch; the probes in progress stay. */
+int evx_vprobe_reduce(const evx_vprobe *vp, const int32_t *layout_idx, int32_t n_layouts, evx_vprobe_row *out,
+                      int32_t clear, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
