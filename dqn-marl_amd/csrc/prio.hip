@@ -118,12 +118,17 @@ __global__ __launch_bounds__(NT) void prio_leaf_kernel(evx_prio t, const int64_t
     if (k >= B) return;
     const int64_t j = idx[k];
     const double p = pow((double)td_abs[k] + eps, alpha);
-    // every priority counts for the max (a sequential loop sees them all); non-negative
+    // a priority that is not finite (|TD| NaN or +inf) changes neither max_leaf nor a leaf: as a
+    // bit pattern a NaN would win the max, and every slot pushed from then on would take it
+    const bool ok = isfinite(p);
+    // every finite priority counts for the max (a sequential loop sees them all); non-negative
     // doubles order like their bit patterns
-    atomicMax(reinterpret_cast<unsigned long long*>(t.max_leaf), (unsigned long long)__double_as_longlong(p));
+    if (ok) atomicMax(reinterpret_cast<unsigned long long*>(t.max_leaf), (unsigned long long)__double_as_longlong(p));
     if (t.owner[j] != k) return;  // not the owner (or the owner already cleared it)
-    t.sum[t.capacity + j] = p;
-    t.mn[t.capacity + j] = p;
+    if (ok) {  // (a non-finite last row still owns its slot: the slot keeps its old leaf)
+        t.sum[t.capacity + j] = p;
+        t.mn[t.capacity + j] = p;
+    }
     t.owner[j] = -1;
 }
 

@@ -418,7 +418,11 @@ int evx_prio_init(const evx_prio *t, void *stream);
  * rebuilt over the touched leaf blocks. n_new + n_hide <= C. */
 int evx_prio_set_range(const evx_prio *t, int64_t pos, int64_t n_new, int64_t n_hide, void *stream);
 /* Leaf idx[k] = (td_abs[k] + eps)^alpha for k = 0..B-1 (a later k wins over an earlier
- * one with the same slot, as a sequential loop), max_leaf updated, trees rebuilt. */
+ * one with the same slot, as a sequential loop), max_leaf updated, trees rebuilt.
+ * A row whose priority is not finite (td_abs NaN or +inf) leaves its slot's leaf and max_leaf
+ * as they were. It still takes part in ownership: the last row naming a slot owns it, so a slot
+ * whose last row is not finite keeps the leaf it had before the call. The trees therefore stay
+ * finite whatever the learner's |TD| holds. owner is all -1 again when the call has run. */
 int evx_prio_update(const evx_prio *t, const int64_t *idx, const float *td_abs, int32_t B, double eps,
                     double alpha, void *stream);
 /* Stratified proportional sampling: for k = 0..B-1, u = (k + U_k) * (total / B) with U_k a

@@ -9,6 +9,7 @@
  * tests/test_prio_cpu.py. Only tests/ may call this. */
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
     uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
@@ -52,12 +53,20 @@ void orc_prio_set_range(double *sum, double *mn, int64_t C, const double *max_le
 
 void orc_prio_update(double *sum, double *mn, int64_t C, double *max_leaf, const int64_t *idx, const float *td_abs,
                      int B, double eps, double alpha) {
+    /* the last row naming a slot owns it; a row whose priority is not finite (|TD| NaN or +inf)
+     * changes neither its slot's leaf nor max_leaf, so a slot whose last row is such a row keeps
+     * the leaf it had before the call (not an earlier row's value) */
+    int32_t *last = (int32_t *)calloc((size_t)C, sizeof(int32_t)); /* 1 + the last row naming the slot */
+    for (int k = 0; k < B; k++) last[idx[k]] = k + 1;
     for (int k = 0; k < B; k++) {
         const double p = pow((double)td_abs[k] + eps, alpha);
+        if (!isfinite(p)) continue;
+        if (p > *max_leaf) *max_leaf = p;
+        if (last[idx[k]] != k + 1) continue;
         sum[C + idx[k]] = p;
         mn[C + idx[k]] = p;
-        if (p > *max_leaf) *max_leaf = p;
     }
+    free(last);
     rebuild_all(sum, mn, C);
 }
 
