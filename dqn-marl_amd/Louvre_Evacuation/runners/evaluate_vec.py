@@ -18,6 +18,12 @@ evacuated and dead, episodes running, mean evacuated / dead / remaining, average
 ``tracked_<strategy>.npz`` (the first N persons of env 0, step by step) and
 ``evaluation_<strategy>.png`` (``utils.visualization.plot_evaluation``; needs matplotlib).
 
+``--maps`` adds where it happened (``evaluate(maps=True)``): per strategy ``maps_<strategy>.npz``
+(per grid cell the persons that arrived, stalled, left through an exit or died there and the
+robots' positions, with occupancy, density and the stall ratio; summed over the layouts), one
+printed line with the exits' shares and the worst stall cell, and with ``--plot``
+``maps_<strategy>.png`` (``utils.visualization.plot_maps``).
+
 The reference's "no robot" strategy is not offered: it parks the robot at (1000, 1000), and
 the vector kernels' tables are padded by 6 cells only, so they must not be fed off-grid
 positions.
@@ -36,6 +42,8 @@ if project_root not in sys.path:
 import torch  # noqa: E402
 import yaml  # noqa: E402
 
+MAPS_KEYS = ["arrive", "stall", "evac", "died", "robot", "occupancy", "density", "stall_ratio", "steps", "episodes",
+             "bad", "exit_use", "hotspots"]
 CSV_COLUMNS = ["strategy", "avg_health", "death_rate", "evac_rate", "avg_time", "episodes"]
 CURVE_COLUMNS = ["step", "time_s", "new_evacuated", "new_dead", "ended", "running", "evacuated_mean", "dead_mean",
                  "remaining_mean", "avg_health"]
@@ -60,7 +68,10 @@ def build_parser():
                     help="write curves_<strategy>.csv: one row per step (evacuated, dead, remaining, avg health ...)")
     ap.add_argument("--track", type=int, default=0, metavar="N",
                     help="write tracked_<strategy>.npz: the first N persons of env 0, step by step")
-    ap.add_argument("--plot", action="store_true", help="write evaluation_<strategy>.png (needs matplotlib)")
+    ap.add_argument("--maps", action="store_true",
+                    help="write maps_<strategy>.npz: occupancy, stalls, exit use, deaths and robot positions per cell")
+    ap.add_argument("--plot", action="store_true",
+                    help="write evaluation_<strategy>.png, and with --maps maps_<strategy>.png (needs matplotlib)")
     return ap
 
 
@@ -160,6 +171,50 @@ def write_outputs(args, out_dir, name, ev, spec):
         print(f"{name}: figure written to {path}")
 
 
+def maps_arrays(maps) -> dict:
+    """The arrays of maps_<strategy>.npz (MAPS_KEYS) from ``evaluate(maps=True)["maps"]``: the entry
+    summed over the layouts; ``exit_use`` rows (x, y, count, share) and ``hotspots`` rows (x, y, stall)
+    as float64 / int64 tables."""
+    import numpy as np
+    m = maps["sum"]
+    out = {k: np.asarray(m[k]) for k in MAPS_KEYS[:10]}
+    out["bad"] = np.asarray(maps["bad"])
+    out["exit_use"] = np.asarray(m["exit_use"], np.float64).reshape(-1, 4)
+    out["hotspots"] = np.asarray(m["hotspots"], np.int64).reshape(-1, 3)
+    return out
+
+
+def maps_line(name, maps) -> str:
+    """One line: every exit cell's share of the evacuated, and the cell where most persons stalled."""
+    m = maps["sum"]
+    use = m["exit_use"]
+    exits = ", ".join(f"({x},{y}) {share:.1%}" for x, y, _, share in use[:8]) or "nobody evacuated"
+    if len(use) > 8:
+        exits += f", {len(use) - 8} more cells"
+    hot = m["hotspots"]
+    top = f"({hot[0][0]},{hot[0][1]}) with {hot[0][2]} person-steps" if hot else "none"
+    return f"{name}: exit use {exits}; top stall cell {top}"
+
+
+def write_maps(args, out_dir, name, ev, spec):
+    """The per-strategy files --maps asks for, and its line."""
+    import numpy as np
+    path = os.path.join(out_dir, f"maps_{name}.npz")
+    np.savez(path, **maps_arrays(ev["maps"]))
+    print(maps_line(name, ev["maps"]))
+    print(f"{name}: maps written to {path}")
+    if args.plot:
+        try:
+            import matplotlib  # noqa: F401
+        except ImportError:
+            print(f"{name}: --plot needs matplotlib, which is not installed; no map figure written")
+            return
+        from Louvre_Evacuation.utils.visualization import plot_maps
+        path = plot_maps(ev["maps"], os.path.join(out_dir, f"maps_{name}.png"), layout=spec,
+                         title=f"{name}: {ev['episodes']} episodes")
+        print(f"{name}: map figure written to {path}")
+
+
 def evaluate_vec(args):
     from evacx.env import DeviceLayout
     from evacx.evaluate import evaluate
@@ -182,6 +237,8 @@ def evaluate_vec(args):
         raise ValueError(f"--track must be 0..{lay.P}")
     timeline = bool(args.curves or args.track or args.plot)
     extra = dict(timeline=True, track=args.track or None) if timeline else {}
+    if args.maps:
+        extra["maps"] = True
     rows = []
     for name, policy, learner in strategies(args, lay.R, device):
         ev = evaluate(lay, args.envs, args.episodes, policy, learner=learner, seed_base=args.seed_base,
@@ -189,6 +246,8 @@ def evaluate_vec(args):
         rows.append(table_row(name, ev))
         if timeline:
             write_outputs(args, out_dir, name, ev, spec)
+        if args.maps:
+            write_maps(args, out_dir, name, ev, spec)
     print(f"{'strategy':<10} {'avg health':>10} {'death rate':>10} {'evac rate':>10} {'avg time':>9} {'episodes':>9}")
     for name, health, death, evac, time, n in rows:
         print(f"{name:<10} {_fmt(health, '10.2f')} {_fmt(death, '10.2%')} {_fmt(evac, '10.2%')} "

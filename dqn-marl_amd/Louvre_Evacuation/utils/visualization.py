@@ -135,3 +135,37 @@ def plot_evaluation(result, save_path, layout=None, title=None):
     fig.savefig(save_path, dpi=100, format="png")
     plt.close(fig)
     return save_path
+
+
+def plot_maps(result, save_path, layout=None, title=None, row="sum"):
+    """Four heat maps of one vector evaluation (``evacx.evaluate(..., maps=True)``'s result, or its
+    ``maps``), written to ``save_path`` as a PNG: mean persons per cell and step (density), the
+    share of them that stood still (stall ratio), where people died, and where the robots were;
+    the exit cells carry their share of the evacuated. ``row`` picks a layout's entry instead of
+    the sum; ``layout`` (``exit``) marks the configured exit."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    import numpy as np
+    m = result.get("maps", result)[row]
+    spec = getattr(layout, "spec", layout)
+    panels = (("density", "persons per cell and step", "viridis"), ("stall_ratio", "stall ratio", "magma"),
+              ("died", "deaths", "Reds"), ("robot", "robot steps", "Blues"))
+    fig, axes = plt.subplots(2, 2, figsize=(12, 9))
+    for ax, (key, name, cmap) in zip(axes.reshape(-1), panels):
+        a = np.asarray(m[key], np.float64).T  # [y][x]: x to the right, y upwards
+        im = ax.imshow(a, origin="lower", cmap=cmap, interpolation="nearest")
+        fig.colorbar(im, ax=ax, shrink=0.8)
+        if spec is not None:
+            ax.plot([spec.exit[0]], [spec.exit[1]], marker="s", mfc="none", color="tab:green", ms=9, ls="")
+        ax.set_title(name)
+        ax.set_xlabel("x")
+        ax.set_ylabel("y")
+    for x, y, _, share in m["exit_use"]:
+        axes[0, 0].annotate(f"{share:.0%}", (x, y), color="white", fontsize=7, ha="center", va="center")
+    if title:
+        fig.suptitle(f"{title} ({m['steps']} env-steps)")
+    fig.tight_layout()
+    fig.savefig(save_path, dpi=100, format="png")
+    plt.close(fig)
+    return save_path

@@ -50,6 +50,8 @@ LSTATS_MAX_A = 8  # EVX_LSTATS_MAX_A
 LSTATS_TD_BUCKETS = 48  # EVX_LSTATS_TD_BUCKETS
 LSTATS_WS_FIELDS = 10  # EVX_LSTATS_WS_FIELDS
 VPROBE_ROW_WORDS = 12  # sizeof(evx_vprobe_row) / 8
+SPATIAL = {"LDS": 1, "BANDS": 2}  # EVX_SPATIAL_*: how evx_spatial_update counts the dense maps
+SPATIAL_MAX_GRID = 4096  # the largest GX, GY evx_spatial_update takes
 
 
 # ---------------------------------------------------------------- structures
@@ -159,6 +161,17 @@ class evx_timeline(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ["E", "T", "n_rows", "n_trk"]] + \
         _ptrs("t", "p_evac", "p_dead", "n_total", "evac", "dead", "ended", "seen", "alive", "health_q", "late",
               "bad_health", "trk_env", "trk_person", "trk_pk", "trk_health", "trk_len")
+
+
+class evx_spatial(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ["E", "P", "R", "GX", "GY", "n_rows"]] + \
+        _ptrs("prev", "n_total", "arrive", "stall", "evac", "died", "robot", "steps", "bad")
+
+
+class evx_spatial_launch(C.Structure):
+    """The launch shape of evx_spatial_update (evx_spatial_plan)."""
+    _fields_ = [(n, C.c_int32) for n in ["route", "bands", "band_w", "band_cells", "lds_bytes", "envs_per_wg",
+                                        "threads", "launches"]]
 
 
 class evx_lstats(C.Structure):
@@ -292,6 +305,11 @@ SIGNATURES = {
     "evx_timeline_update": (C.c_int, [_P(evx_timeline)] + [_vp] * 5 + [_i32, _i64, _vp]),
     "evx_timeline_trace0": (C.c_int, [_P(evx_timeline), _vp, _vp, _i32, _vp]),
     "evx_timeline_last_error": (C.c_char_p, []),
+    "evx_spatial_init": (C.c_int, [_P(evx_spatial), _vp]),
+    "evx_spatial_sync": (C.c_int, [_P(evx_spatial), _vp, _vp, _vp]),
+    "evx_spatial_update": (C.c_int, [_P(evx_spatial)] + [_vp] * 4 + [_i64, _vp]),
+    "evx_spatial_plan": (C.c_int, [_i32] * 4 + [_P(evx_spatial_launch)]),
+    "evx_spatial_last_error": (C.c_char_p, []),
     "evx_lstats_ws_doubles": (C.c_int64, [_i32, _i32]),
     "evx_lstats_init": (C.c_int, [_P(evx_lstats), _vp]),
     "evx_lstats_update": (C.c_int, [_P(evx_lstats)] + [_vp] * 5 + [_f32, _i32, _OPTS, _vp, _vp, _f32, _vp, _vp, _i64,

@@ -10,7 +10,8 @@ over-represented), and looks at the device only every ``check_every`` steps.
 (EvacuationEnv.get_performance_metrics, envs/evacuation_env.py:290-309) through
 ``evacx.health.HealthStats``; ``timeline=True`` adds the per-step evacuation curves and tracked
 persons of the reference's recorded evaluation episode (``evacx.timeline.Timeline``);
-``policy="greedy"`` also takes one network per robot (a
+``maps=True`` adds where it happened -- occupancy, stalls, exit use, deaths and robot positions per
+grid cell (``evacx.spatial.SpatialMaps``); ``policy="greedy"`` also takes one network per robot (a
 GroupedLearner, a GroupedQMix, or a sequence of Learners).
 """
 from __future__ import annotations
@@ -108,7 +109,7 @@ class _EachRobot:
 
 def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_base: int = 1234, seed: int = 0,
              check_every: int = 16, max_steps: Optional[int] = None, layout_of: Optional[Sequence[int]] = None,
-             metrics: bool = False, timeline: bool = False, track=None) -> dict:
+             metrics: bool = False, timeline: bool = False, track=None, maps: bool = False) -> dict:
     """Run E envs of ``layout`` (a DeviceLayout, or a LayoutSet with ``layout_of``) under
     ``policy`` until every env has finished ``episodes_per_env`` episodes, and return the
     EpisodeStats summary over exactly E * episodes_per_env episodes, with ``per_env`` = the
@@ -143,7 +144,15 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
     evacuation-time and death-time distributions, per layout and summed). ``track`` = a person
     count n (the first n persons of env 0) or (env_ids, person_ids) also keeps those persons'
     positions and health over their env's first episode (``curves["tracked"]``); it needs
-    ``timeline=True`` (ValueError). No host sync is added."""
+    ``timeline=True`` (ValueError). No host sync is added.
+
+    maps=True: the same reset-apart path, with an ``evacx.spatial.SpatialMaps`` (cap =
+    episodes_per_env) that is synced after the first reset, counts every step between the step and
+    the reset, after the health and timeline updates, and is synced again for the envs the masked
+    reset restarted. The result gains ``maps`` (``SpatialMaps.maps()``: per layout and summed, the
+    arrive / stall / evac / died / robot counts per grid cell, occupancy, density, the stall ratio,
+    the exits' shares and the stall hotspots). No host sync is added; with maps=False nothing is
+    allocated or launched."""
     _check_policy(policy, learner)
     if track is not None and not timeline:
         raise ValueError("evaluate: track needs timeline=True")
@@ -171,6 +180,11 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
         tline = Timeline(E, layout.device, layout.P, T=EPISODE_MAX_STEPS, layout_idx=env.layout_idx,
                          n_layouts=n_layouts, cap=K, track=track)
         tline.trace0(env)
+    smaps = None
+    if maps:
+        from .spatial import SpatialMaps
+        smaps = SpatialMaps(E, layout.device, layout, layout_idx=env.layout_idx, n_layouts=n_layouts, cap=K)
+        smaps.sync(env)
     n = E * layout.R
     actions = torch.full((n,), policy if isinstance(policy, int) else 0, dtype=torch.int32, device=layout.device)
     q0 = torch.zeros(n, N_ACTIONS, dtype=torch.float32, device=layout.device) if policy == "random" else None
@@ -195,7 +209,7 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
             Q = learner.q_values(x.view(n, 11, 11, 6), train=False, tag="eval")
             _lib.check(_lib.lib().evx_act(Q.data_ptr(), n, learner.actions, 0.0, seed, steps * n, actions.data_ptr(),
                                           _stream()), "act")
-        if health is None and tline is None:
+        if health is None and tline is None and smaps is None:
             env.step(actions, auto_reset=True)
             stats.update(env.reward, env.done, env.counts)
         else:  # the state the step left is read between the step and the reset
@@ -204,8 +218,12 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
                 health.update(env, env.done)
             if tline is not None:
                 tline.update(env, env.done, env.counts)
+            if smaps is not None:
+                smaps.update(env, env.done)
             stats.update(env.reward, env.done, env.counts)
             env.reset(mask=env.done)
+            if smaps is not None:
+                smaps.sync(env, mask=env.done)
         steps += 1
         if steps % check_every == 0 or steps >= max_steps:
             s = stats.summary(clear=False)
@@ -227,6 +245,8 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
                               tab_alive=health.tab_alive)
     if tline is not None:
         out["curves"] = tline.curves()
+    if smaps is not None:
+        out["maps"] = smaps.maps()
     return out
 
 

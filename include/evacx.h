@@ -952,6 +952,87 @@ int evx_timeline_update(const evx_timeline *tl, const int32_t *counts, const uin
 int evx_timeline_trace0(const evx_timeline *tl, const int32_t *pk, const double *health, int32_t P, void *stream);
 const char *evx_timeline_last_error(void);
 
+/* ---- Spatial maps (csrc/spatial.hip): where an evacuation happened -- per layout row and grid
+ * cell, how many persons arrived, stood still, left through an exit or died there, and where the
+ * robots spent their steps -- over every counted episode of every env. The reference keeps one
+ * per-env diagnostic (People.thmap) and aggregates nothing. All arrays are the caller's device
+ * arrays; every accumulator is an integer count, so the result does not depend on the order of the
+ * adds and there are no float atomics. The grid is the padded one of the env kernels:
+ * GX = L + 2, GY = W + 2, cell = x * GY + y, G = GX * GY. */
+typedef struct {
+    int32_t E;
+    int32_t P;             /* persons per env, 1..EVX_HEALTH_MAX_P */
+    int32_t R;             /* robots per env, >= 0 */
+    int32_t GX, GY;        /* 1..4096 each */
+    int32_t n_rows;        /* layout rows (an env's row is layout_idx[e], 0 without layout_idx) */
+    uint32_t *prev;        /* [E][P]: each env's pk as of the previous state */
+    int64_t *n_total;      /* [E]: episodes finished since evx_spatial_init (the maps' own count) */
+    /* per row and cell [n_rows][G] */
+    int64_t *arrive;       /* live persons that stand on a cell other than the one before the step */
+    int64_t *stall;        /* live persons that stand on the cell they stood on before the step */
+    int64_t *evac;         /* persons that became safe at the step, at the cell they are on */
+    int64_t *died;         /* persons that died at the step */
+    int64_t *robot;        /* robot positions after the step */
+    int64_t *steps;        /* [n_rows]: env-steps folded */
+    int64_t *bad;          /* [1]: persons and robots whose cell lies outside the grid, left out of every map */
+} evx_spatial;
+
+/* EVX_SPATIAL_*: how evx_spatial_update accumulates the two dense maps (arrive, stall) */
+#define EVX_SPATIAL_LDS 1   /* one launch: both maps of the whole grid as u32 counters in LDS */
+#define EVX_SPATIAL_BANDS 2 /* the grid cut into x-bands that fit, one workgroup column per band, and a
+                               second launch that takes the step (prev, n_total) */
+
+/* The launch shape of evx_spatial_update, as the launcher itself decides it (evx_spatial_plan). */
+typedef struct {
+    int32_t route;         /* EVX_SPATIAL_* */
+    int32_t bands;         /* x-bands (grid.y of the update launch); 1 on EVX_SPATIAL_LDS */
+    int32_t band_w;        /* columns (x) per band */
+    int32_t band_cells;    /* band_w * GY: counters per map in LDS */
+    int32_t lds_bytes;     /* dynamic LDS of one workgroup: 64 + 8 * band_cells, at most 160 KiB */
+    int32_t envs_per_wg;   /* envs one workgroup folds before it flushes its counters (grid.x = ceil(E / this)) */
+    int32_t threads;       /* threads per workgroup; one wave takes one env at a time */
+    int32_t launches;      /* 1, or 2 with bands */
+} evx_spatial_launch;
+
+/* Zeroes prev, n_total, the five maps, steps and bad (one launch). */
+int evx_spatial_init(const evx_spatial *sp, void *stream);
+/* prev[e][.] = pk[e][.] for the envs with mask[e] != 0 (mask == NULL: every env), one launch. Call
+ * it after the first reset and after every masked reset: the state a reset writes is where the next
+ * episode's persons start, not a move. pk is typed as evx_timeline_update takes it. */
+int evx_spatial_sync(const evx_spatial *sp, const int32_t *pk, const uint8_t *mask, void *stream);
+/* One step of every env from pk [E][P] as the step left it, before any reset, and robots [E][R]
+ * (evx_state.robots: (u16)x | (u16)y << 16, where the robots stand after the step; evx_state.view
+ * is only the centre of robot 0's observation and may lag behind). For env e:
+ *   row = clamp(layout_idx[e], 0, n_rows - 1), 0 with layout_idx == NULL;
+ *   the env is counted iff cap <= 0 || n_total[e] < cap (evx_episode_update's rule).
+ * For every person i of a counted env, with old = prev[e][i], cur = pk[e][i], x = v & 0xfff,
+ * y = (v >> 12) & 0xfff, safe = bit 24, dead = bit 25, live = neither bit, cell(v) = x * GY + y:
+ *   old not live: nothing (safe and dead are absorbing);
+ *   cur outside the grid (x >= GX || y >= GY): bad += 1, nothing else;
+ *   otherwise exactly one map takes 1 at [row][cell(cur)]: evac if cur is safe (safe wins over
+ *   dead), else died if cur is dead, else arrive if cell(cur) != cell(old), else stall.
+ * For every robot of a counted env robot[row][cell] += 1, or bad += 1 outside the grid; and
+ * steps[row] += 1. Then, for every env, counted or not: prev[e][.] = pk[e][.], and
+ * n_total[e] += 1 where done[e].
+ * occupancy = arrive + stall is the live persons per cell after the step; flow = arrive + evac is
+ * the persons that entered a cell, exact while every newly safe person also moved.
+ * arrive and stall are counted in LDS: a workgroup of 1024 threads folds envs_per_wg envs, one wave
+ * per env at a time and row by row, into u32 counters (envs_per_wg * P < 2^32, so no input can
+ * overflow one) and flushes the non-zero ones with returnless 64-bit atomic adds; evac, died and
+ * robot, which take at most one add per person and episode or R per env-step, go straight to
+ * 64-bit atomics. A grid whose two maps exceed 160 KiB of LDS is cut into x-bands
+ * (EVX_SPATIAL_BANDS): workgroup (s, b) folds the persons of share s whose x lies in band b, band 0
+ * also the robots, bad and steps, and a second launch writes prev and n_total.
+ * -22 with a message, before any launch: a NULL descriptor or descriptor array; E < 1; P outside
+ * 1..EVX_HEALTH_MAX_P; R < 0; GX or GY outside 1..4096; n_rows < 1; NULL pk or done; NULL robots
+ * with R > 0. */
+int evx_spatial_update(const evx_spatial *sp, const int32_t *pk, const int32_t *robots, const uint8_t *done,
+                       const int32_t *layout_idx, int64_t cap, void *stream);
+/* The route and launch shape evx_spatial_update takes for this grid and P, from the function the
+ * launcher itself calls; no launch and no device call. -22 for sizes the update refuses. */
+int evx_spatial_plan(int32_t GX, int32_t GY, int32_t P, int32_t n_rows, evx_spatial_launch *plan);
+const char *evx_spatial_last_error(void);
+
 /* ---- Learner diagnostics (csrc/lstats.hip): what Double-Q, the Huber loss and the soft target
  * exist to control -- the Q-values, targets and TD errors of the sampled batches, the loss and the
  * pre-clip gradient norm -- accumulated on the device over a window of learn steps, and a value
