@@ -2408,11 +2408,8 @@ __device__ __forceinline__ void step_env(const evx_layout& lay, const evx_state&
     }
     // LDS hand-offs only (the person words are drained below); big grids' bitmaps are global
     if constexpr (BIGG) wave_sync(); else wave_fence();
-    {
-        const int nev = (int)misc[0];
-        if (nev > EV_CAP) err |= 16;
-        const int ne = min(nev, EV_CAP);
-        for (int i = lane; i < ne; i += 64) {  // last writer = largest (first planner, sub-step)
+    auto ev_resolve = [&](const int ne) {  // last writer = largest (first planner, sub-step)
+        for (int i = lane; i < ne; i += 64) {
             const uint32_t c = ev[2 * i], kv = ev[2 * i + 1];
             bool top = true;
             for (int j = 0; j < ne; j++)
@@ -2421,6 +2418,67 @@ __device__ __forceinline__ void step_env(const evx_layout& lay, const evx_state&
                 if (kv & 1u) atomicOr(&rmapb[c >> 5], 1u << (c & 31));
                 else atomicAnd(&rmapb[c >> 5], ~(1u << (c & 31)));
             }
+        }
+    };
+    const int nev = __builtin_amdgcn_readfirstlane((int)misc[0]);
+    if (nev <= EV_CAP) {
+        ev_resolve(nev);
+    } else {
+        // More events than the list holds (a dense crowd, where most movers follow another: 150x150
+        // with 6000 persons has ~1000 on the steps everybody plans). The order matters per cell only,
+        // so the plan is walked again once per range of cells, recording the events of that range
+        // alone -- they depend on the plan and on the contested / loser / target / vacated bitmaps,
+        // none of which execute_move changed -- and a range whose events still overflow is halved.
+        int c0 = 0;
+        int span = max(1, (int)((long long)g.G * (EV_CAP / 2) / nev));
+        while (c0 < g.G) {
+            const int c1 = min(g.G, c0 + span);
+            wave_sync();  // the list's readers are done
+            if (lane == 0) misc[0] = 0;
+            wave_sync();
+            for (int i0 = 0; i0 < nplan; i0 += 64) {
+                if (i0 + lane < nplan) {
+                    const uint2 en = plan[i0 + lane];
+                    const int p = (int)en.x;
+                    const int cold = (int)(en.y & 0xffffffu);
+                    const int t = cold + doff_of(en.y >> 24, GY);
+                    const bool in_old = cold >= c0 && cold < c1, in_new = t >= c0 && t < c1;
+                    if (in_old || in_new) {
+                        const uint4 wb = exec_words(en);
+                        const bool cont = any_cont && ((wb.x >> (cb_idx(t) & 31)) & 1u);
+                        const bool win = !cont || !((wb.y >> (p & 31)) & 1u);
+                        const bool ev_old = in_old && ((wb.z >> (cold & 31)) & 1u);
+                        const bool ev_new = in_new && ((wb.w >> (t & 31)) & 1u);
+                        if (win && (ev_old || ev_new)) {
+                            const int pf = cont ? find_pf(Lp, ncont, t, pb, p) : p;
+                            if (ev_old) {
+                                const int s = atomicAdd((int*)&misc[0], 1);
+                                if (s < EV_CAP) {
+                                    ev[2 * s] = (uint32_t)cold;
+                                    ev[2 * s + 1] = ((uint32_t)pf << 2) | 0u;
+                                }
+                            }
+                            if (ev_new) {
+                                const bool ex = (lay.cellinfo[t] >> 1) & 1u;
+                                const int s = atomicAdd((int*)&misc[0], 1);
+                                if (s < EV_CAP) {
+                                    ev[2 * s] = (uint32_t)t;
+                                    ev[2 * s + 1] = ((uint32_t)pf << 2) | 2u | (ex ? 0u : 1u);
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            wave_sync();
+            const int n = __builtin_amdgcn_readfirstlane((int)misc[0]);
+            if (n > EV_CAP && span > 1) {
+                span = (span + 1) >> 1;
+                continue;
+            }
+            if (n > EV_CAP) err |= 16;  // one cell with more events than the list holds
+            ev_resolve(min(n, EV_CAP));
+            c0 = c1;
         }
     }
     wave_sync();  // the person words of the movers and the rmap bits complete
@@ -3375,10 +3433,44 @@ struct StepLaunch {
     size_t lds;  // dynamic LDS bytes per workgroup
     int hcap, hmin, pslots;
 };
-int step_select(const evx_layout& l, const evx_state& s, StepLaunch* sl) {
+// The launch plan of a step, decided on the host from sizes alone (no device call, nothing
+// dereferenced): step_select launches what it says and evx_env_step_plan_query hands it out.
+// has_order / has_idx: evx_state.order / layout_idx are set; ncu: the device's compute units.
+int step_plan(const evx_layout& l, int E, bool has_order, bool has_idx, int ncu, evx_env_step_plan* p) {
     const bool bigg = evx::big_grid(l.L, l.W);
     if (step_lds_bytes(l, bigg) > 160 * 1024) return fail(-7, "layout needs more than 160 KiB of LDS");
-    const bool multi = l.layout_set && s.layout_idx;
+    // Default: 4-wave workgroups with the heavy-env path while a launch is short enough for
+    // its heaviest env to set its length (fewer than 64 envs per CU); one-wave workgroups
+    // beyond, where throughput rules: a wave's VGPRs and LDS free the moment its env is done
+    // instead of when the slowest of four is (32768 envs: env_step 1.50 -> 1.31 ms).
+    // (64 envs per CU: the 8192-env share of cfg5 keeps the heavy-env workgroups -- env_step 0.42 ->
+    // 0.37 ms; big grids, which have no heavy path, switch at 32)
+    int nwb = E >= (bigg ? 32 : 64) * ncu ? 1 : 4;
+    // EVX_ENV_NWB = 1 / 2 / 4 overrides (tuning, and tests of the one-wave variant at a small E)
+    if (const char* v = getenv("EVX_ENV_NWB")) {
+        const int n = atoi(v);
+        if (n == 1 || n == 2 || n == 4) nwb = n;
+    }
+    if (bigg && nwb > 2) nwb = 2;  // BIGG kernels: 1 or 2 envs per workgroup
+    while (nwb > 1 && step_launch_lds(l, nwb, bigg) > 160 * 1024) nwb >>= 1;
+    int hmin = 0;
+    p->nwb = nwb;
+    p->bigg = bigg;
+    p->multi = l.layout_set && has_idx;
+    p->hcap = (nwb == evx::WNW && has_order) ? heavy_cap(l, &hmin) : 0;
+    p->hmin = hmin;
+    p->lds_env_bytes = (int32_t)step_lds_bytes(l, bigg);
+    p->lds_wg_bytes = (int32_t)step_launch_lds(l, nwb, bigg);
+    const evx::WaveLds S = evx::wave_lds(l.L, l.W, l.P, l.R, bigg);
+    p->vac_in_ring = !bigg && S.vac == S.pyring;
+    p->near_in_misc = S.nearc == S.misc;
+    p->wide_past_envs = !bigg && evx::wide_lds(l).end > evx::WNW * evx::step_lds_words(l);
+    return 0;
+}
+int step_select(const evx_layout& l, const evx_state& s, StepLaunch* sl) {
+    evx_env_step_plan p;
+    const int rc = step_plan(l, s.E, s.order != nullptr, s.layout_idx != nullptr, evxh::cu_count(), &p);
+    if (rc) return rc;
     {
         static std::atomic<uint64_t> attr_done;
         const void* ks[10] = {(const void*)evx::env_step_kernel<1, false>, (const void*)evx::env_step_kernel<2, false>,
@@ -3390,37 +3482,32 @@ int step_select(const evx_layout& l, const evx_state& s, StepLaunch* sl) {
                               (const void*)evx::env_step_kernel<2, true, true>};
         evxh::max_lds_once(attr_done, ks, 10, 160 * 1024);
     }
-    // Default: 4-wave workgroups with the heavy-env path while a launch is short enough for
-    // its heaviest env to set its length (fewer than 64 envs per CU); one-wave workgroups
-    // beyond, where throughput rules: a wave's VGPRs and LDS free the moment its env is done
-    // instead of when the slowest of four is (32768 envs: env_step 1.50 -> 1.31 ms).
-    const int ncu = evxh::cu_count();
-    // (64 envs per CU: the 8192-env share of cfg5 keeps the heavy-env workgroups -- env_step 0.42 ->
-    // 0.37 ms; big grids, which have no heavy path, switch at 32)
-    int nwb = s.E >= (bigg ? 32 : 64) * ncu ? 1 : 4;
-    // EVX_ENV_NWB = 1 / 2 / 4 overrides (tuning, and tests of the one-wave variant at a small E)
-    if (const char* v = getenv("EVX_ENV_NWB")) {
-        const int n = atoi(v);
-        if (n == 1 || n == 2 || n == 4) nwb = n;
-    }
-    if (bigg && nwb > 2) nwb = 2;  // BIGG kernels: 1 or 2 envs per workgroup
-    while (nwb > 1 && step_launch_lds(l, nwb, bigg) > 160 * 1024) nwb >>= 1;
-    sl->nwb = nwb;
-    sl->hmin = 0;
-    sl->hcap = (nwb == evx::WNW && s.order) ? heavy_cap(l, &sl->hmin) : 0;
+    sl->nwb = p.nwb;
+    sl->hmin = p.hmin;
+    sl->hcap = p.hcap;
     // single-wave envs at order slots < H + pslots could run at raised wave priority: 0 (a sweep
     // of 0 / 1 / 256 / 768 / 1536 slots measured box noise in the training step)
     sl->pslots = 0;
-    sl->lds = step_launch_lds(l, nwb, bigg);
-    if (bigg)
-        sl->fn = nwb == 2 ? (multi ? evx::env_step_kernel<2, true, true> : evx::env_step_kernel<2, false, true>)
-                          : (multi ? evx::env_step_kernel<1, true, true> : evx::env_step_kernel<1, false, true>);
-    else if (nwb == 4)
+    sl->lds = (size_t)p.lds_wg_bytes;
+    const bool multi = p.multi;
+    if (p.bigg)
+        sl->fn = p.nwb == 2 ? (multi ? evx::env_step_kernel<2, true, true> : evx::env_step_kernel<2, false, true>)
+                            : (multi ? evx::env_step_kernel<1, true, true> : evx::env_step_kernel<1, false, true>);
+    else if (p.nwb == 4)
         sl->fn = multi ? evx::env_step_kernel<4, true> : evx::env_step_kernel<4, false>;
-    else if (nwb == 2)
+    else if (p.nwb == 2)
         sl->fn = multi ? evx::env_step_kernel<2, true> : evx::env_step_kernel<2, false>;
     else
         sl->fn = multi ? evx::env_step_kernel<1, true> : evx::env_step_kernel<1, false>;
+    return 0;
+}
+// contested-list keys are (target << bits(P-1)) | person in 32 bits
+int check_move_keys(const evx_layout& l) {
+    const int G = (l.L + 2) * (l.W + 2);
+    int pb = 1, gb = 1;
+    while ((1 << pb) < l.P) pb++;
+    while ((1LL << gb) < (long long)G) gb++;
+    if (pb + gb > 32) return fail(-22, "grid cells x people too large for 32-bit move keys");
     return 0;
 }
 }  // namespace
@@ -3447,6 +3534,15 @@ int evx_env_step_occupancy(const evx_layout* l, const evx_state* s, int32_t* blo
     return 0;
 }
 
+int evx_env_step_plan_query(const evx_layout* l, const evx_state* s, int32_t ncu, evx_env_step_plan* out) {
+    int rc = check_layout(l);
+    if (rc) return rc;
+    if (!s || !out) return fail(-22, "NULL argument");
+    rc = check_move_keys(*l);
+    if (rc) return rc;
+    return step_plan(*l, s->E, s->order != nullptr, s->layout_idx != nullptr, ncu > 0 ? ncu : evxh::cu_count(), out);
+}
+
 int64_t evx_step_lds_bytes(const evx_layout* l) {
     if (check_layout(l)) return -1;
     return (int64_t)step_lds_bytes(*l, evx::big_grid(l->L, l->W));
@@ -3470,13 +3566,8 @@ int evx_env_step_part(const evx_layout* l, const evx_state* s, const int32_t* ac
     if (!s->scratch) return fail(-22, "state scratch is NULL (evx_step_scratch_words per env)");
     if (!l->nbr_valid || !l->floor_d5) return fail(-22, "missing table nbr_valid / floor_d5");
     if (s->E <= 0) return 0;
-    const int G = (l->L + 2) * (l->W + 2);
-    {  // contested-list keys are (target << bits(P-1)) | person in 32 bits
-        int pb = 1, gb = 1;
-        while ((1 << pb) < l->P) pb++;
-        while ((1LL << gb) < (long long)G) gb++;
-        if (pb + gb > 32) return fail(-22, "grid cells x people too large for 32-bit move keys");
-    }
+    rc = check_move_keys(*l);
+    if (rc) return rc;
     StepLaunch sl;
     rc = step_select(*l, *s, &sl);
     if (rc) return rc;

@@ -82,6 +82,13 @@ class evx_step_out(C.Structure):
     _fields_ = _ptrs("reward", "done", "counts", "obs", "err", "stamps", "obs_term")
 
 
+class evx_env_step_plan(C.Structure):
+    """How a step is launched (evx_env_step_plan_query): env_step_kernel<nwb, multi, bigg>, its LDS,
+    the heavy-env path and the three LDS layout switches."""
+    _fields_ = [(n, C.c_int32) for n in ["nwb", "bigg", "multi", "hcap", "hmin", "lds_env_bytes", "lds_wg_bytes",
+                                        "vac_in_ring", "near_in_misc", "wide_past_envs"]]
+
+
 class evx_gemm_desc(C.Structure):
     _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("precision", C.c_int32),
                 ("flags", C.c_int32), ("alpha", C.c_float),
@@ -201,6 +208,7 @@ SIGNATURES = {
     "evx_env_step": (C.c_int, [_LAY, _ST, _vp, _P(evx_step_out), _vp]),
     "evx_env_step_part": (C.c_int, [_LAY, _ST, _vp, _P(evx_step_out), _i32, _vp]),
     "evx_env_step_occupancy": (C.c_int, [_LAY, _ST] + [_P(_i32)] * 3),
+    "evx_env_step_plan_query": (C.c_int, [_LAY, _ST, _i32, _P(evx_env_step_plan)]),
     "evx_env_reset": (C.c_int, [_LAY, _ST] + [_vp] * 4),
     "evx_obs_expand_f32": (C.c_int, [_LAY, _vp, _i64, _vp, _vp]),
     "evx_obs_expand_f64": (C.c_int, [_LAY, _vp, _i64, _vp, _vp]),

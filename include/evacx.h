@@ -114,7 +114,9 @@ typedef struct {
     evx_obs *obs;      /* [E*R] observation after the step */
     int32_t *err;      /* [1] sticky device error word (may be NULL); bits: 1 > 128 movers on one
                         * target, 2 a runaway Python-stream window, 4 reset placement, 8 / 16
-                        * scratch or event-list overflow, 32 kept-list mismatch, 64 an MT block
+                        * scratch overflow / more than 256 order-sensitive events on one cell (more
+                        * events than the LDS list holds over a whole step are handled: the plan is
+                        * walked again per range of cells), 32 kept-list mismatch, 64 an MT block
                         * overwritten before the state store (any bit: results not bit-exact) */
     int64_t *stamps;   /* [E*48] diagnostic per-phase s_memtime stamps + counters (NULL = off) */
     /* Auto-reset (NULL = off, the reference's separate env.reset): envs that finish this
@@ -142,6 +144,35 @@ int evx_env_step_part(const evx_layout *l, const evx_state *s, const int32_t *ac
  * EVX_ENV_NWB = 1 / 2 / 4 in the environment overrides the waves per workgroup of both. */
 int evx_env_step_occupancy(const evx_layout *l, const evx_state *s, int32_t *blocks_per_cu, int32_t *lds_bytes,
                            int32_t *block_threads);
+/* How a step of st->E envs of this layout is launched: env_step_kernel<nwb, multi, bigg>, its LDS and
+ * the heavy-env path, with the three places where the LDS layout of an env switches. */
+typedef struct {
+    int32_t nwb;            /* waves (envs) per workgroup: 1, 2 or 4. 4 below 64 envs per CU (big grids: 2
+                             * below 32), else 1; EVX_ENV_NWB = 1 / 2 / 4 overrides; halved while the
+                             * workgroup's LDS exceeds 160 KiB */
+    int32_t bigg;           /* 1: a big grid (bitmaps of more than 1024 words: target / contested / vacated
+                             * bitmaps in the env's global scratch, no heavy path, nwb <= 2) */
+    int32_t multi;          /* 1: per-env layouts (evx_layout.layout_set with evx_state.layout_idx) */
+    int32_t hcap;           /* most heavy envs (rows phase on a 4-wave workgroup) per step; 0: none -- nwb < 4,
+                             * no order buffer, a big grid, or the 4-wave workgroup does not fit 160 KiB
+                             * (EVX_HEAVY_CAP overrides, read once per process) */
+    int32_t hmin;           /* persons in play that make an env heavy: max(1, P / 4) (EVX_HEAVY_MIN
+                             * overrides, read once per process); 0 when nwb < 4 or without an order buffer */
+    int32_t lds_env_bytes;  /* dynamic LDS of one env's wave (evx_step_lds_bytes) */
+    int32_t lds_wg_bytes;   /* dynamic LDS of the workgroup */
+    int32_t vac_in_ring;    /* 1: the vacated-cell bitmap overlays the Python MT ring (bitmaps of <= 624
+                             * words); 0: a region of its own, or (big grids) global scratch */
+    int32_t near_in_misc;   /* 1: the near-robot block map overlays the shuffle-group region (<= 144 words:
+                             * grids up to 266 x 266); 0: a region of its own */
+    int32_t wide_past_envs; /* 1: the heavy path's rows buffers run past the four env regions of the
+                             * 4-wave workgroup (0 on big grids, which have no heavy path) */
+} evx_env_step_plan;
+/* The plan evx_env_step_part launches by, from the function the launcher itself switches on. ncu > 0:
+ * the compute units to plan for -- no device call at all, so it runs on a host without a GPU;
+ * ncu <= 0: the current device's. Only E, order and layout_idx of st are looked at, none
+ * dereferenced, and no table of the layout is read. An argument error the step would report
+ * before launching comes back as the same code with the same evx_last_error text. */
+int evx_env_step_plan_query(const evx_layout *l, const evx_state *s, int32_t ncu, evx_env_step_plan *out);
 
 /* Replaces EvacuationEnv.reset / EvacuationEnvMulti.reset (envs/evacuation_env.py:61-82,
  * envs/evacuation_env_multi.py:31-42) incl. People placement (envs/people.py:183-194).

@@ -92,7 +92,7 @@ def test_earlier_loader_names_are_the_one_loader():
 
 STRUCTS = ["evx_layout", "evx_state", "evx_replay", "evx_step_out", "evx_qmlp_params", "evx_qmlp_dropout",
            "evx_qmlp_grads", "evx_qmlp_fwd_out", "evx_td_opts", "evx_gemm_desc", "evx_gemm_plan", "evx_adam",
-           "evx_prio", "evx_episodes", "evx_health", "evx_qmlp_plan", "evx_qmlp_fwd_plan"]
+           "evx_prio", "evx_episodes", "evx_health", "evx_qmlp_plan", "evx_qmlp_fwd_plan", "evx_env_step_plan"]
 
 
 def _mirrored_constants(_lib):
@@ -143,7 +143,7 @@ def test_structure_layouts_and_constants_match_the_header(tmp_path):
     assert r.returncode == 0, r.stderr
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, check=True).stdout
     got = {k: int(v) for k, v in (ln.rsplit(" ", 1) for ln in out.splitlines())}
-    assert len(STRUCTS) == 17 and set(got) == set(want)
+    assert len(STRUCTS) == 18 and set(got) == set(want)
     assert {k: (got[k], want[k]) for k in want if got[k] != want[k]} == {}
 
 
