@@ -36,6 +36,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 
 #include "evacx.h"
@@ -1225,6 +1226,21 @@ __global__ __launch_bounds__(256, 2) void qact3h_kernel(Fwd a0) {
     const Fwd& a = GR ? ag : a0;
     extern __shared__ __attribute__((aligned(16))) char dsm[];
     act3h_tile<DM, SAVE>(a, dsm, (int)blockIdx.x * 64);
+}
+// The blocked grouped act (evx_qmlp_act_gb: a population of independent learners, member g = net
+// blockIdx.y): net g owns rows [g N, (g + 1) N) of obs / q / actions (fwd_net's blocked view, gn = 0),
+// explores with its own epsilon, and its rows' epsilon draws are counted from act_offset + g N -- the
+// single-net act of the block with drop row0 = g N and act_offset + g N, in one launch for all nets.
+struct ActEps {
+    float eps[64];
+};
+template <int DM>
+__global__ __launch_bounds__(256, 2) void qact3h_gb_kernel(Fwd a0, ActEps e) {
+    Fwd a = fwd_net(a0, (int)blockIdx.y);
+    a.epsilon = e.eps[blockIdx.y];
+    a.act_offset += (uint64_t)blockIdx.y * (uint64_t)a.N;
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    act3h_tile<DM, false>(a, dsm, (int)blockIdx.x * 64);
 }
 
 // ------------------------------------------------------------ persistent x3 act
@@ -2696,7 +2712,8 @@ __device__ __forceinline__ float adam_one(const AdamPack& a, int i, float coef) 
     a.p[i] = pn;
     return pn;
 }
-__global__ __launch_bounds__(256) void adam_pack3_kernel(AdamPack a0) {
+// the body of adam_pack3_kernel and adam_pack3_gl_kernel: net blockIdx.y's step with a0's hyperparameters
+__device__ __forceinline__ void adam_pack3_body(const AdamPack& a0) {
     __shared__ float red[256];
     AdamPack a = a0;
     if (blockIdx.y) {  // grouped: net blockIdx.y (clip_grad_norm_ and Adam per net)
@@ -2763,6 +2780,16 @@ __global__ __launch_bounds__(256) void adam_pack3_kernel(AdamPack a0) {
     } else {
         adam_one(a, i, coef);
     }
+}
+__global__ __launch_bounds__(256) void adam_pack3_kernel(AdamPack a0) { adam_pack3_body(a0); }
+// evx_qmlp_adam_pack3_gl: a step size per net (lr[g] / (1 - beta1^step), formed on the host), every
+// other hyperparameter common to the nets
+struct AdamSteps {
+    float v[64];
+};
+__global__ __launch_bounds__(256) void adam_pack3_gl_kernel(AdamPack a0, AdamSteps s) {
+    a0.step_size = s.v[blockIdx.y];
+    adam_pack3_body(a0);
 }
 
 // Polyak target update t = tau p + (1 - tau) t on the flat target parameters with the target's
@@ -2985,7 +3012,7 @@ static void with_drop_mode(int dm, F&& f) {
 static void raise_lds_limits() {
     using namespace evxm;
     auto k = [](auto kernel) { return (const void*)kernel; };
-    static std::atomic<uint64_t> done3h, done3p, done1;
+    static std::atomic<uint64_t> done3h, done3p, done1, donegb;
     const void* k3h[14] = {
         k(qact3h_kernel<false, 0>),       k(qact3h_kernel<false, 1>),       k(qact3h_kernel<false, 2>),
         k(qact3h_kernel<false, 0, true>), k(qact3h_kernel<false, 1, true>), k(qact3h_kernel<false, 2, true>),
@@ -2995,6 +3022,8 @@ static void raise_lds_limits() {
     evxh::max_lds_once(done3h, k3h, 14, ACT3H_LDS);
     evxh::max_lds_once(done3p, k3p, 2, ACT3P_LDS);
     evxh::max_lds_once(done1, k1, 1, ACT_LDS);
+    const void* kgb[3] = {k(qact3h_gb_kernel<0>), k(qact3h_gb_kernel<1>), k(qact3h_gb_kernel<2>)};
+    evxh::max_lds_once(donegb, kgb, 3, ACT3H_LDS);
 }
 
 // fc1's rows per tile: 128 once such tiles over every problem fill the chip (384 of them), else 64
@@ -3007,7 +3036,8 @@ enum FwdEntry {
     FE_FORWARD,   // qfc1 (+ qfc23) only: evx_qmlp_forward, _stat, _stat_x, _forward2_g
     FE_FORWARD2,  // evx_qmlp_forward2: the learner's pair, which may go through the act kernels
     FE_ACT,       // evx_qmlp_act, _act64
-    FE_ACT_G      // evx_qmlp_act_g
+    FE_ACT_G,     // evx_qmlp_act_g
+    FE_ACT_GB     // evx_qmlp_act_gb
 };
 
 // The one decision of what a forward or act call launches: host arithmetic on the records as
@@ -3101,6 +3131,9 @@ static evx_qmlp_fwd_plan fwd_plan(const evxm::Fwd& a0, const evxm::Fwd& a1, int3
         case FE_ACT_G:
             p.route = EVX_FWD_ACT_GROUPED;
             break;
+        case FE_ACT_GB:
+            p.route = EVX_FWD_ACT_GROUPED_BLOCKED;
+            break;
     }
     return p;
 }
@@ -3111,6 +3144,7 @@ struct FwdCall {
     int pairs = 1, nets = 1;
     bool x3 = false;
     evx_qmlp_fwd_plan plan{};
+    evxm::ActEps eps{};  // evx_qmlp_act_gb: the nets' epsilons
 };
 
 static void launch_x_expand(const evxm::Fwd& a, int32_t n, hipStream_t st) {
@@ -3190,6 +3224,13 @@ static int launch_plan(FwdCall& c, int32_t n, hipStream_t st) {
         case EVX_FWD_ACT_GROUPED:
             launch_act3<true>(a0, n, c.nets, p.drop_mode, st);
             return hip_status("qact_g");
+        case EVX_FWD_ACT_GROUPED_BLOCKED:
+            with_drop_mode(p.drop_mode, [&](auto m) {
+                hipLaunchKernelGGL(evxm::qact3h_gb_kernel<decltype(m)::value>,
+                                   dim3((unsigned)((n + 63) / 64), (unsigned)c.nets), dim3(256), evxm::ACT3H_LDS, st,
+                                   a0, c.eps);
+            });
+            return hip_status("qact_gb");
         case EVX_FWD_ACT_BF16:
             hipLaunchKernelGGL(evxm::qact_kernel, dim3((unsigned)ntiles), dim3(512), evxm::ACT_LDS, st, a0);
             break;
@@ -3271,14 +3312,35 @@ static int forward_run(const evx_layout* lay, int32_t n, const evx_obs* obs0, co
 }
 
 // evx_qmlp_act's checks, record and plan; kernel64: evx_qmlp_act64's; grouped: evx_qmlp_act_g's over
-// `nets` nets. ncu <= 0: the current device's CU count
+// `nets` nets. ncu <= 0: the current device's CU count. blocked (with grouped): evx_qmlp_act_gb's, net g on
+// rows [g n, (g + 1) n) with epsilon[g] (host, [nets])
 static int act_prepare(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
                        const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, bool grouped, int32_t nets,
-                       bool kernel64, int ncu, FwdCall& c) {
+                       bool kernel64, int ncu, FwdCall& c, bool blocked = false, const float* epsilon = nullptr) {
     c.plan = evx_qmlp_fwd_plan{};
+    if (blocked) {  // every refusal before n <= 0 returns: a bad argument is reported at any n
+        if (!lay || !obs || !p || !out || !epsilon) return fail(-22, "qmlp_act_gb: NULL argument");
+        if (nets < 1 || nets > 64) return fail(-22, "qmlp_act_gb: nets must be 1..64");
+        for (int g = 0; g < nets; g++)
+            if (!std::isfinite(epsilon[g])) return fail(-22, "qmlp_act_gb: epsilon must be finite");
+        if (n & 1) return fail(-22, "qmlp_act_gb: rows per net must be even (dropout row pairs)");
+    }
     if (grouped)
         if (int rc = group_check(nets, p)) return rc;
     if (n <= 0) return 0;
+    if (blocked) {
+        if (!out->q && !out->actions) return fail(-22, "qmlp_act_gb: needs q or actions");
+        if (out->perm) return fail(-22, "qmlp_act_gb: no act permutation with grouped nets");
+        if (p->stat) return fail(-22, "qmlp_act_gb: the act table path is single-net");
+        if (out->act_ws) return fail(-22, "qmlp_act_gb: no act workspace with grouped nets");
+        if ((int64_t)n * nets >= (int64_t)1 << 31) return fail(-22, "qmlp_act_gb: too many rows");
+        c.nets = nets;
+        for (int g = 0; g < nets; g++) c.eps.eps[g] = epsilon[g];
+        if (int rc = make_fwd(lay, obs, n, p, drop, out, c.a0, FM_ACT, 0)) return rc;
+        c.x3 = true;
+        c.plan = fwd_plan(c.a0, c.a0, n, 1, c.nets, c.x3, true, FE_ACT_GB, false, 0);
+        return 0;
+    }
     if (!grouped) {
         if (!out) return fail(-22, "qmlp_act: NULL out");
         if (!out->q && !out->actions) return fail(-22, "qmlp_act: needs q or actions");
@@ -3400,6 +3462,23 @@ int evx_qmlp_act64(const evx_layout* lay, const evx_obs* obs, int32_t n, const e
 int evx_qmlp_act_g(const evx_layout* lay, const evx_obs* obs, int32_t n, int32_t nets, const evx_qmlp_params* p,
                    const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, void* stream) {
     return act_run(lay, obs, n, p, drop, out, true, nets, false, stream);
+}
+
+int evx_qmlp_act_gb(const evx_layout* lay, const evx_obs* obs, int32_t n, int32_t nets, const evx_qmlp_params* p,
+                    const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out, const float* epsilon, void* stream) {
+    FwdCall c;
+    if (int rc = act_prepare(lay, obs, n, p, drop, out, true, nets, false, 0, c, true, epsilon)) return rc;
+    return launch_plan(c, n, (hipStream_t)stream);
+}
+
+int evx_qmlp_act_gb_plan_query(const evx_layout* lay, const evx_obs* obs, int32_t n, int32_t nets,
+                               const evx_qmlp_params* p, const evx_qmlp_dropout* drop, const evx_qmlp_fwd_out* out,
+                               const float* epsilon, evx_qmlp_fwd_plan* plan) {
+    if (!plan) return fail(-22, "qmlp_act_gb_plan_query: NULL plan");
+    FwdCall c;
+    const int rc = act_prepare(lay, obs, n, p, drop, out, true, nets, false, 0, c, true, epsilon);
+    *plan = c.plan;
+    return rc;
 }
 
 int evx_qmlp_act_plan_query(const evx_layout* lay, const evx_obs* obs, int32_t n, const evx_qmlp_params* p,
@@ -3716,7 +3795,7 @@ int evx_qmlp_sumsq_parts(const float* g, float* ss, void* stream) {
 static int adam_pack3(float* p, float* g, float* m, float* v, float max_norm, const evx_adam* h, uint16_t* w1b,
                       uint16_t* w1l, float* b1c, uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl,
                       uint16_t* w1o, uint16_t* w1ol, const float* ss, int32_t nss, float* norm_out, void* stream,
-                      int nets);
+                      int nets, const float* lrs = nullptr);
 int evx_qmlp_adam_pack3(float* p, float* g, float* m, float* v, float max_norm, const evx_adam* h, uint16_t* w1b,
                         uint16_t* w1l, float* b1c, uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl,
                         uint16_t* w1o, uint16_t* w1ol, const float* ss, int32_t nss, float* norm_out, void* stream) {
@@ -3731,10 +3810,21 @@ int evx_qmlp_adam_pack3_g(float* p, float* g, float* m, float* v, float max_norm
     return adam_pack3(p, g, m, v, max_norm, h, w1b, w1l, b1c, w2b, w2l, w2t, w2tl, w1o, w1ol, ss, nss, norm_out,
                       stream, nets);
 }
+int evx_qmlp_adam_pack3_gl(float* p, float* g, float* m, float* v, float max_norm, const evx_adam* h, uint16_t* w1b,
+                           uint16_t* w1l, float* b1c, uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl,
+                           uint16_t* w1o, uint16_t* w1ol, const float* ss, int32_t nss, float* norm_out, int32_t nets,
+                           const float* lr, void* stream) {
+    if (!lr) return fail(-22, "qmlp_adam_pack3_gl: NULL lr");
+    if (nets < 1 || nets > 64) return fail(-22, "qmlp_adam_pack3_gl: nets must be 1..64");
+    for (int k = 0; k < nets; k++)
+        if (!std::isfinite(lr[k])) return fail(-22, "qmlp_adam_pack3_gl: lr must be finite");
+    return adam_pack3(p, g, m, v, max_norm, h, w1b, w1l, b1c, w2b, w2l, w2t, w2tl, w1o, w1ol, ss, nss, norm_out,
+                      stream, nets, lr);
+}
 static int adam_pack3(float* p, float* g, float* m, float* v, float max_norm, const evx_adam* h, uint16_t* w1b,
                       uint16_t* w1l, float* b1c, uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl,
                       uint16_t* w1o, uint16_t* w1ol, const float* ss, int32_t nss, float* norm_out, void* stream,
-                      int nets) {
+                      int nets, const float* lrs) {
     if ((w1o == nullptr) != (w1ol == nullptr)) return fail(-22, "qmlp_adam_pack3: w1o and w1ol go together");
     if (!p || !g || !m || !v || !h || !w1b || !w1l || !b1c || !w2b || !w2l || !ss)
         return fail(-22, "qmlp_adam_pack3: NULL argument");
@@ -3754,6 +3844,13 @@ static int adam_pack3(float* p, float* g, float* m, float* v, float max_norm, co
     a.w2t = reinterpret_cast<__bf16*>(w2t); a.w2tl = reinterpret_cast<__bf16*>(w2tl);
     a.b1c = b1c; a.norm_out = norm_out;
     a.w1o = reinterpret_cast<__bf16*>(w1o); a.w1ol = reinterpret_cast<__bf16*>(w1ol);
+    if (lrs) {  // a learning rate per net: the same expression of each, passed by value
+        evxm::AdamSteps s{};
+        for (int k = 0; k < nets; k++) s.v[k] = (float)(lrs[k] / bc1);
+        hipLaunchKernelGGL(evxm::adam_pack3_gl_kernel, dim3((unsigned)((evxm::NPAR + 255) / 256), nets), dim3(256), 0,
+                           (hipStream_t)stream, a, s);
+        return hip_status("qmlp_adam_pack3_gl");
+    }
     hipLaunchKernelGGL(evxm::adam_pack3_kernel, dim3((unsigned)((evxm::NPAR + 255) / 256), nets), dim3(256), 0,
                        (hipStream_t)stream, a);
     return hip_status("qmlp_adam_pack3");

@@ -42,6 +42,7 @@ REDUCE = {"NONE": 0, "GENERIC": 1, "QUARTERS": 2}  # EVX_REDUCE_*: the split-K r
 # EVX_FWD_*: what an MLP forward or act call launches (evx_qmlp_fwd_plan_query, evx_qmlp_act_plan_query)
 FWD = {"NONE": 0, "FC": 1, "FC_GROUPED": 2, "PAIRED": 3, "TARGET_ACT_TABLE": 4, "TARGET_ACT_FC": 5, "ACT_BF16": 6,
        "ACT_64": 7, "ACT_PERSISTENT": 8, "ACT_GROUPED": 9}
+FWD_ACT_GROUPED_BLOCKED = 10  # EVX_FWD_ACT_GROUPED_BLOCKED (an enumerator): evx_qmlp_act_gb's route
 EPISODE_REDUCE_SPAN = 1024  # EVX_EPISODE_REDUCE_SPAN: envs one pass of a reduce workgroup covers
 EPISODE_ROW_WORDS = 10  # sizeof(evx_episode_row) / 8
 HEALTH_ROW_WORDS = 6  # sizeof(evx_health_row) / 8
@@ -293,9 +294,14 @@ SIGNATURES = {
     "evx_qmlp_polyak_pack3": (C.c_int, [_vp, _vp, _f32, _f32] + [_vp] * 10),
     "evx_qmlp_backward_ss_g": (C.c_int, [_PAR, _i32, _i32] + [_vp] * 4 + [_f32, _vp, _vp, _GRADS, _vp, _vp]),
     "evx_qmlp_adam_pack3_g": (C.c_int, [_vp] * 4 + [_f32, _P(evx_adam)] + [_vp] * 10 + [_i32, _vp, _i32, _vp]),
+    "evx_qmlp_adam_pack3_gl": (C.c_int, [_vp] * 4 + [_f32, _P(evx_adam)] + [_vp] * 10 + [_i32, _vp, _i32, _vp, _vp]),
     "evx_qmlp_group_plan": (C.c_int, [_i32, _i32, _P(evx_qmlp_plan)]),
     "evx_qmlp_fwd_plan_query": (C.c_int, [_LAY, _i32, _vp, *_NET, _vp, *_NET, _i32, _P(evx_qmlp_fwd_plan)]),
     "evx_qmlp_act_plan_query": (C.c_int, [_LAY, _vp, _i32, *_NET, _i32, _i32, _i32, _P(evx_qmlp_fwd_plan)]),
+    "evx_qmlp_act_gb": (C.c_int, [_LAY, _vp, _i32, _i32, *_NET, _vp, _vp]),
+    "evx_qmlp_act_gb_plan_query": (C.c_int, [_LAY, _vp, _i32, _i32, *_NET, _vp, _P(evx_qmlp_fwd_plan)]),
+    "evx_replay_push_blocks": (C.c_int, [_RING] + [_vp] * 6 + [_i32, _i32, _i32, _i64, _vp]),
+    "evx_replay_sample_blocks": (C.c_int, [_RING, _i64, _i32, _i32, _u64, _u64] + [_vp] * 6),
     "evx_qmix_nparams": (C.c_int32, [_i32]),
     "evx_qmix_part_floats": (C.c_int64, [_i32, _i32]),
     "evx_qmix_loss": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32, _i32] + [_vp] * 7 + [_i64, _vp]),

@@ -27,9 +27,9 @@ from typing import List, Optional
 
 import torch
 
-from ._lib import check, evx_adam, evx_qmlp_fwd_out, evx_qmlp_grads, evx_qmlp_plan, lib
+from ._lib import check, evx_adam, evx_qmlp_fwd_out, evx_qmlp_fwd_plan, evx_qmlp_grads, evx_qmlp_plan, lib
 from .env import _stream
-from .qmlp import HID, HID2, K1X, NACT, MLPFast, _need
+from .qmlp import HID, HID2, K1X, NACT, MLPFast, _need, td_opts
 from .qnet import DROPOUT_P, FlatParams, layer_specs, param_shapes
 
 
@@ -130,13 +130,51 @@ class GroupedLearner:
         check(lib().evx_qmlp_act_g(C.byref(lay_c), obs.data_ptr(), n, G, C.byref(self.fast.c), C.byref(d),
                                    C.byref(o), _stream()), "qmlp_act_g")
 
+    def _act_blocks_args(self, lay_c, obs, n, epsilon, actions, q, act_seed, act_offset, drop_p, drop_seed, drop_stream):
+        G = self.G
+        if len(epsilon) != G:
+            raise ValueError(f"act_blocks: epsilon must hold {G} values, not {len(epsilon)}")
+        _need("act_gb obs", obs, n * G, 8)
+        _need("act_gb q", q, n * G, NACT)
+        _need("act_gb actions", actions, n * G, 1)
+        d = MLPFast._drop((self.seed if drop_seed is None else drop_seed, drop_stream, drop_p))
+        o = evx_qmlp_fwd_out(q=_p(q), actions=_p(actions), act_seed=act_seed, act_offset=act_offset)
+        eps = (C.c_float * G)(*[float(e) for e in epsilon])
+        return C.byref(lay_c), obs.data_ptr(), n, G, C.byref(self.fast.c), C.byref(d), C.byref(o), eps
+
+    def act_blocks(self, lay_c, obs: torch.Tensor, n: int, epsilon, actions=None, q=None, act_seed=0, act_offset=0,
+                   drop_p=DROPOUT_P, drop_seed=None, drop_stream=None):
+        """DQNAgent.act of every net on its own block of rows (evx_qmlp_act_gb, one launch): net g
+        reads rows [g n, (g + 1) n) of obs and writes the same rows of q / actions, explores with
+        epsilon[g] (a sequence of G floats) and draws with counters act_offset + g n + i; dropout
+        rows keyed g n + i -- MLPFast.act of the block with drop row0 = g n, bit for bit."""
+        if drop_stream is None:
+            self._act_calls += 1
+            drop_stream = 0x40000000 + self._act_calls
+        args = self._act_blocks_args(lay_c, obs, n, epsilon, actions, q, act_seed, act_offset, drop_p, drop_seed,
+                                     drop_stream)
+        check(lib().evx_qmlp_act_gb(*args, _stream()), "qmlp_act_gb")
+
+    def act_blocks_plan(self, lay_c, obs: torch.Tensor, n: int, epsilon, actions=None, q=None, **kw) -> evx_qmlp_fwd_plan:
+        """What act_blocks with these arguments launches (evx_qmlp_act_gb_plan_query; nothing launched)."""
+        plan = evx_qmlp_fwd_plan()
+        args = self._act_blocks_args(lay_c, obs, n, epsilon, actions, q, kw.get("act_seed", 0), kw.get("act_offset", 0),
+                                     kw.get("drop_p", DROPOUT_P), kw.get("drop_seed"), kw.get("drop_stream", 0))
+        check(lib().evx_qmlp_act_gb_plan_query(*args, C.byref(plan)), "qmlp_act_gb_plan_query")
+        return plan
+
     # ---------------------------------------------------------------- learn
-    def learn_obs(self, lay_c, s_obs, a, r, done, s2_obs, B: int, update: bool = True):
+    def learn_obs(self, lay_c, s_obs, a, r, done, s2_obs, B: int, update: bool = True, gamma_row=None, lr=None):
         """One DQNAgent.learn step of every net: net g's batch is rows [g B, (g + 1) B) of s_obs /
-        a / r / done / s2_obs. Returns the per-net losses [G] (device, no host sync)."""
+        a / r / done / s2_obs. Returns the per-net losses [G] (device, no host sync).
+        gamma_row: device f32 [G B], the discount of every row in place of gamma (evx_td_loss_opt;
+        evacx.population: gamma[g] on every row of block g); lr: step_optimizer's. None: the
+        entries and the bits of a call without them."""
         G = self.G
         if B <= 0 or B % 2:
             raise ValueError("learn_obs: B must be even and > 0")
+        if gamma_row is not None and (gamma_row.dtype != torch.float32 or gamma_row.numel() < G * B):
+            raise ValueError(f"learn_obs: gamma_row must be a float32 tensor of at least G B = {G * B} elements")
         for name, t, w in (("s_obs", s_obs, 8), ("s2_obs", s2_obs, 8), ("a", a, 1), ("r", r, 1), ("done", done, 1)):
             _need("learn_obs " + name, t, G * B, w)
         X = self._buf("x", G * B * K1X, torch.int16)
@@ -155,15 +193,22 @@ class GroupedLearner:
                                         C.byref(o_tg), _stream()), "qmlp_forward2_g")
         dQ = self._buf("dq", G * B * NACT, torch.float32)
         tw = self._buf("td_ws", max(1, int(lib().evx_td_loss_ws_floats(B, G))), torch.float32)
-        check(lib().evx_td_loss_zero_g(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(), done.data_ptr(),
-                                       self.gamma, B, G, None, dQ.data_ptr(), self.loss.data_ptr(), None,
-                                       self.gflat.data_ptr(), self.gflat.numel(), tw.data_ptr(), tw.numel(),
-                                       _stream()), "td_loss_zero_g")
+        if gamma_row is None:
+            check(lib().evx_td_loss_zero_g(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(),
+                                           done.data_ptr(), self.gamma, B, G, None, dQ.data_ptr(),
+                                           self.loss.data_ptr(), None, self.gflat.data_ptr(), self.gflat.numel(),
+                                           tw.data_ptr(), tw.numel(), _stream()), "td_loss_zero_g")
+        else:
+            o = td_opts(gamma_row=gamma_row)
+            check(lib().evx_td_loss_opt(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(), done.data_ptr(),
+                                        self.gamma, B, G, None, dQ.data_ptr(), self.loss.data_ptr(), None,
+                                        self.gflat.data_ptr(), self.gflat.numel(), tw.data_ptr(), tw.numel(),
+                                        C.byref(o), _stream()), "td_loss_opt")
         if self.stats is not None:
-            self.stat_batch = (Q, Qt, a, r, done, None, None, B)
+            self.stat_batch = (Q, Qt, a, r, done, None, gamma_row, B)
         self._backward(B, dQ, X, H1, H2)
         if update:
-            self.step_optimizer()
+            self.step_optimizer(lr=lr)
         return self.loss
 
     def _backward(self, B, dQ, X, H1, H2):
@@ -179,19 +224,25 @@ class GroupedLearner:
                                            H2.data_ptr(), float(self.drop_p), dz2.data_ptr(), dz1.data_ptr(),
                                            C.byref(g), self._ss.data_ptr(), _stream()), "qmlp_backward_ss_g")
 
-    def step_optimizer(self):
-        """clip_grad_norm_(net g, max_norm) + Adam for every net (one launch, evx_qmlp_adam_pack3_g)."""
+    def step_optimizer(self, lr=None):
+        """clip_grad_norm_(net g, max_norm) + Adam for every net (one launch, evx_qmlp_adam_pack3_g).
+        lr: a sequence of G learning rates, net g's in place of self.lr (evx_qmlp_adam_pack3_gl)."""
+        if lr is not None and len(lr) != self.G:
+            raise ValueError(f"step_optimizer: lr must hold {self.G} learning rates, not {len(lr)}")
         self.adam_step += 1
         h = evx_adam(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=0.0,
                      step=self.adam_step)
         b = self.fast.bufs
-        check(lib().evx_qmlp_adam_pack3_g(self.flat.data_ptr(), self.gflat.data_ptr(), self.m.data_ptr(),
-                                          self.v.data_ptr(), float(self.max_norm or 0.0), C.byref(h),
-                                          b["w1b"].data_ptr(), b["w1l"].data_ptr(), b["b1c"].data_ptr(),
-                                          b["w2b"].data_ptr(), b["w2l"].data_ptr(), b["w2t"].data_ptr(),
-                                          b["w2tl"].data_ptr(), b["w1o"].data_ptr(), b["w1ol"].data_ptr(),
-                                          self._ss.data_ptr(), self.nss, self.norm.data_ptr(), self.G, _stream()),
-              "qmlp_adam_pack3_g")
+        args = (self.flat.data_ptr(), self.gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                float(self.max_norm or 0.0), C.byref(h), b["w1b"].data_ptr(), b["w1l"].data_ptr(),
+                b["b1c"].data_ptr(), b["w2b"].data_ptr(), b["w2l"].data_ptr(), b["w2t"].data_ptr(),
+                b["w2tl"].data_ptr(), b["w1o"].data_ptr(), b["w1ol"].data_ptr(), self._ss.data_ptr(), self.nss,
+                self.norm.data_ptr(), self.G)
+        if lr is None:
+            check(lib().evx_qmlp_adam_pack3_g(*args, _stream()), "qmlp_adam_pack3_g")
+        else:
+            lrs = (C.c_float * self.G)(*[float(x) for x in lr])
+            check(lib().evx_qmlp_adam_pack3_gl(*args, lrs, _stream()), "qmlp_adam_pack3_gl")
         if self.stats is not None and self.stat_batch is not None:  # after Adam has written norm
             Q, Qt, a, r, done, sel, gamma_row, B = self.stat_batch
             n = self.G * B

@@ -729,6 +729,15 @@ int evx_qmlp_adam_pack3_g(float *p, float *g, float *m, float *v, float max_norm
                           uint16_t *w1l, float *b1c, uint16_t *w2b, uint16_t *w2l, uint16_t *w2t, uint16_t *w2tl,
                           uint16_t *w1o, uint16_t *w1ol, const float *ss, int32_t nss, float *norm_out, int32_t nets,
                           void *stream);
+/* evx_qmlp_adam_pack3_g with a learning rate per net: lr [nets] on the host, net g's step size
+ * (float)(lr[g] / (1 - beta1^step)) -- the expression of h->lr in the entries above, so equal lr give
+ * evx_qmlp_adam_pack3_g bit for bit; h->lr is not read. Betas, eps, step, weight decay and max_norm are
+ * common to the nets. -22 before any launch: a NULL required pointer, nets outside 1..64, an lr that
+ * is not finite. */
+int evx_qmlp_adam_pack3_gl(float *p, float *g, float *m, float *v, float max_norm, const evx_adam *h, uint16_t *w1b,
+                           uint16_t *w1l, float *b1c, uint16_t *w2b, uint16_t *w2l, uint16_t *w2t, uint16_t *w2tl,
+                           uint16_t *w1o, uint16_t *w1ol, const float *ss, int32_t nss, float *norm_out, int32_t nets,
+                           const float *lr, void *stream);
 /* The launch shape of the grouped x3 learn chain (evx_qmlp_forward2_g, evx_td_loss_zero_g,
  * evx_qmlp_backward_ss_g) at B rows per net: every figure depends on B and nets alone. */
 typedef struct {
@@ -788,6 +797,41 @@ int evx_qmlp_fwd_plan_query(const evx_layout *lay, int32_t n, const evx_obs *obs
 int evx_qmlp_act_plan_query(const evx_layout *lay, const evx_obs *obs, int32_t n, const evx_qmlp_params *p,
                             const evx_qmlp_dropout *drop, const evx_qmlp_fwd_out *out, int32_t nets,
                             int32_t kernel64, int32_t ncu, evx_qmlp_fwd_plan *plan);
+
+/* ---- A population of independent learners (evacx/population.py): member k owns a contiguous block
+ * of envs, so its rows are a block of every row buffer, not a stride through it. */
+/* The route of evx_qmlp_act_gb, appended to the EVX_FWD_* values above (an enumerator: the #define
+ * list stays the set of routes the single-net and per-robot entries take). */
+enum { EVX_FWD_ACT_GROUPED_BLOCKED = 10 /* qact3h_gb_kernel (blockIdx.y = net, its rows one block) */ };
+/* The blocked grouped act: net g reads obs rows [g n, (g + 1) n) and writes the same rows of q /
+ * actions (n rows per net, even): the single-net act of that block through net g with dropout row0
+ * = g n, exploration epsilon[g] (host array [nets]; out->epsilon is not read) and epsilon draws
+ * counted from out->act_offset + g n. x3 parameters in the [nets] layout above. No act table, no
+ * permutation, no act_ws. -22 before any launch: a NULL required pointer, nets outside 1..64, n odd,
+ * an epsilon that is not finite, and what evx_qmlp_act_g refuses. */
+int evx_qmlp_act_gb(const evx_layout *lay, const evx_obs *obs, int32_t n, int32_t nets, const evx_qmlp_params *p,
+                    const evx_qmlp_dropout *drop, const evx_qmlp_fwd_out *out, const float *epsilon, void *stream);
+/* Its plan (as evx_qmlp_act_plan_query: the launcher's own decision, nothing launched, no device call). */
+int evx_qmlp_act_gb_plan_query(const evx_layout *lay, const evx_obs *obs, int32_t n, int32_t nets,
+                               const evx_qmlp_params *p, const evx_qmlp_dropout *drop, const evx_qmlp_fwd_out *out,
+                               const float *epsilon, evx_qmlp_fwd_plan *plan);
+/* `nets` replay rings of rp->capacity slots each as one allocation [nets][capacity] per array of rp
+ * (ring k's arrays start k * capacity slots after ring 0's, which rp points at). Every ring takes n
+ * rows per push, so pos and size are common to them.
+ * evx_replay_push_blocks: evx_replay_push_term of rows [k n, (k + 1) n) of s / s2 / s2_term / a into
+ * ring k at pos, for every k in one launch: row k n + i goes to slot (pos + i) mod capacity with the
+ * reward and done flag of env (k n + i) / agents_per_env, s2_term (may be NULL) where that env is done.
+ * evx_replay_sample_blocks: rows [k B, (k + 1) B) of the outputs are what
+ * evx_replay_sample(ring k, size, B, seed, offset + k B) draws, for every k in one launch.
+ * -22 before any launch: a NULL required pointer, nets outside 1..64, n or B odd, a capacity that
+ * does not hold n, n no multiple of agents_per_env, pos outside [0, capacity), size outside
+ * [1, capacity], B > size. */
+int evx_replay_push_blocks(const evx_replay *rp, const evx_obs *s, const evx_obs *s2, const evx_obs *s2_term,
+                           const int32_t *a, const double *r_env, const uint8_t *done_env, int32_t n, int32_t nets,
+                           int32_t agents_per_env, int64_t pos, void *stream);
+int evx_replay_sample_blocks(const evx_replay *rp, int64_t size, int32_t B, int32_t nets, uint64_t seed,
+                             uint64_t offset, evx_obs *s, evx_obs *s2, int32_t *a, float *r, uint8_t *done,
+                             void *stream);
 
 /* ---- QMIX mixer (runners/train_qmix.py:39-54 MixingNetwork, loss :78-104) for n <= 16 agents:
  * Q / Qt [n][B][A] (evx_qmlp_forward2_g), act [n][B], rew / done [B]; mix / mix_t the online /
