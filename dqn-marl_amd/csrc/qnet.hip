@@ -1889,6 +1889,7 @@ int evx_conv3x3_gemm(const evx_gemm_desc* g, int32_t mode, int32_t cs, void* str
 int evx_colsum(const float* X, int64_t ld, int32_t M, int32_t N, float* out, int32_t accum, float* scratch,
                int32_t scratch_elems, void* stream) {
     if (M <= 0 || N <= 0) return 0;
+    if (!X || !out || !scratch) return fail(-22, "colsum: NULL argument");
     int chunks = (M + evxq::COLSUM_ROWS - 1) / evxq::COLSUM_ROWS;
     if ((int64_t)chunks * N > scratch_elems) chunks = scratch_elems / N;
     if (chunks < 1) return fail(-22, "colsum: scratch too small");
@@ -1970,6 +1971,8 @@ int evx_td_loss(const float* Q, const float* Qt, int32_t A, const int32_t* act, 
 }
 
 int evx_sumsq_norm(const float* g, int64_t n, float* scratch, int32_t scratch_elems, float* norm, void* stream) {
+    if (scratch_elems < 1) return fail(-22, "sumsq: scratch_elems must be >= 1");
+    if (!scratch || !norm || (n > 0 && !g)) return fail(-22, "sumsq: NULL argument");
     int parts = (int)((n + 4095) / 4096);
     if (parts > scratch_elems) parts = scratch_elems;
     if (parts > 2048) parts = 2048;
@@ -1982,7 +1985,12 @@ int evx_sumsq_norm(const float* g, int64_t n, float* scratch, int32_t scratch_el
 int evx_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const float* norm, float max_norm,
                   const evx_adam* h, void* stream) {
     if (!h) return fail(-22, "adam: NULL hyper-parameters");
+    if (h->step < 1) return fail(-22, "adam: step must be >= 1 (the bias corrections divide by 1 - beta^step)");
+    if (!(h->beta1 >= 0.f && h->beta1 < 1.f) || !(h->beta2 >= 0.f && h->beta2 < 1.f))
+        return fail(-22, "adam: betas must lie in [0, 1)");
+    if (!std::isfinite(h->lr) || !std::isfinite(h->eps)) return fail(-22, "adam: lr and eps must be finite");
     if (n <= 0) return 0;
+    if (!p || !g || !m || !v) return fail(-22, "adam: NULL argument");
     const double bc1 = 1.0 - pow((double)h->beta1, (double)h->step);
     const double bc2 = 1.0 - pow((double)h->beta2, (double)h->step);
     const float step_size = (float)(h->lr / bc1);
@@ -1995,7 +2003,9 @@ int evx_clip_adam(float* p, float* g, float* m, float* v, int64_t n, const float
 }
 
 int evx_dropout_mask(uint8_t* mask, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream) {
+    if (!(p >= 0.f && p <= 1.f)) return fail(-22, "dropout_mask: p must lie in [0, 1]");
     if (n <= 0) return 0;
+    if (!mask) return fail(-22, "dropout_mask: NULL argument");
     hipLaunchKernelGGL(evxq::dropout_mask_kernel, dim3(nblk((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, mask, n,
                        p, seed, offset);
     return hip_status("dropout_mask");
@@ -2103,32 +2113,40 @@ int evx_replay_nstep(const evx_replay* rp, const int64_t* idx, int32_t B, int64_
 
 int evx_gather_obs(const evx_obs* src, const int64_t* idx, int32_t n, evx_obs* dst, void* stream) {
     if (n <= 0) return 0;
+    if (!src || !idx || !dst) return fail(-22, "gather_obs: NULL argument");
     hipLaunchKernelGGL(evxq::gather_rows_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, src, idx, n, dst);
     return hip_status("gather_obs");
 }
 
 int evx_im2col3x3(const float* x, int32_t B, int32_t C, int32_t nhwc, float* cols, void* stream) {
+    if (B <= 0) return 0;
+    if (C < 1) return fail(-22, "im2col: C must be >= 1");
+    if (!x || !cols) return fail(-22, "im2col: NULL argument");
     const int64_t total = (int64_t)B * 121 * C * 9;
-    if (total <= 0) return 0;
     hipLaunchKernelGGL(evxq::im2col_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, B, C, nhwc, cols);
     return hip_status("im2col");
 }
 
 int evx_col2im3x3(const float* dcols, int32_t B, int32_t C, float* dx, void* stream) {
+    if (B <= 0) return 0;
+    if (C < 1) return fail(-22, "col2im: C must be >= 1");
+    if (!dcols || !dx) return fail(-22, "col2im: NULL argument");
     const int64_t total = (int64_t)B * C * 121;
-    if (total <= 0) return 0;
     hipLaunchKernelGGL(evxq::col2im_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, dcols, B, C, dx);
     return hip_status("col2im");
 }
 
 int evx_relu_grad(float* dy, const float* y, int64_t n, void* stream) {
     if (n <= 0) return 0;
+    if (!dy || !y) return fail(-22, "relu_grad: NULL argument");
     hipLaunchKernelGGL(evxq::relu_grad_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, dy, y, n);
     return hip_status("relu_grad");
 }
 
 int evx_pix_split(const float* src, int32_t B, int32_t C, uint16_t* dst, void* stream) {
-    if (B <= 0 || C <= 0) return 0;
+    if (B <= 0) return 0;
+    if (C < 1) return fail(-22, "pix_split: C must be >= 1");
+    if (!src || !dst) return fail(-22, "pix_split: NULL argument");
     const size_t lds = (size_t)121 * (C + 1) * 4;
     if (lds > 64 * 1024) return fail(-22, "pix_split: C > 134 channels");
     hipLaunchKernelGGL(evxq::pix_split_kernel, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, src, B, C,
@@ -2137,8 +2155,10 @@ int evx_pix_split(const float* src, int32_t B, int32_t C, uint16_t* dst, void* s
 }
 
 int evx_pix_nchw(const float* src, int32_t B, int32_t C, int32_t to_nchw, float* dst, void* stream) {
+    if (B <= 0) return 0;
+    if (C < 1) return fail(-22, "pix_nchw: C must be >= 1");
+    if (!src || !dst) return fail(-22, "pix_nchw: NULL argument");
     const int64_t total = (int64_t)B * C * 121;
-    if (total <= 0) return 0;
     const size_t lds = (size_t)121 * (C + 1) * 4;
     if (lds > 64 * 1024) {  // the LDS tile holds C <= 134: element-wise beyond
         hipLaunchKernelGGL(evxq::pix2nchw_flat_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, src, total,

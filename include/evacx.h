@@ -328,7 +328,9 @@ typedef struct {
  * pointers are only tested for NULL and alignment). An argument error the call would report before
  * launching comes back as the same negative code with the same evx_q_last_error text. */
 int evx_gemm_plan_query(const evx_gemm_desc *g, int32_t mode, int32_t cs, evx_gemm_plan *out);
-/* out[n] (+)= sum_m X[m*ld+n] (bias gradients), fixed summation order */
+/* out[n] (+)= sum_m X[m*ld+n] (bias gradients), fixed summation order. scratch: one partial per
+ * 64 rows and column, ceil(M / 64) * N floats; a shorter one (scratch_elems >= N) makes the chunks
+ * longer. M <= 0 or N <= 0: 0, nothing done. -22: scratch_elems < N; a NULL X, out or scratch. */
 int evx_colsum(const float *X, int64_t ld, int32_t M, int32_t N, float *out, int32_t accum, float *scratch,
                int32_t scratch_elems, void *stream);
 /* DQNAgent.learn TD step (agents/dqn_agent.py:143-151): loss = mean((Q[a] - (r + gamma*max Qt * !done))^2),
@@ -350,12 +352,21 @@ int evx_td_loss_w(const float *Q, const float *Qt, int32_t A, const int32_t *act
 int evx_td_loss_zero(const float *Q, const float *Qt, int32_t A, const int32_t *act, const float *rew,
                      const uint8_t *done, float gamma, int32_t B, const float *w, float *dQ, float *loss, float *td_abs,
                      float *zero, int64_t nzero, float *ws, int64_t ws_floats, void *stream);
-/* ||g||_2 into norm[0] (clip_grad_norm_'s total norm) */
+/* ||g||_2 into norm[0] (clip_grad_norm_'s total norm). scratch: one partial per 4096 elements, at
+ * most min(scratch_elems, 2048) of them. n <= 0 writes norm[0] = 0 (g is not read). -22:
+ * scratch_elems < 1; a NULL scratch or norm; a NULL g with n > 0. */
 int evx_sumsq_norm(const float *g, int64_t n, float *scratch, int32_t scratch_elems, float *norm, void *stream);
-/* g *= min(1, max_norm/(norm+1e-6)) (skipped if norm NULL) then one torch.optim.Adam step */
+/* g *= min(1, max_norm/(norm+1e-6)) (skipped if norm NULL or max_norm <= 0) then one
+ * torch.optim.Adam step (g + weight_decay p when weight_decay != 0; g is written back as used).
+ * -22, whatever n: a NULL h; h->step < 1 (the bias corrections divide by 1 - beta^step: step 0
+ * would write infinities into every parameter); a beta outside [0, 1) or NaN; a non-finite lr or
+ * eps. Then n <= 0: 0, nothing done. -22: a NULL p, g, m or v. */
 int evx_clip_adam(float *p, float *g, float *m, float *v, int64_t n, const float *norm, float max_norm,
                   const evx_adam *h, void *stream);
-/* nn.Dropout keep-mask (1 with probability 1-p), counter-based Philox4x32-10 */
+/* nn.Dropout keep-mask (1 with probability 1-p), counter-based Philox4x32-10: element i is lane
+ * i % 4 of counter (i / 4 + offset, 0x5eed, 0) under the key seed, kept where u01 >= p; a call uses
+ * ceil(n / 4) counters (oracle/draw_oracle.c orc_dropout_mask restates it). -22, whatever n: p
+ * outside [0, 1] or NaN. Then n <= 0: 0. -22: a NULL mask. */
 int evx_dropout_mask(uint8_t *mask, int64_t n, float p, uint64_t seed, uint64_t offset, void *stream);
 /* DQNAgent.act (agents/dqn_agent.py:101-124): epsilon-greedy over argmax_a Q[i][a] */
 int evx_act(const float *Q, int32_t n, int32_t A, float epsilon, uint64_t seed, uint64_t offset,
@@ -480,8 +491,13 @@ int evx_floor_field(int32_t n_layouts, int32_t GX, int32_t GY, const uint8_t *va
                     const double *pen, double *floor, int32_t *passes, void *stream);
 const char *evx_floor_last_error(void);
 
+/* dst[i] = src[idx[i]], i < n (idx within the source: not checked). n <= 0: 0. -22: a NULL src,
+ * idx or dst. */
 int evx_gather_obs(const evx_obs *src, const int64_t *idx, int32_t n, evx_obs *dst, void *stream);
-/* DQNNetwork conv layers (agents/dqn_agent.py:22-24) as im2col + GEMM on 11x11 maps */
+/* DQNNetwork conv layers (agents/dqn_agent.py:22-24) as im2col + GEMM on 11x11 maps: x [B][C][11][11]
+ * (nhwc: [B][11][11][C]) <-> cols [B*121][C*9], k = c*9 + ky*3 + kx; col2im sums the <= 9 taps of an
+ * input element in a fixed order. These two, evx_pix_split and evx_pix_nchw: B <= 0: 0, nothing done
+ * (whatever C); else -22 for C < 1 and for a NULL pointer. */
 int evx_im2col3x3(const float *x, int32_t B, int32_t C, int32_t nhwc, float *cols, void *stream);
 int evx_col2im3x3(const float *dcols, int32_t B, int32_t C, float *dx, void *stream);
 /* NCHW [B][C][121] f32 -> pixel-major [B][121*C] as bf16 hi / lo planes (lo B*121*C elements after
@@ -490,6 +506,7 @@ int evx_pix_split(const float *src, int32_t B, int32_t C, uint16_t *dst, void *s
 /* [B*121][C] pixel-major <-> [B][C][121] NCHW (to_nchw): through LDS for C <= 134, element-wise
    beyond (any C) */
 int evx_pix_nchw(const float *src, int32_t B, int32_t C, int32_t to_nchw, float *dst, void *stream);
+/* dy[i] = y[i] > 0 ? dy[i] : 0 (a NaN y zeroes dy). n <= 0: 0. -22: a NULL dy or y. */
 int evx_relu_grad(float *dy, const float *y, int64_t n, void *stream);
 const char *evx_q_last_error(void);
 

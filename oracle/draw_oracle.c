@@ -8,6 +8,8 @@
  *                        csrc/qmlp.hip fc3_act)
  *   orc_replay_indices : evx_replay_sample / _window (csrc/qnet.hip replay_sample_kernel)
  *   orc_dropout_keep   : the fused MLP kernels' dropout hash (csrc/qmlp.hip drop_row/drop_pair)
+ *   orc_dropout_mask   : evx_dropout_mask, the dense learner's keep mask (csrc/qnet.hip
+ *                        dropout_mask_kernel)
  */
 #include <stdint.h>
 
@@ -35,6 +37,19 @@ void orc_epsilon_greedy(const float *Q, int n, int A, float epsilon, uint64_t se
             if (u01(r[0]) <= epsilon) best = (int)(((uint64_t)r[1] * (uint64_t)A) >> 32);
         }
         out[i] = best;
+    }
+}
+
+/* keep[i] of evx_dropout_mask: element i is lane i % 4 of Philox(ctr = (i / 4 + offset) lo, hi,
+ * 0x5eed, 0; key = seed lo, hi); kept (1) where u01(lane) >= p, so p = 0 keeps all, p = 1 none */
+void orc_dropout_mask(int64_t n, float p, uint64_t seed, uint64_t offset, uint8_t *keep) {
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    for (int64_t i4 = 0; i4 < n; i4 += 4) {
+        const uint64_t c = (uint64_t)i4 / 4 + offset;
+        const uint32_t ctr[4] = {(uint32_t)c, (uint32_t)(c >> 32), 0x5eedu, 0u};
+        uint32_t r[4];
+        orc_philox4x32_10(ctr, key, r);
+        for (int j = 0; j < 4 && i4 + j < n; j++) keep[i4 + j] = u01(r[j]) >= p ? 1 : 0;
     }
 }
 

@@ -267,6 +267,17 @@ def epsilon_greedy(Q, epsilon, seed, offset):
     return out
 
 
+def dropout_mask(n, p, seed, offset):
+    """evx_dropout_mask restated: uint8 [n], element i = lane i % 4 of Philox counter i // 4 + offset
+    under the key 0x5eed, kept where u01 >= p."""
+    keep = np.zeros(int(n), np.uint8)
+    L = lib()
+    L.orc_dropout_mask.argtypes = [C.c_int64, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.orc_dropout_mask.restype = None
+    L.orc_dropout_mask(int(n), float(p), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _p(keep))
+    return keep
+
+
 def replay_indices(base, size, capacity, B, seed, offset, stream=0):
     """evx_replay_sample(_window / _agents)'s ring slots restated (without replacement): int64 [B]."""
     idx = np.zeros(B, np.int64)
