@@ -17,11 +17,12 @@
 
 #include "evacx.h"
 #include "evx_host.h"
+#include "evx_reduce.h"
 
 namespace evxe {
 
-constexpr int NT = 256;      // update / discard / clear: one env per thread
-constexpr int RT = EVX_EPISODE_REDUCE_SPAN;  // the reduce's workgroup: envs per pass
+constexpr int NT = 256;  // update / discard / clear: one env per thread
+using evxr::RT, evxr::in_row, evxr::tree, evxr::AddI, evxr::AddD, evxr::MinD, evxr::MaxD;
 
 // ret += reward, len += 1 (the reference's total_reward += reward, runners/train_dqn.py:109, in
 // step order); a finished episode is folded into the window, the last-episode slots and the
@@ -117,37 +118,7 @@ __device__ __forceinline__ void acc_add(Acc& a, const Acc& b) {
     a.mx = b.mx > a.mx ? b.mx : a.mx;
 }
 
-struct AddI {
-    __device__ int64_t operator()(int64_t a, int64_t b) const { return a + b; }
-};
-struct AddD {
-    __device__ double operator()(double a, double b) const { return a + b; }
-};
-struct MinD {
-    __device__ double operator()(double a, double b) const { return b < a ? b : a; }
-};
-struct MaxD {
-    __device__ double operator()(double a, double b) const { return b > a ? b : a; }
-};
-// s[t] = op(s[t], s[t + h]) for h = RT/2 .. 1; every thread returns s[0]
-template <typename T, typename Op>
-__device__ __forceinline__ T tree(T* s, int t, T v, Op op) {
-    s[t] = v;
-    __syncthreads();
-    for (int h = RT / 2; h > 0; h >>= 1) {
-        if (t < h) s[t] = op(s[t], s[t + h]);
-        __syncthreads();
-    }
-    const T r = s[0];
-    __syncthreads();
-    return r;
-}
-
-// One workgroup per output row (row r < n_layouts: the envs of layout r; row n_layouts: all).
-// Summation order (stated in evacx.h): thread t adds its row's envs t, t + RT, t + 2 RT, ... in
-// ascending env order starting from 0; the RT thread sums are then added pairwise in LDS,
-// s[t] = s[t] + s[t + h] for h = RT/2, RT/4, ..., 1. An env that is not of the row adds nothing
-// (it is skipped, not added as zero: -0.0 stays out of it).
+// One workgroup per output row, in the order of evx_reduce.h.
 __global__ __launch_bounds__(RT) void episode_reduce_kernel(evx_episodes ep, const int32_t* __restrict__ layout_idx,
                                                             int n_layouts, int64_t cap,
                                                             evx_episode_row* __restrict__ out) {
@@ -156,7 +127,7 @@ __global__ __launch_bounds__(RT) void episode_reduce_kernel(evx_episodes ep, con
     const int row = blockIdx.x, t = threadIdx.x;
     Acc a = {0, 0, 0, 0, 0, 0, 0.0, 0.0, INFINITY, -INFINITY};
     for (int e = t; e < ep.E; e += RT) {
-        if (row < n_layouts && (layout_idx ? layout_idx[e] : 0) != row) continue;
+        if (!in_row(layout_idx, n_layouts, row, e)) continue;
         Acc b;
         b.n = ep.w_n[e];
         b.len = ep.w_len[e];
@@ -190,31 +161,21 @@ __global__ __launch_bounds__(RT) void episode_reduce_kernel(evx_episodes ep, con
 }  // namespace evxe
 
 namespace {
+using evxh::blocks;
 using evxh::fail;
+using evxh::failf;
 using evxh::hip_status;
 int check_ep(const evx_episodes* ep, const char* who) {
-    static thread_local char msg[128];
-    if (!ep) {
-        snprintf(msg, sizeof(msg), "%s: NULL episode descriptor", who);
-        return fail(-22, msg);
-    }
-    if (ep->E < 1) {
-        snprintf(msg, sizeof(msg), "%s: E must be >= 1", who);
-        return fail(-22, msg);
-    }
+    if (!ep) return failf(-22, "%s: NULL episode descriptor", who);
+    if (ep->E < 1) return failf(-22, "%s: E must be >= 1", who);
     if (!ep->ret || !ep->len || !ep->w_n || !ep->w_len || !ep->w_evac || !ep->w_dead || !ep->w_ret || !ep->w_ret2 ||
         !ep->w_min || !ep->w_max || !ep->last_ret || !ep->last_len || !ep->last_evac || !ep->last_dead ||
-        !ep->n_total) {
-        snprintf(msg, sizeof(msg), "%s: NULL episode buffer", who);
-        return fail(-22, msg);
-    }
-    if (ep->tab_slots < 0 || (ep->tab_slots > 0 && (!ep->tab_ret || !ep->tab_len || !ep->tab_evac || !ep->tab_dead))) {
-        snprintf(msg, sizeof(msg), "%s: episode table slots without its buffers", who);
-        return fail(-22, msg);
-    }
+        !ep->n_total)
+        return failf(-22, "%s: NULL episode buffer", who);
+    if (ep->tab_slots < 0 || (ep->tab_slots > 0 && (!ep->tab_ret || !ep->tab_len || !ep->tab_evac || !ep->tab_dead)))
+        return failf(-22, "%s: episode table slots without its buffers", who);
     return 0;
 }
-unsigned blocks(int32_t E) { return (unsigned)((E + evxe::NT - 1) / evxe::NT); }
 }  // namespace
 
 extern "C" {
@@ -223,8 +184,8 @@ const char* evx_episode_last_error(void) { return evxh::g_err; }
 
 int evx_episode_init(const evx_episodes* ep, void* stream) {
     if (int rc = check_ep(ep, "episode_init")) return rc;
-    hipLaunchKernelGGL(evxe::episode_clear_kernel, dim3(blocks(ep->E)), dim3(evxe::NT), 0, (hipStream_t)stream, *ep,
-                       1);
+    hipLaunchKernelGGL(evxe::episode_clear_kernel, dim3(blocks(ep->E, evxe::NT)), dim3(evxe::NT), 0,
+                       (hipStream_t)stream, *ep, 1);
     return hip_status("episode_init");
 }
 
@@ -232,33 +193,24 @@ int evx_episode_update(const evx_episodes* ep, const double* reward, const uint8
                        int64_t cap, void* stream) {
     if (int rc = check_ep(ep, "episode_update")) return rc;
     if (!reward || !done || !counts) return fail(-22, "episode_update: NULL reward, done or counts");
-    hipLaunchKernelGGL(evxe::episode_update_kernel, dim3(blocks(ep->E)), dim3(evxe::NT), 0, (hipStream_t)stream, *ep,
-                       reward, done, counts, cap);
+    hipLaunchKernelGGL(evxe::episode_update_kernel, dim3(blocks(ep->E, evxe::NT)), dim3(evxe::NT), 0,
+                       (hipStream_t)stream, *ep, reward, done, counts, cap);
     return hip_status("episode_update");
 }
 
 int evx_episode_discard(const evx_episodes* ep, const uint8_t* mask, void* stream) {
     if (int rc = check_ep(ep, "episode_discard")) return rc;
-    hipLaunchKernelGGL(evxe::episode_discard_kernel, dim3(blocks(ep->E)), dim3(evxe::NT), 0, (hipStream_t)stream, *ep,
-                       mask);
+    hipLaunchKernelGGL(evxe::episode_discard_kernel, dim3(blocks(ep->E, evxe::NT)), dim3(evxe::NT), 0,
+                       (hipStream_t)stream, *ep, mask);
     return hip_status("episode_discard");
 }
 
 int evx_episode_reduce(const evx_episodes* ep, const int32_t* layout_idx, int32_t n_layouts, int64_t cap,
                        evx_episode_row* out, int32_t clear, void* stream) {
     if (int rc = check_ep(ep, "episode_reduce")) return rc;
-    if (!out) return fail(-22, "episode_reduce: NULL output rows");
-    if (n_layouts < 1 || n_layouts > 65535) return fail(-22, "episode_reduce: n_layouts must be 1..65535");
-    if (n_layouts > 1 && !layout_idx) return fail(-22, "episode_reduce: several layouts need layout_idx");
-    const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(evxe::episode_reduce_kernel, dim3((unsigned)n_layouts + 1), dim3(evxe::RT), 0, st, *ep,
-                       layout_idx, n_layouts, cap, out);
-    if (int rc = hip_status("episode_reduce")) return rc;
-    if (clear) {  // after every row's workgroup has read the window (stream order)
-        hipLaunchKernelGGL(evxe::episode_clear_kernel, dim3(blocks(ep->E)), dim3(evxe::NT), 0, st, *ep, 0);
-        return hip_status("episode_reduce (clear)");
-    }
-    return 0;
+    if (int rc = evxr::check_rows("episode_reduce", out, n_layouts, layout_idx)) return rc;
+    return evxr::reduce_rows("episode_reduce", stream, clear, evxe::episode_reduce_kernel, evxe::episode_clear_kernel,
+                             evxe::NT, *ep, layout_idx, n_layouts, cap, out);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -42,6 +43,18 @@ inline int fail(int code, const char* msg) {
     snprintf(g_err, sizeof(g_err), "%s", msg);
     return code;
 }
+
+// fail() with a printf format: the text goes straight into g_err.
+__attribute__((format(printf, 2, 3))) inline int failf(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+// Workgroups of `per` elements that cover n.
+inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // 0 when e (default: the pending launch error) is hipSuccess, else -5 with "<what>: <hip's text>".
 inline int hip_status(const char* what, hipError_t e = hipGetLastError()) {

@@ -18,18 +18,17 @@
 #include "evacx.h"
 #include "evx_device.h"
 #include "evx_host.h"
+#include "evx_reduce.h"
 
-// (this file's kernels and constants share the name evxh with evx_host.h's host helpers -- the
-// error text, fail, hip_status -- which the entry points below use; the two sets do not overlap)
-namespace evxh {
+namespace evxhl {
 
 constexpr int NT = 256;                      // init / clear: one env per thread
-constexpr int RT = EVX_EPISODE_REDUCE_SPAN;  // the reduce's workgroup: envs per pass
 constexpr int WAVE = 64;                     // update: one wave per env
 constexpr int LEAF_CAP = 256;                // numpy pairwise leaves of one chunk (a leaf of a split holds > 56
                                              // elements, so a chunk of <= 8192 has < 147 of them)
 constexpr int NP_CHUNK = 8192;               // np.mean's reduction buffer: elements per pairwise sum
 constexpr uint32_t DEAD_BIT = 1u << 25;      // pk: the person is dead
+using evxr::RT, evxr::in_row, evxr::tree, evxr::AddI, evxr::AddD, evxr::MinD;
 
 // np.mean of `n` compacted healths in `a` (LDS), the whole wave; the result is valid on lane 0.
 // numpy cuts the list into consecutive chunks of NP_CHUNK elements, sums each chunk with its
@@ -161,32 +160,7 @@ __global__ __launch_bounds__(NT) void health_clear_kernel(evx_health h, int all)
     }
 }
 
-struct AddI {
-    __device__ int64_t operator()(int64_t a, int64_t b) const { return a + b; }
-};
-struct AddD {
-    __device__ double operator()(double a, double b) const { return a + b; }
-};
-struct MinD {
-    __device__ double operator()(double a, double b) const { return b < a ? b : a; }
-};
-// s[t] = op(s[t], s[t + h]) for h = RT/2 .. 1; every thread returns s[0]
-template <typename T, typename Op>
-__device__ __forceinline__ T tree(T* s, int t, T v, Op op) {
-    s[t] = v;
-    __syncthreads();
-    for (int h = RT / 2; h > 0; h >>= 1) {
-        if (t < h) s[t] = op(s[t], s[t + h]);
-        __syncthreads();
-    }
-    const T r = s[0];
-    __syncthreads();
-    return r;
-}
-
-// One workgroup per output row, in evx_episode_reduce's order: thread t adds its row's envs t,
-// t + RT, ... ascending onto 0.0 (envs of other layouts are skipped, not added as zero), then
-// the RT thread sums are added pairwise in LDS.
+// One workgroup per output row, in the order of evx_reduce.h.
 __global__ __launch_bounds__(RT) void health_reduce_kernel(evx_health h, const int32_t* __restrict__ layout_idx,
                                                            int n_layouts, evx_health_row* __restrict__ out) {
     __shared__ double shd[RT];
@@ -195,7 +169,7 @@ __global__ __launch_bounds__(RT) void health_reduce_kernel(evx_health h, const i
     int64_t n = 0, has = 0, alive = 0;
     double avg = 0.0, mins = 0.0, lo = INFINITY;
     for (int e = t; e < h.E; e += RT) {
-        if (row < n_layouts && (layout_idx ? layout_idx[e] : 0) != row) continue;
+        if (!in_row(layout_idx, n_layouts, row, e)) continue;
         n += h.w_n[e];
         has += h.w_has[e];
         alive += h.w_alive[e];
@@ -214,33 +188,23 @@ __global__ __launch_bounds__(RT) void health_reduce_kernel(evx_health h, const i
     if (t == 0) out[row] = o;
 }
 
-}  // namespace evxh
+}  // namespace evxhl
 
 namespace {
+using evxh::blocks;
 using evxh::fail;
+using evxh::failf;
 using evxh::hip_status;
 int check_h(const evx_health* h, const char* who) {
-    static thread_local char msg[128];
-    if (!h) {
-        snprintf(msg, sizeof(msg), "%s: NULL health descriptor", who);
-        return fail(-22, msg);
-    }
-    if (h->E < 1) {
-        snprintf(msg, sizeof(msg), "%s: E must be >= 1", who);
-        return fail(-22, msg);
-    }
+    if (!h) return failf(-22, "%s: NULL health descriptor", who);
+    if (h->E < 1) return failf(-22, "%s: E must be >= 1", who);
     if (!h->n_total || !h->w_n || !h->w_has || !h->w_alive || !h->w_avg || !h->w_min || !h->w_lo || !h->last_avg ||
-        !h->last_min || !h->last_alive) {
-        snprintf(msg, sizeof(msg), "%s: NULL health buffer", who);
-        return fail(-22, msg);
-    }
-    if (h->tab_slots < 0 || (h->tab_slots > 0 && (!h->tab_avg || !h->tab_min || !h->tab_alive))) {
-        snprintf(msg, sizeof(msg), "%s: health table slots without its buffers", who);
-        return fail(-22, msg);
-    }
+        !h->last_min || !h->last_alive)
+        return failf(-22, "%s: NULL health buffer", who);
+    if (h->tab_slots < 0 || (h->tab_slots > 0 && (!h->tab_avg || !h->tab_min || !h->tab_alive)))
+        return failf(-22, "%s: health table slots without its buffers", who);
     return 0;
 }
-unsigned blocks(int32_t E) { return (unsigned)((E + evxh::NT - 1) / evxh::NT); }
 }  // namespace
 
 extern "C" {
@@ -249,7 +213,8 @@ const char* evx_health_last_error(void) { return evxh::g_err; }
 
 int evx_health_init(const evx_health* h, void* stream) {
     if (int rc = check_h(h, "health_init")) return rc;
-    hipLaunchKernelGGL(evxh::health_clear_kernel, dim3(blocks(h->E)), dim3(evxh::NT), 0, (hipStream_t)stream, *h, 1);
+    hipLaunchKernelGGL(evxhl::health_clear_kernel, dim3(blocks(h->E, evxhl::NT)), dim3(evxhl::NT), 0,
+                       (hipStream_t)stream, *h, 1);
     return hip_status("health_init");
 }
 
@@ -259,7 +224,7 @@ int evx_health_update(const evx_health* h, const int32_t* pk, const double* heal
     if (!pk || !health || !done) return fail(-22, "health_update: NULL pk, health or done");
     if (P < 1 || P > EVX_HEALTH_MAX_P) return fail(-22, "health_update: P must be 1..16383");
     const size_t lds = (size_t)P * sizeof(double);  // the compacted healths
-    hipLaunchKernelGGL(evxh::health_update_kernel, dim3((unsigned)h->E), dim3(evxh::WAVE), lds, (hipStream_t)stream,
+    hipLaunchKernelGGL(evxhl::health_update_kernel, dim3((unsigned)h->E), dim3(evxhl::WAVE), lds, (hipStream_t)stream,
                        *h, (const uint32_t*)pk, health, (int)P, done, cap);
     return hip_status("health_update");
 }
@@ -267,18 +232,9 @@ int evx_health_update(const evx_health* h, const int32_t* pk, const double* heal
 int evx_health_reduce(const evx_health* h, const int32_t* layout_idx, int32_t n_layouts, evx_health_row* out,
                       int32_t clear, void* stream) {
     if (int rc = check_h(h, "health_reduce")) return rc;
-    if (!out) return fail(-22, "health_reduce: NULL output rows");
-    if (n_layouts < 1 || n_layouts > 65535) return fail(-22, "health_reduce: n_layouts must be 1..65535");
-    if (n_layouts > 1 && !layout_idx) return fail(-22, "health_reduce: several layouts need layout_idx");
-    const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(evxh::health_reduce_kernel, dim3((unsigned)n_layouts + 1), dim3(evxh::RT), 0, st, *h,
-                       layout_idx, n_layouts, out);
-    if (int rc = hip_status("health_reduce")) return rc;
-    if (clear) {  // after every row's workgroup has read the window (stream order)
-        hipLaunchKernelGGL(evxh::health_clear_kernel, dim3(blocks(h->E)), dim3(evxh::NT), 0, st, *h, 0);
-        return hip_status("health_reduce (clear)");
-    }
-    return 0;
+    if (int rc = evxr::check_rows("health_reduce", out, n_layouts, layout_idx)) return rc;
+    return evxr::reduce_rows("health_reduce", stream, clear, evxhl::health_reduce_kernel, evxhl::health_clear_kernel,
+                             evxhl::NT, *h, layout_idx, n_layouts, out);
 }
 
 }  // extern "C"

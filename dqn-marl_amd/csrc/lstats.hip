@@ -22,14 +22,15 @@
 
 #include "evacx.h"
 #include "evx_host.h"
+#include "evx_reduce.h"
 
 namespace evxl {
 
 constexpr int NT = 256;                      // rows per block; envs per block of the probe's kernels
-constexpr int RT = EVX_EPISODE_REDUCE_SPAN;  // the probe reduce's workgroup
 constexpr int MAXA = EVX_LSTATS_MAX_A;
 constexpr int NBK = EVX_LSTATS_TD_BUCKETS;
 constexpr int WF = EVX_LSTATS_WS_FIELDS;
+using evxr::RT, evxr::in_row, evxr::tree, evxr::AddI, evxr::AddD, evxr::MinD, evxr::MaxD;
 // the block's integer counters in LDS: rows_bad, n_done, n_greedy, act_hist[MAXA], td_hist[NBK]
 constexpr int C_BAD = 0, C_DONE = 1, C_GREEDY = 2, C_ACT = 3, C_TD = C_ACT + MAXA, NCNT = C_TD + NBK;
 
@@ -322,34 +323,7 @@ __global__ __launch_bounds__(NT) void vprobe_clear_kernel(evx_vprobe vp, int all
     }
 }
 
-struct AddI {
-    __device__ int64_t operator()(int64_t a, int64_t b) const { return a + b; }
-};
-struct AddD {
-    __device__ double operator()(double a, double b) const { return a + b; }
-};
-struct MinD {
-    __device__ double operator()(double a, double b) const { return b < a ? b : a; }
-};
-struct MaxD {
-    __device__ double operator()(double a, double b) const { return b > a ? b : a; }
-};
-// s[t] = op(s[t], s[t + h]) for h = RT/2 .. 1; every thread returns s[0]
-template <typename T, typename Op>
-__device__ __forceinline__ T tree(T* s, int t, T v, Op op) {
-    s[t] = v;
-    __syncthreads();
-    for (int h = RT / 2; h > 0; h >>= 1) {
-        if (t < h) s[t] = op(s[t], s[t + h]);
-        __syncthreads();
-    }
-    const T r = s[0];
-    __syncthreads();
-    return r;
-}
-
-// evx_episode_reduce's shape and order: one workgroup per output row, thread t adds the row's envs
-// t, t + RT, ... ascending onto 0.0 (other layouts' envs are skipped), then the pairwise tree.
+// One workgroup per output row, in the order of evx_reduce.h.
 __global__ __launch_bounds__(RT) void vprobe_reduce_kernel(evx_vprobe vp, const int32_t* __restrict__ layout_idx,
                                                            int n_layouts, evx_vprobe_row* __restrict__ out) {
     __shared__ double shd[RT];
@@ -358,7 +332,7 @@ __global__ __launch_bounds__(RT) void vprobe_reduce_kernel(evx_vprobe vp, const 
     int64_t n = 0, bad = 0, open = 0;
     double q = 0.0, g = 0.0, e1 = 0.0, e2 = 0.0, q2 = 0.0, g2 = 0.0, qg = 0.0, mn = INFINITY, mx = -INFINITY;
     for (int e = t; e < vp.E; e += RT) {
-        if (row < n_layouts && (layout_idx ? layout_idx[e] : 0) != row) continue;
+        if (!in_row(layout_idx, n_layouts, row, e)) continue;
         n += vp.w_n[e];
         bad += vp.w_bad[e];
         open += vp.open[e] ? 1 : 0;
@@ -392,60 +366,33 @@ __global__ __launch_bounds__(RT) void vprobe_reduce_kernel(evx_vprobe vp, const 
 }  // namespace evxl
 
 namespace {
+using evxh::blocks;
 using evxh::fail;
+using evxh::failf;
 using evxh::hip_status;
 
 int check_ls(const evx_lstats* ls, const char* who) {
-    static thread_local char msg[128];
-    if (!ls) {
-        snprintf(msg, sizeof(msg), "%s: NULL statistics descriptor", who);
-        return fail(-22, msg);
-    }
-    if (ls->nets < 1 || ls->nets > 64) {
-        snprintf(msg, sizeof(msg), "%s: nets must be 1..64", who);
-        return fail(-22, msg);
-    }
-    if (ls->A < 1 || ls->A > EVX_LSTATS_MAX_A) {
-        snprintf(msg, sizeof(msg), "%s: A must be 1..%d", who, EVX_LSTATS_MAX_A);
-        return fail(-22, msg);
-    }
+    if (!ls) return failf(-22, "%s: NULL statistics descriptor", who);
+    if (ls->nets < 1 || ls->nets > 64) return failf(-22, "%s: nets must be 1..64", who);
+    if (ls->A < 1 || ls->A > EVX_LSTATS_MAX_A) return failf(-22, "%s: A must be 1..%d", who, EVX_LSTATS_MAX_A);
     if (!ls->steps || !ls->steps_bad || !ls->rows || !ls->rows_bad || !ls->n_done || !ls->n_greedy ||
         !ls->n_clipped || !ls->act_hist || !ls->td_hist || !ls->s_q || !ls->s_qmax || !ls->s_y || !ls->s_d ||
         !ls->s_absd || !ls->s_d2 || !ls->s_rew || !ls->s_loss || !ls->s_norm || !ls->max_absd || !ls->max_q ||
-        !ls->min_q || !ls->max_loss || !ls->max_norm) {
-        snprintf(msg, sizeof(msg), "%s: NULL statistics buffer", who);
-        return fail(-22, msg);
-    }
+        !ls->min_q || !ls->max_loss || !ls->max_norm)
+        return failf(-22, "%s: NULL statistics buffer", who);
     return 0;
 }
 
 int check_vp(const evx_vprobe* vp, const char* who) {
-    static thread_local char msg[128];
-    if (!vp) {
-        snprintf(msg, sizeof(msg), "%s: NULL probe descriptor", who);
-        return fail(-22, msg);
-    }
-    if (vp->E < 1 || vp->R < 1 || vp->A < 1) {
-        snprintf(msg, sizeof(msg), "%s: E, R and A must be >= 1", who);
-        return fail(-22, msg);
-    }
-    if (vp->A > EVX_LSTATS_MAX_A) {
-        snprintf(msg, sizeof(msg), "%s: A must be <= %d", who, EVX_LSTATS_MAX_A);
-        return fail(-22, msg);
-    }
-    if ((int64_t)vp->E * vp->R > INT32_MAX) {
-        snprintf(msg, sizeof(msg), "%s: E * R beyond 2^31 - 1", who);
-        return fail(-22, msg);
-    }
+    if (!vp) return failf(-22, "%s: NULL probe descriptor", who);
+    if (vp->E < 1 || vp->R < 1 || vp->A < 1) return failf(-22, "%s: E, R and A must be >= 1", who);
+    if (vp->A > EVX_LSTATS_MAX_A) return failf(-22, "%s: A must be <= %d", who, EVX_LSTATS_MAX_A);
+    if ((int64_t)vp->E * vp->R > INT32_MAX) return failf(-22, "%s: E * R beyond 2^31 - 1", who);
     if (!vp->open || !vp->q0 || !vp->g || !vp->disc || !vp->len || !vp->w_n || !vp->w_bad || !vp->w_q || !vp->w_g ||
-        !vp->w_e || !vp->w_e2 || !vp->w_q2 || !vp->w_g2 || !vp->w_qg || !vp->w_emin || !vp->w_emax) {
-        snprintf(msg, sizeof(msg), "%s: NULL probe buffer", who);
-        return fail(-22, msg);
-    }
+        !vp->w_e || !vp->w_e2 || !vp->w_q2 || !vp->w_g2 || !vp->w_qg || !vp->w_emin || !vp->w_emax)
+        return failf(-22, "%s: NULL probe buffer", who);
     return 0;
 }
-
-unsigned blocks(int64_t n) { return (unsigned)((n + evxl::NT - 1) / evxl::NT); }
 }  // namespace
 
 extern "C" {
@@ -459,7 +406,7 @@ int64_t evx_lstats_ws_doubles(int32_t B, int32_t nets) {
 
 int evx_lstats_init(const evx_lstats* ls, void* stream) {
     if (int rc = check_ls(ls, "lstats_init")) return rc;
-    hipLaunchKernelGGL(evxl::lstats_clear_kernel, dim3(blocks((int64_t)ls->nets * EVX_LSTATS_TD_BUCKETS)),
+    hipLaunchKernelGGL(evxl::lstats_clear_kernel, dim3(blocks((int64_t)ls->nets * EVX_LSTATS_TD_BUCKETS, evxl::NT)),
                        dim3(evxl::NT), 0, (hipStream_t)stream, *ls);
     return hip_status("lstats_init");
 }
@@ -498,7 +445,8 @@ int evx_lstats_update(const evx_lstats* ls, const float* Q, const float* Qt, con
 
 int evx_vprobe_init(const evx_vprobe* vp, void* stream) {
     if (int rc = check_vp(vp, "vprobe_init")) return rc;
-    hipLaunchKernelGGL(evxl::vprobe_clear_kernel, dim3(blocks(vp->E)), dim3(evxl::NT), 0, (hipStream_t)stream, *vp, 1);
+    hipLaunchKernelGGL(evxl::vprobe_clear_kernel, dim3(blocks(vp->E, evxl::NT)), dim3(evxl::NT), 0,
+                       (hipStream_t)stream, *vp, 1);
     return hip_status("vprobe_init");
 }
 
@@ -507,33 +455,24 @@ int evx_vprobe_update(const evx_vprobe* vp, const float* Q, const int32_t* act, 
     if (int rc = check_vp(vp, "vprobe_update")) return rc;
     if (!Q || !act || !reward || !done) return fail(-22, "vprobe_update: NULL Q, act, reward or done");
     if (!isfinite(gamma) || gamma < 0.0 || gamma > 1.0) return fail(-22, "vprobe_update: gamma must be in [0, 1]");
-    hipLaunchKernelGGL(evxl::vprobe_update_kernel, dim3(blocks(vp->E)), dim3(evxl::NT), 0, (hipStream_t)stream, *vp, Q,
-                       act, reward, done, gamma);
+    hipLaunchKernelGGL(evxl::vprobe_update_kernel, dim3(blocks(vp->E, evxl::NT)), dim3(evxl::NT), 0,
+                       (hipStream_t)stream, *vp, Q, act, reward, done, gamma);
     return hip_status("vprobe_update");
 }
 
 int evx_vprobe_discard(const evx_vprobe* vp, const uint8_t* mask, void* stream) {
     if (int rc = check_vp(vp, "vprobe_discard")) return rc;
-    hipLaunchKernelGGL(evxl::vprobe_discard_kernel, dim3(blocks(vp->E)), dim3(evxl::NT), 0, (hipStream_t)stream, *vp,
-                       mask);
+    hipLaunchKernelGGL(evxl::vprobe_discard_kernel, dim3(blocks(vp->E, evxl::NT)), dim3(evxl::NT), 0,
+                       (hipStream_t)stream, *vp, mask);
     return hip_status("vprobe_discard");
 }
 
 int evx_vprobe_reduce(const evx_vprobe* vp, const int32_t* layout_idx, int32_t n_layouts, evx_vprobe_row* out,
                       int32_t clear, void* stream) {
     if (int rc = check_vp(vp, "vprobe_reduce")) return rc;
-    if (!out) return fail(-22, "vprobe_reduce: NULL output rows");
-    if (n_layouts < 1 || n_layouts > 65535) return fail(-22, "vprobe_reduce: n_layouts must be 1..65535");
-    if (n_layouts > 1 && !layout_idx) return fail(-22, "vprobe_reduce: several layouts need layout_idx");
-    const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(evxl::vprobe_reduce_kernel, dim3((unsigned)n_layouts + 1), dim3(evxl::RT), 0, st, *vp,
-                       layout_idx, n_layouts, out);
-    if (int rc = hip_status("vprobe_reduce")) return rc;
-    if (clear) {  // after every row's workgroup has read the window (stream order)
-        hipLaunchKernelGGL(evxl::vprobe_clear_kernel, dim3(blocks(vp->E)), dim3(evxl::NT), 0, st, *vp, 0);
-        return hip_status("vprobe_reduce (clear)");
-    }
-    return 0;
+    if (int rc = evxr::check_rows("vprobe_reduce", out, n_layouts, layout_idx)) return rc;
+    return evxr::reduce_rows("vprobe_reduce", stream, clear, evxl::vprobe_reduce_kernel, evxl::vprobe_clear_kernel,
+                             evxl::NT, *vp, layout_idx, n_layouts, out);
 }
 
 }  // extern "C"

@@ -194,7 +194,9 @@ __global__ __launch_bounds__(NT_FLAT) void spatial_init_kernel(evx_spatial sp) {
 }  // namespace evxs
 
 namespace {
+using evxh::blocks;
 using evxh::fail;
+using evxh::failf;
 using evxh::hip_status;
 
 const char* check_sizes(int32_t GX, int32_t GY, int32_t P, int32_t n_rows) {
@@ -230,7 +232,6 @@ evx_spatial_launch make_plan(int32_t GX, int32_t GY, int32_t P) {
 }
 
 int check_sp(const evx_spatial* sp, const char* who) {
-    static thread_local char msg[128];
     const char* what = nullptr;
     if (!sp)
         what = "NULL spatial descriptor";
@@ -243,11 +244,8 @@ int check_sp(const evx_spatial* sp, const char* who) {
     else if (!sp->prev || !sp->n_total || !sp->arrive || !sp->stall || !sp->evac || !sp->died || !sp->robot ||
              !sp->steps || !sp->bad)
         what = "NULL spatial buffer";
-    if (!what) return 0;
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(-22, msg);
+    return what ? failf(-22, "%s: %s", who, what) : 0;
 }
-unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 }  // namespace
 
 extern "C" {
@@ -255,12 +253,8 @@ extern "C" {
 const char* evx_spatial_last_error(void) { return evxh::g_err; }
 
 int evx_spatial_plan(int32_t GX, int32_t GY, int32_t P, int32_t n_rows, evx_spatial_launch* plan) {
-    static thread_local char msg[128];
     if (!plan) return fail(-22, "spatial_plan: NULL plan");
-    if (const char* s = check_sizes(GX, GY, P, n_rows)) {
-        snprintf(msg, sizeof(msg), "spatial_plan: %s", s);
-        return fail(-22, msg);
-    }
+    if (const char* s = check_sizes(GX, GY, P, n_rows)) return failf(-22, "spatial_plan: %s", s);
     *plan = make_plan(GX, GY, P);
     return 0;
 }

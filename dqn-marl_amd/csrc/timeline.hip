@@ -178,10 +178,11 @@ __global__ __launch_bounds__(NT) void timeline_init_kernel(evx_timeline tl) {
 }  // namespace evxt
 
 namespace {
+using evxh::blocks;
 using evxh::fail;
+using evxh::failf;
 using evxh::hip_status;
 int check_tl(const evx_timeline* tl, const char* who) {
-    static thread_local char msg[128];
     const char* what = nullptr;
     if (!tl)
         what = "NULL timeline descriptor";
@@ -196,11 +197,8 @@ int check_tl(const evx_timeline* tl, const char* who) {
         what = "n_trk must be >= 0";
     else if (tl->n_trk > 0 && (!tl->trk_env || !tl->trk_person || !tl->trk_pk || !tl->trk_health || !tl->trk_len))
         what = "tracked persons without their trace arrays";
-    if (!what) return 0;
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(-22, msg);
+    return what ? failf(-22, "%s: %s", who, what) : 0;
 }
-unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 }  // namespace
 
 extern "C" {

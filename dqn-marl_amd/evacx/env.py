@@ -265,6 +265,12 @@ class LayoutSet:
         return len(self.layouts)
 
 
+def n_layout_rows(layout) -> int:
+    """The layouts of ``layout``, a LayoutSet's (or anything with ``layouts``), else 1: the
+    per-layout rows of the accumulators over its envs."""
+    return len(layout.layouts) if hasattr(layout, "layouts") else 1
+
+
 def _perm_ws(E: int, device) -> torch.Tensor:
     n = int(_lib.lib().evx_perm_ws_bytes(E))
     return torch.zeros(max(n, 1), dtype=torch.uint8, device=device)

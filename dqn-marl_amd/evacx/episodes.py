@@ -15,6 +15,7 @@ from typing import Optional
 
 import torch
 
+from ._envstats import EnvSlice, as_mask, check_rows, host_rows, need
 from ._lib import EPISODE_REDUCE_SPAN as REDUCE_SPAN, EPISODE_ROW_WORDS as ROW_WORDS  # noqa: F401
 from ._lib import check, evx_episodes, lib
 from .env import _ptr, _stream
@@ -25,15 +26,6 @@ _I32 = ("len", "last_len", "last_evac", "last_dead")
 _TAB = ("tab_ret", "tab_len", "tab_evac", "tab_dead")
 # the loader's earlier name here, kept for callers written against them
 elib = lib
-
-
-def _need(name, t, n, dtype, device):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name}: a tensor is needed, not {type(t).__name__}")
-    if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
-        raise ValueError(f"{name}: needs {n} contiguous {dtype} elements, got {t.numel()} of {t.dtype}")
-    if device is not None and t.device != device:
-        raise ValueError(f"{name}: on {t.device}, the statistics are on {device}")
 
 
 def _row_dict(irow, frow, P: int) -> dict:
@@ -50,38 +42,24 @@ def _row_dict(irow, frow, P: int) -> dict:
     return d
 
 
-class _Slice:
-    """``n`` envs of an EpisodeStats from env ``lo`` (a VecEnv.split part's own envs): the same
-    buffers through offset pointers."""
-
-    def __init__(self, owner: "EpisodeStats", lo: int, n: int):
-        self.owner, self.lo, self.E = owner, lo, n
-        K = owner.record
-        self.c = evx_episodes(E=n, tab_slots=K)
-        for name in _I64 + _F64 + _I32:
-            setattr(self.c, name, _ptr(getattr(owner, name)[lo:lo + n]))
-        if K:
-            for name in _TAB:
-                setattr(self.c, name, _ptr(getattr(owner, name)[lo:lo + n]))
+class _Slice(EnvSlice):
+    """``n`` envs of an EpisodeStats from env ``lo`` (a VecEnv.split part's own envs)."""
+    _desc, _per_env, _tables, _fixed = evx_episodes, _I64 + _F64 + _I32, _TAB, {"tab_slots": "record"}
 
     def update(self, reward: torch.Tensor, done: torch.Tensor, counts: torch.Tensor):
         """Fold one step's outputs of these envs (VecEnv.reward / done / counts), one launch on
         the current stream."""
         dev = self.owner.device
-        _need("reward", reward, self.E, torch.float64, dev)
-        _need("done", done, self.E, torch.uint8, dev)
-        _need("counts", counts, 2 * self.E, torch.int32, dev)
+        need("reward", reward, self.E, torch.float64, dev)
+        need("done", done, self.E, torch.uint8, dev)
+        need("counts", counts, 2 * self.E, torch.int32, dev)
         check(lib().evx_episode_update(C.byref(self.c), reward.data_ptr(), done.data_ptr(), counts.data_ptr(),
                                        self.owner.cap, _stream()), "episode_update")
 
     def discard(self, mask: Optional[torch.Tensor] = None):
         """Drop the episode in progress of the masked envs (None: all): for envs reset from
         outside the step. One launch on the current stream."""
-        m = mask
-        if m is not None:
-            if isinstance(m, torch.Tensor) and m.dtype == torch.bool:
-                m = m.to(torch.uint8)
-            _need("mask", m, self.E, torch.uint8, self.owner.device)
+        m = as_mask(mask, self.E, self.owner.device)
         check(lib().evx_episode_discard(C.byref(self.c), _ptr(m), _stream()), "episode_discard")
 
 
@@ -97,6 +75,7 @@ class EpisodeStats(_Slice):
     ``w_len``, ``w_evac``, ``w_dead``, ``w_ret``, ``w_ret2``, ``w_min``, ``w_max``; the last
     finished episode ``last_return`` (= ``last_ret``), ``last_len``, ``last_evac``,
     ``last_dead``; the lifetime count ``n_total``."""
+    _part = _Slice
 
     def __init__(self, E: int, device, P: int, layout_idx: Optional[torch.Tensor] = None, n_layouts: int = 1,
                  cap: int = 0, record: int = 0):
@@ -105,15 +84,7 @@ class EpisodeStats(_Slice):
             raise ValueError(f"EpisodeStats: E and P must be >= 1, not {E}, {P}")
         if cap < 0 or record < 0:
             raise ValueError("EpisodeStats: cap and record must be >= 0")
-        if not 1 <= n_layouts <= 65535:
-            raise ValueError(f"EpisodeStats: n_layouts must be 1..65535, not {n_layouts}")
-        if n_layouts > 1 and layout_idx is None:
-            raise ValueError("EpisodeStats: several layouts need layout_idx")
-        device = torch.device(device)
-        if layout_idx is not None:
-            _need("layout_idx", layout_idx, E, torch.int32, None)
-            if layout_idx.device.type != device.type:
-                raise ValueError(f"layout_idx: on {layout_idx.device}, the statistics are on {device}")
+        device = check_rows("EpisodeStats", E, n_layouts, layout_idx, device)
         self.P, self.n_layouts, self.cap, self.record, self.device = P, n_layouts, cap, record, device
         self.layout_idx = layout_idx
         for name in _I64:
@@ -132,13 +103,6 @@ class EpisodeStats(_Slice):
         super().__init__(self, 0, E)
         check(lib().evx_episode_init(C.byref(self.c), _stream()), "episode_init")
 
-    def view(self, lo: int, n: int) -> _Slice:
-        """The slice object of envs [lo, lo + n): its update / discard touch only those."""
-        lo, n = int(lo), int(n)
-        if lo < 0 or n < 1 or lo + n > self.E:
-            raise ValueError(f"view: envs [{lo}, {lo + n}) are not within 0..{self.E}")
-        return _Slice(self, lo, n)
-
     def summary(self, clear: bool = True) -> dict:
         """Reduce the window over envs (one launch, plus one that empties the window when
         ``clear``), copy the rows to the host (this waits for the current stream) and return
@@ -146,9 +110,7 @@ class EpisodeStats(_Slice):
         in the window the means and rates are None."""
         check(lib().evx_episode_reduce(C.byref(self.c), _ptr(self.layout_idx), self.n_layouts, self.cap,
                                        self.rows.data_ptr(), int(bool(clear)), _stream()), "episode_reduce")
-        host = self.rows.cpu()
-        irows = host.view(self.n_layouts + 1, ROW_WORDS).tolist()
-        frows = host.view(torch.float64).view(self.n_layouts + 1, ROW_WORDS).tolist()
+        irows, frows = host_rows(self.rows, self.n_layouts + 1, ROW_WORDS)
         out = _row_dict(irows[-1], frows[-1], self.P)
         out["per_layout"] = [_row_dict(irows[l], frows[l], self.P) for l in range(self.n_layouts)]
         return out

@@ -22,7 +22,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from .env import OBS_WORDS, VecEnv, _stream
+from .env import OBS_WORDS, VecEnv, _stream, n_layout_rows
 from .episodes import EpisodeStats
 
 N_ACTIONS = 5
@@ -167,7 +167,7 @@ def evaluate(layout, E: int, episodes_per_env: int, policy, learner=None, seed_b
     env = VecEnv(layout, E, layout_of=layout_of)
     env.seed([seed_base + i for i in range(E)])
     env.reset()
-    n_layouts = len(layout.layouts) if hasattr(layout, "layouts") else 1
+    n_layouts = n_layout_rows(layout)
     stats = EpisodeStats(E, layout.device, layout.P, layout_idx=env.layout_idx, n_layouts=n_layouts, cap=K, record=K)
     health = None
     if metrics:

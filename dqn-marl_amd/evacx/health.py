@@ -15,10 +15,10 @@ from typing import Optional
 
 import torch
 
+from ._envstats import EnvSlice, check_rows, host_rows, need
 from ._lib import HEALTH_MAX_P as MAX_P, HEALTH_ROW_WORDS as ROW_WORDS
 from ._lib import check, evx_health, lib
 from .env import _ptr, _stream
-from .episodes import _need
 
 _I64 = ("n_total", "w_n", "w_has", "w_alive")
 _F64 = ("w_avg", "w_min", "w_lo", "last_avg", "last_min")
@@ -39,18 +39,9 @@ def _row_dict(irow, frow) -> dict:
     return d
 
 
-class _Slice:
-    """``n`` envs of a HealthStats from env ``lo``: the same buffers through offset pointers."""
-
-    def __init__(self, owner: "HealthStats", lo: int, n: int):
-        self.owner, self.lo, self.E = owner, lo, n
-        K = owner.record
-        self.c = evx_health(E=n, tab_slots=K)
-        for name in _I64 + _F64 + _I32:
-            setattr(self.c, name, _ptr(getattr(owner, name)[lo:lo + n]))
-        if K:
-            for name in _TAB:
-                setattr(self.c, name, _ptr(getattr(owner, name)[lo:lo + n]))
+class _Slice(EnvSlice):
+    """``n`` envs of a HealthStats from env ``lo``."""
+    _desc, _per_env, _tables, _fixed = evx_health, _I64 + _F64 + _I32, _TAB, {"tab_slots": "record"}
 
     def update(self, env_or_tensors, done: torch.Tensor):
         """Fold the finished episodes of these envs: ``env_or_tensors`` is a VecEnv (its ``pk`` and
@@ -61,9 +52,9 @@ class _Slice:
         else:
             pk, health = env_or_tensors.pk, env_or_tensors.health
         dev, P = self.owner.device, self.owner.P
-        _need("pk", pk, self.E * P, torch.int32, dev)
-        _need("health", health, self.E * P, torch.float64, dev)
-        _need("done", done, self.E, torch.uint8, dev)
+        need("pk", pk, self.E * P, torch.int32, dev)
+        need("health", health, self.E * P, torch.float64, dev)
+        need("done", done, self.E, torch.uint8, dev)
         check(lib().evx_health_update(C.byref(self.c), pk.data_ptr(), health.data_ptr(), P, done.data_ptr(),
                                       self.owner.cap, _stream()), "health_update")
 
@@ -75,6 +66,7 @@ class HealthStats(_Slice):
     ``w_alive``, ``w_avg``, ``w_min`` (sums), ``w_lo`` (smallest min_health); the last finished
     episode ``last_avg``, ``last_min``, ``last_alive``; the lifetime count ``n_total``; with
     record = K the table ``tab_avg``, ``tab_min``, ``tab_alive`` [E, K]."""
+    _part = _Slice
 
     def __init__(self, E: int, device, P: int, layout_idx: Optional[torch.Tensor] = None, n_layouts: int = 1,
                  cap: int = 0, record: int = 0):
@@ -83,15 +75,7 @@ class HealthStats(_Slice):
             raise ValueError(f"HealthStats: E must be >= 1 and P 1..{MAX_P}, not {E}, {P}")
         if cap < 0 or record < 0:
             raise ValueError("HealthStats: cap and record must be >= 0")
-        if not 1 <= n_layouts <= 65535:
-            raise ValueError(f"HealthStats: n_layouts must be 1..65535, not {n_layouts}")
-        if n_layouts > 1 and layout_idx is None:
-            raise ValueError("HealthStats: several layouts need layout_idx")
-        device = torch.device(device)
-        if layout_idx is not None:
-            _need("layout_idx", layout_idx, E, torch.int32, None)
-            if layout_idx.device.type != device.type:
-                raise ValueError(f"layout_idx: on {layout_idx.device}, the statistics are on {device}")
+        device = check_rows("HealthStats", E, n_layouts, layout_idx, device)
         self.P, self.n_layouts, self.cap, self.record = P, n_layouts, cap, record
         self.layout_idx = layout_idx
         for name in _I64:
@@ -109,13 +93,6 @@ class HealthStats(_Slice):
         super().__init__(self, 0, E)
         check(lib().evx_health_init(C.byref(self.c), _stream()), "health_init")
 
-    def view(self, lo: int, n: int) -> _Slice:
-        """The slice object of envs [lo, lo + n): its update touches only those."""
-        lo, n = int(lo), int(n)
-        if lo < 0 or n < 1 or lo + n > self.E:
-            raise ValueError(f"view: envs [{lo}, {lo + n}) are not within 0..{self.E}")
-        return _Slice(self, lo, n)
-
     def summary(self, clear: bool = True) -> dict:
         """Reduce the window over envs (one launch, plus one that empties the window when
         ``clear``), copy the rows to the host (this waits for the current stream) and return the
@@ -124,9 +101,7 @@ class HealthStats(_Slice):
         smallest), ``alive_mean`` (None with no episode), the raw sums, and ``per_layout``."""
         check(lib().evx_health_reduce(C.byref(self.c), _ptr(self.layout_idx), self.n_layouts, self.rows.data_ptr(),
                                       int(bool(clear)), _stream()), "health_reduce")
-        host = self.rows.cpu()
-        irows = host.view(self.n_layouts + 1, ROW_WORDS).tolist()
-        frows = host.view(torch.float64).view(self.n_layouts + 1, ROW_WORDS).tolist()
+        irows, frows = host_rows(self.rows, self.n_layouts + 1, ROW_WORDS)
         out = _row_dict(irows[-1], frows[-1])
         out["per_layout"] = [_row_dict(irows[l], frows[l]) for l in range(self.n_layouts)]
         return out

@@ -20,11 +20,11 @@ from typing import Optional
 
 import torch
 
+from ._envstats import EnvSlice, as_mask, check_rows, host_rows, need
 from ._lib import EPISODE_REDUCE_SPAN as REDUCE_SPAN  # noqa: F401
 from ._lib import LSTATS_MAX_A as MAX_A, LSTATS_TD_BUCKETS as TD_BUCKETS, VPROBE_ROW_WORDS as ROW_WORDS
 from ._lib import check, evx_lstats, evx_td_opts, evx_vprobe, lib
 from .env import _ptr, _stream
-from .episodes import _need
 
 _LS_I64 = ("steps", "steps_bad", "rows", "rows_bad", "n_done", "n_greedy", "n_clipped")
 _LS_SUM = ("s_q", "s_qmax", "s_y", "s_d", "s_absd", "s_d2", "s_rew", "s_loss", "s_norm")
@@ -125,16 +125,16 @@ class LearnStats:
         if B < 1:
             raise ValueError(f"LearnStats.update: B must be >= 1, not {B}")
         n, dev = self.nets * B, self.device
-        _need("Q", Q, n * self.A, torch.float32, dev)
-        _need("Qt", Qt, n * self.A, torch.float32, dev)
-        _need("a", a, n, torch.int32, dev)
-        _need("r", r, n, torch.float32, dev)
-        _need("done", done, n, torch.uint8, dev)
+        need("Q", Q, n * self.A, torch.float32, dev)
+        need("Qt", Qt, n * self.A, torch.float32, dev)
+        need("a", a, n, torch.int32, dev)
+        need("r", r, n, torch.float32, dev)
+        need("done", done, n, torch.uint8, dev)
         for name, t, per, dt in (("sel", sel, n, torch.int32), ("gamma_row", gamma_row, n, torch.float32),
                                  ("loss", loss, self.nets, torch.float32), ("norm", norm, self.nets, torch.float32),
                                  ("d_out", d_out, n, torch.float32)):
             if t is not None:
-                _need(name, t, per, dt, dev)
+                need(name, t, per, dt, dev)
         if not math.isfinite(gamma):
             raise ValueError(f"LearnStats.update: gamma must be finite, not {gamma}")
         if self._ws is None or self._ws_B < B:  # the block partials' workspace, grown with B
@@ -202,35 +202,26 @@ def probe_stats(n: int, bad: int, open_: int, q: float, g: float, e: float, e2: 
     return d
 
 
-class _ProbeSlice:
-    """``n`` envs of a ValueProbe from env ``lo``: the same buffers through offset pointers."""
-
-    def __init__(self, owner: "ValueProbe", lo: int, n: int):
-        self.owner, self.lo, self.E = owner, lo, n
-        self.c = evx_vprobe(E=n, R=owner.R, A=owner.A)
-        for name in ("open", "len") + _VP_F64 + _VP_I64:
-            setattr(self.c, name, _ptr(getattr(owner, name)[lo:lo + n]))
+class _ProbeSlice(EnvSlice):
+    """``n`` envs of a ValueProbe from env ``lo``."""
+    _desc, _per_env, _fixed = evx_vprobe, ("open", "len") + _VP_F64 + _VP_I64, {"R": "R", "A": "A"}
 
     def update(self, Q: torch.Tensor, act: torch.Tensor, reward: torch.Tensor, done: torch.Tensor):
         """One step of these envs, one launch on the current stream: Q (float32 [E * R, A]) and act
         (int32 [E * R]) of the act that chose the step's actions, the step's reward (float64 [E])
         and done (uint8 [E])."""
         o = self.owner
-        _need("Q", Q, self.E * o.R * o.A, torch.float32, o.device)
-        _need("act", act, self.E * o.R, torch.int32, o.device)
-        _need("reward", reward, self.E, torch.float64, o.device)
-        _need("done", done, self.E, torch.uint8, o.device)
+        need("Q", Q, self.E * o.R * o.A, torch.float32, o.device)
+        need("act", act, self.E * o.R, torch.int32, o.device)
+        need("reward", reward, self.E, torch.float64, o.device)
+        need("done", done, self.E, torch.uint8, o.device)
         check(lib().evx_vprobe_update(C.byref(self.c), Q.data_ptr(), act.data_ptr(), reward.data_ptr(),
                                       done.data_ptr(), o.gamma, _stream()), "vprobe_update")
 
     def discard(self, mask: Optional[torch.Tensor] = None):
         """Close the probes of the masked envs (None: all) without folding them: for envs reset
         from outside the step. One launch on the current stream."""
-        m = mask
-        if m is not None:
-            if isinstance(m, torch.Tensor) and m.dtype == torch.bool:
-                m = m.to(torch.uint8)
-            _need("mask", m, self.E, torch.uint8, self.owner.device)
+        m = as_mask(mask, self.E, self.owner.device)
         check(lib().evx_vprobe_discard(C.byref(self.c), _ptr(m), _stream()), "vprobe_discard")
 
 
@@ -239,6 +230,7 @@ class ValueProbe(_ProbeSlice):
     ``g``, ``disc``, ``len``) and the window (``w_n``, ``w_bad``, ``w_q``, ``w_g``, ``w_e``,
     ``w_e2``, ``w_q2``, ``w_g2``, ``w_qg``, ``w_emin``, ``w_emax``), public device tensors [E].
     gamma: the discount of the return (the learner's). layout_idx / n_layouts: as EpisodeStats."""
+    _part = _ProbeSlice
 
     def __init__(self, E: int, R: int, device, gamma: float, layout_idx: Optional[torch.Tensor] = None,
                  n_layouts: int = 1, A: int = 5):
@@ -250,15 +242,7 @@ class ValueProbe(_ProbeSlice):
         gamma = float(gamma)
         if not (math.isfinite(gamma) and 0.0 <= gamma <= 1.0):
             raise ValueError(f"ValueProbe: gamma must be in [0, 1], not {gamma}")
-        if not 1 <= n_layouts <= 65535:
-            raise ValueError(f"ValueProbe: n_layouts must be 1..65535, not {n_layouts}")
-        if n_layouts > 1 and layout_idx is None:
-            raise ValueError("ValueProbe: several layouts need layout_idx")
-        device = torch.device(device)
-        if layout_idx is not None:
-            _need("layout_idx", layout_idx, E, torch.int32, None)
-            if layout_idx.device.type != device.type:
-                raise ValueError(f"layout_idx: on {layout_idx.device}, the probe is on {device}")
+        device = check_rows("ValueProbe", E, n_layouts, layout_idx, device, where="the probe is")
         self.R, self.A, self.gamma, self.n_layouts, self.layout_idx = R, A, gamma, n_layouts, layout_idx
         self.open = torch.zeros(E, dtype=torch.uint8, device=device)
         self.len = torch.zeros(E, dtype=torch.int32, device=device)
@@ -270,13 +254,6 @@ class ValueProbe(_ProbeSlice):
         self.rows = torch.zeros((n_layouts + 1) * ROW_WORDS, dtype=torch.int64, device=device)
         super().__init__(self, 0, E)
         check(lib().evx_vprobe_init(C.byref(self.c), _stream()), "vprobe_init")
-
-    def view(self, lo: int, n: int) -> _ProbeSlice:
-        """The slice object of envs [lo, lo + n): its update / discard touch only those."""
-        lo, n = int(lo), int(n)
-        if lo < 0 or n < 1 or lo + n > self.E:
-            raise ValueError(f"view: envs [{lo}, {lo + n}) are not within 0..{self.E}")
-        return _ProbeSlice(self, lo, n)
 
     def reduce(self, clear: bool = False) -> torch.Tensor:
         """evx_vprobe_reduce into ``rows`` (int64 words, [n_layouts + 1, 12]: probes, bad, open, then
@@ -290,8 +267,7 @@ class ValueProbe(_ProbeSlice):
         window when ``clear``; the probes in progress stay), copy the rows back (waits for the current
         stream) and return the "all" row as probe_stats' dict, with ``per_layout`` a list of the
         same."""
-        host = self.reduce(clear)
-        irows, frows = host.tolist(), host.view(torch.float64).tolist()
+        irows, frows = host_rows(self.reduce(clear), self.n_layouts + 1, ROW_WORDS)
         rows = [probe_stats(*irows[k][:3], *frows[k][3:]) for k in range(self.n_layouts + 1)]
         out = rows[-1]
         out["per_layout"] = rows[:-1]

@@ -18,10 +18,10 @@ from typing import Optional
 import numpy as np
 import torch
 
+from ._envstats import check_rows, need
 from ._lib import HEALTH_MAX_P as MAX_P
 from ._lib import SPATIAL, SPATIAL_MAX_GRID, check, evx_spatial, evx_spatial_launch, lib
 from .env import _ptr, _stream
-from .episodes import _need
 
 MAP_FIELDS = ("arrive", "stall", "evac", "died", "robot")
 N_HOTSPOTS = 10
@@ -101,15 +101,7 @@ class SpatialMaps:
             raise ValueError(f"SpatialMaps: GX and GY must be 1..{SPATIAL_MAX_GRID}, not {GX}, {GY}")
         if cap < 0:
             raise ValueError("SpatialMaps: cap must be >= 0")
-        if not 1 <= n_layouts <= 65535:
-            raise ValueError(f"SpatialMaps: n_layouts must be 1..65535, not {n_layouts}")
-        if n_layouts > 1 and layout_idx is None:
-            raise ValueError("SpatialMaps: several layouts need layout_idx")
-        device = torch.device(device)
-        if layout_idx is not None:
-            _need("layout_idx", layout_idx, E, torch.int32, None)
-            if layout_idx.device.type != device.type:
-                raise ValueError(f"layout_idx: on {layout_idx.device}, the maps are on {device}")
+        device = check_rows("SpatialMaps", E, n_layouts, layout_idx, device, where="the maps are")
         self.E, self.P, self.R, self.GX, self.GY, self.n_layouts, self.cap = E, P, R, GX, GY, n_layouts, cap
         self.layout_idx = layout_idx
         i64 = dict(dtype=torch.int64, device=device)
@@ -130,9 +122,9 @@ class SpatialMaps:
             pk, robots = env_or_tensors
         else:
             pk, robots = env_or_tensors.pk, env_or_tensors.robots
-        _need("pk", pk, self.E * self.P, torch.int32, self.device)
+        need("pk", pk, self.E * self.P, torch.int32, self.device)
         if self.R:
-            _need("robots", robots, self.E * self.R, torch.int32, self.device)
+            need("robots", robots, self.E * self.R, torch.int32, self.device)
         else:
             robots = None
         return pk, robots
@@ -142,9 +134,9 @@ class SpatialMaps:
         first reset and after every masked reset. ``env`` is a VecEnv, pk itself (int32 [E, P]) or a
         pair that starts with it. One launch on the current stream."""
         pk = env if isinstance(env, torch.Tensor) else env[0] if isinstance(env, (tuple, list)) else env.pk
-        _need("pk", pk, self.E * self.P, torch.int32, self.device)
+        need("pk", pk, self.E * self.P, torch.int32, self.device)
         if mask is not None:
-            _need("mask", mask, self.E, torch.uint8, self.device)
+            need("mask", mask, self.E, torch.uint8, self.device)
         check(lib().evx_spatial_sync(C.byref(self.c), pk.data_ptr(), _ptr(mask), _stream()), "spatial_sync")
 
     def update(self, env, done: torch.Tensor):
@@ -153,7 +145,7 @@ class SpatialMaps:
         any reset; ``done`` the step's output. One launch on the current stream, two on the banded
         route (``plan()``)."""
         pk, robots = self._state(env)
-        _need("done", done, self.E, torch.uint8, self.device)
+        need("done", done, self.E, torch.uint8, self.device)
         check(lib().evx_spatial_update(C.byref(self.c), pk.data_ptr(), _ptr(robots), done.data_ptr(),
                                        _ptr(self.layout_idx), self.cap, _stream()), "spatial_update")
 

@@ -18,10 +18,10 @@ from typing import Optional
 import numpy as np
 import torch
 
+from ._envstats import check_rows, need
 from ._lib import HEALTH_MAX_P as MAX_P
 from ._lib import check, evx_timeline, lib
 from .env import _ptr, _stream
-from .episodes import _need
 
 TIME_PER_STEP = 0.5   # envs/evacuation_env.py:27
 Q_ONE = float(1 << 20)  # health_q's unit is 2^-20
@@ -110,19 +110,11 @@ class Timeline:
             raise ValueError(f"Timeline: E and T must be >= 1 and P 1..{MAX_P}, not {E}, {T}, {P}")
         if cap < 0:
             raise ValueError("Timeline: cap must be >= 0")
-        if not 1 <= n_layouts <= 65535:
-            raise ValueError(f"Timeline: n_layouts must be 1..65535, not {n_layouts}")
-        if n_layouts > 1 and layout_idx is None:
-            raise ValueError("Timeline: several layouts need layout_idx")
         if E * max(cap, 1) * P >= MAX_PERSON_STEPS:
             raise ValueError(f"Timeline: E * cap * P = {E * max(cap, 1) * P} is not below 2^36, a slot's health "
                              "sum could overflow")
         env_ids, person_ids = self._track_ids(track, E, P)
-        device = torch.device(device)
-        if layout_idx is not None:
-            _need("layout_idx", layout_idx, E, torch.int32, None)
-            if layout_idx.device.type != device.type:
-                raise ValueError(f"layout_idx: on {layout_idx.device}, the timeline is on {device}")
+        device = check_rows("Timeline", E, n_layouts, layout_idx, device, where="the timeline is")
         self.E, self.P, self.T, self.n_layouts, self.cap = E, P, T, n_layouts, cap
         self.layout_idx, self.n_trk = layout_idx, len(env_ids)
         i32, i64 = dict(dtype=torch.int32, device=device), dict(dtype=torch.int64, device=device)
@@ -170,8 +162,8 @@ class Timeline:
             pk, health = env_or_tensors
         else:
             pk, health = env_or_tensors.pk, env_or_tensors.health
-        _need("pk", pk, self.E * self.P, torch.int32, self.device)
-        _need("health", health, self.E * self.P, torch.float64, self.device)
+        need("pk", pk, self.E * self.P, torch.int32, self.device)
+        need("health", health, self.E * self.P, torch.float64, self.device)
         return pk, health
 
     def update(self, env, done: torch.Tensor, counts: torch.Tensor):
@@ -181,8 +173,8 @@ class Timeline:
         tracked persons); ``done`` / ``counts`` the step's outputs. One launch on the current
         stream, and one before it with tracked persons."""
         pk, health = (None, None) if env is None else self._state(env)
-        _need("done", done, self.E, torch.uint8, self.device)
-        _need("counts", counts, 2 * self.E, torch.int32, self.device)
+        need("done", done, self.E, torch.uint8, self.device)
+        need("counts", counts, 2 * self.E, torch.int32, self.device)
         check(lib().evx_timeline_update(C.byref(self.c), counts.data_ptr(), done.data_ptr(), _ptr(self.layout_idx),
                                         _ptr(pk), _ptr(health), self.P, self.cap, _stream()), "timeline_update")
 

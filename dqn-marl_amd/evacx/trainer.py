@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from ._lib import NSTEP_MAX, OBS_WORDS, check, evx_replay, lib
-from .env import DeviceLayout, VecEnv, _ptr, _stream
+from .env import DeviceLayout, VecEnv, _ptr, _stream, n_layout_rows
 from .qmlp import act_ws_ints
 from .qnet import DROPOUT_P, Learner, validate_td_options
 
@@ -293,19 +293,17 @@ class VecTrainer:
         # episode statistics (the reference's per-episode log, runners/train_dqn.py:129-161), or None
         self.episodes = None
         if episode_stats:
-            from .env import LayoutSet
             from .episodes import EpisodeStats
             self.episodes = EpisodeStats(E, self.device, layout.P, layout_idx=self.env.layout_idx,
-                                         n_layouts=len(layout) if isinstance(layout, LayoutSet) else 1)
+                                         n_layouts=n_layout_rows(layout))
             for grp in self.groups:
                 grp.ep = self.episodes.view(grp.g * grp.env.E, grp.env.E) if len(parts) > 1 else self.episodes
         # the value probe (evacx.lstats.ValueProbe) and the act's Q rows it reads, or None
         self.probe = self.act_q = None
         if value_probe:
-            from .env import LayoutSet
             from .lstats import ValueProbe
             self.probe = ValueProbe(E, self.R, self.device, gamma, layout_idx=self.env.layout_idx,
-                                    n_layouts=len(layout) if isinstance(layout, LayoutSet) else 1)
+                                    n_layouts=n_layout_rows(layout))
             self.act_q = torch.zeros(E * self.R * 5, dtype=torch.float32, device=self.device)
         for grp in self.groups:
             if self.probe is not None:

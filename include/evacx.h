@@ -923,7 +923,8 @@ int evx_episode_discard(const evx_episodes *ep, const uint8_t *mask, void *strea
  * other layouts are skipped), then the thread sums are added pairwise, s[t] = s[t] + s[t + h] for
  * h = SPAN/2, SPAN/4, ..., 1; the row's sum is s[0]. clear != 0: the per-env window arrays are
  * emptied by a second launch of the same call; the episode in progress, the last-episode slots,
- * the table and the lifetime count stay. Any E >= 1. */
+ * the table and the lifetime count stay. Any E >= 1. (The order is implemented once, in
+ * csrc/evx_reduce.h, for this reduce, evx_health_reduce and evx_vprobe_reduce.) */
 int evx_episode_reduce(const evx_episodes *ep, const int32_t *layout_idx, int32_t n_layouts, int64_t cap,
                        evx_episode_row *out, int32_t clear, void *stream);
 const char *evx_episode_last_error(void);

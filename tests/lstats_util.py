@@ -4,7 +4,9 @@ probe's float64 recurrence and the reduce's strided-then-pairwise order. tests/t
 pins these on hand-made cases; tests/test_lstats_gpu.py compares the kernels with them bit for bit."""
 import numpy as np
 
-MAX_A, TD_BUCKETS, BLOCK, SPAN = 8, 48, 256, 1024
+from span_reduce_util import SPAN, span_sum  # noqa: F401  (the reduce's order, shared with the other families' tests)
+
+MAX_A, TD_BUCKETS, BLOCK = 8, 48, 256
 I64 = ("steps", "steps_bad", "rows", "rows_bad", "n_done", "n_greedy", "n_clipped")
 SUMS = ("s_q", "s_qmax", "s_y", "s_d", "s_absd", "s_d2", "s_rew", "s_loss", "s_norm")
 EXT = ("max_absd", "max_q", "min_q", "max_loss", "max_norm")
@@ -199,22 +201,6 @@ def probe_step_vec(st, Q, act, reward, done, gamma, R, lo=0, n=None):
         st["w_emin"][sl] = np.where(f & (err < st["w_emin"][sl]), err, st["w_emin"][sl])
         st["w_emax"][sl] = np.where(f & (err > st["w_emax"][sl]), err, st["w_emax"][sl])
         st["open"][sl] = np.where(done, 0, 1)
-
-
-def span_sum(vals, member):
-    """evx_episode_reduce's order over the member envs: thread t adds envs t, t + SPAN, ... ascending
-    onto 0.0 (non-members skipped), then s[t] = s[t] + s[t + h] for h = SPAN/2 .. 1."""
-    vals = np.asarray(vals, np.float64)
-    s = np.zeros(SPAN)
-    with np.errstate(all="ignore"):
-        for e in range(len(vals)):
-            if member[e]:
-                s[e % SPAN] = s[e % SPAN] + vals[e]
-        h = SPAN // 2
-        while h:
-            s[:h] = s[:h] + s[h:2 * h]
-            h //= 2
-    return s[0]
 
 
 def probe_rows(st, layout_idx, n_layouts):

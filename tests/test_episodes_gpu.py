@@ -5,7 +5,9 @@ The reference everywhere is the numpy fold below (sequential f64 adds per env in
 then per-env window sums in episode order) or the C oracle -- never EpisodeStats itself.
 Per-env numbers must match the fold exactly (f64 fields bit for bit); the summary's f64 sums
 are compared with math.fsum under |got - fsum| <= 64 * 2^-52 * sum|x|, which covers any fixed
-summation tree at these sizes (at most 3 sequential + 10 pairwise adds per sum here)."""
+summation tree at these sizes (at most 3 sequential + 10 pairwise adds per sum here); the reduce's
+own order is held bit for bit to its numpy restatement (span_reduce_util) on window arrays written
+from the host."""
 import csv
 import dataclasses
 import math
@@ -18,10 +20,11 @@ import pytest
 import torch
 
 from golden_util import ROOT
+from span_reduce_util import SPAN, span_max, span_min, span_sum
 
 pytestmark = pytest.mark.gpu
 
-SPAN = 1024  # envs one pass of a reduce workgroup covers (EVX_EPISODE_REDUCE_SPAN)
+# SPAN: envs one pass of a reduce workgroup covers (EVX_EPISODE_REDUCE_SPAN)
 # boundary sizes; SPAN + 1 = 1025 is the first E at which a reduce thread adds a second env
 SIZES = [1, 63, 65, SPAN + 1, 2 * SPAN + 5]
 assert 1025 in SIZES
@@ -185,6 +188,44 @@ def test_boundary_sizes_match_the_fold(E):
             assert torch.equal(snap[k].view(torch.int64) if snap[k].dtype == torch.float64 else snap[k],
                                snap2[k].view(torch.int64) if snap2[k].dtype == torch.float64 else snap2[k]), k
         assert torch.equal(rows, rows2), ("summary bits", sliced)
+
+
+def test_reduce_adds_in_the_stated_order():
+    _need_gpu()
+    from evacx.episodes import ROW_WORDS, EpisodeStats
+    E, nl, cap = 2500, 3, 2  # 2500 > 2 * SPAN: a reduce thread adds up to three envs
+    rng = np.random.default_rng(47)
+    lidx = rng.integers(0, nl, E).astype(np.int32)  # layout nl is carried by no env: an empty row
+    st = EpisodeStats(E, "cuda", 150, layout_idx=torch.from_numpy(lidx).cuda(), n_layouts=nl + 1, cap=cap)
+    w = dict(w_n=rng.integers(0, 5, E), w_len=rng.integers(0, 6000, E), w_evac=rng.integers(0, 600, E),
+             w_dead=rng.integers(0, 600, E), w_ret=rng.standard_normal(E) * np.exp(rng.uniform(-3, 6, E)),
+             w_ret2=rng.random(E) * np.exp(rng.uniform(-6, 12, E)), w_min=rng.standard_normal(E) * 400,
+             w_max=rng.standard_normal(E) * 400, n_total=rng.integers(0, 4, E))
+    for k, v in w.items():
+        getattr(st, k).copy_(torch.from_numpy(v))
+    s = st.summary(clear=False)
+    rows = st.rows.cpu().clone()
+    irow = rows.view(nl + 2, ROW_WORDS).numpy()
+    frow = rows.view(torch.float64).view(nl + 2, ROW_WORDS).numpy()
+    for r in range(nl + 2):
+        member = np.ones(E, bool) if r == nl + 1 else lidx == r
+        for j, k in enumerate(("w_n", "w_len", "w_evac", "w_dead")):
+            assert irow[r, j] == w[k][member].sum(), (r, k)
+        assert irow[r, 8] == (w["n_total"][member] < cap).sum() and irow[r, 9] == (w["n_total"][member] == 0).sum(), r
+        assert _bits(frow[r, 4]) == _bits(span_sum(w["w_ret"], member)), r
+        assert _bits(frow[r, 5]) == _bits(span_sum(w["w_ret2"], member)), r
+        assert frow[r, 6] == span_min(w["w_min"], member) and frow[r, 7] == span_max(w["w_max"], member), r
+        if r != nl:
+            assert member.any() and frow[r, 6] == w["w_min"][member].min() and frow[r, 7] == w["w_max"][member].max(), r
+    # the empty row: sums 0 and 0.0, min +inf, max -inf
+    assert not (lidx == nl).any() and irow[nl, :4].tolist() == [0, 0, 0, 0] and irow[nl, 8:].tolist() == [0, 0]
+    assert _bits(frow[nl, 4]) == _bits(0.0) == _bits(frow[nl, 5]) and frow[nl, 6] == np.inf and frow[nl, 7] == -np.inf
+    assert s["episodes"] == int(w["w_n"].sum()) and len(s["per_layout"]) == nl + 1
+    assert sum(p["episodes"] for p in s["per_layout"]) == s["episodes"]
+    assert s["per_layout"][nl]["episodes"] == 0 and s["per_layout"][nl]["return_mean"] is None
+    assert s["remaining"] == int((w["n_total"] < cap).sum()) and s["no_episode"] == int((w["n_total"] == 0).sum())
+    st.summary(clear=False)
+    assert torch.equal(rows, st.rows.cpu())  # a second run: the same bits
 
 
 # ------------------------------------------------------------------ 2. clear

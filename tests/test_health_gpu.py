@@ -11,10 +11,10 @@ import pytest
 import torch
 
 import health_util as hu
+from span_reduce_util import span_min, span_sum
 
 pytestmark = pytest.mark.gpu
 
-SPAN = 1024       # EVX_EPISODE_REDUCE_SPAN
 DEAD = 1 << 25    # pk: the person is dead
 SAFE = 1 << 24    # pk: the person is evacuated
 
@@ -166,21 +166,6 @@ def test_window_cap_table_and_lifetime_match_a_numpy_fold():
     assert _same(st.tab_avg.cpu().numpy(), tab["tab_avg"]) and (st.w_lo.cpu().numpy() == np.inf).all()
 
 
-def _reduce_reference(vals, member, op=None):
-    """The stated order: thread t adds the row's envs t, t + SPAN, ... ascending onto 0.0 (others
-    skipped), then s[t] = s[t] + s[t + h] for h = SPAN/2 .. 1."""
-    s = np.zeros(SPAN, vals.dtype) if op is None else np.full(SPAN, np.inf)
-    for t in range(SPAN):
-        for e in range(t, len(vals), SPAN):
-            if member[e]:
-                s[t] = s[t] + vals[e] if op is None else min(s[t], vals[e])
-    h = SPAN // 2
-    while h:
-        s[:h] = s[:h] + s[h:2 * h] if op is None else np.minimum(s[:h], s[h:2 * h])
-        h //= 2
-    return s[0]
-
-
 def test_reduce_adds_in_the_stated_order():
     _need_gpu()
     from evacx.health import ROW_WORDS, HealthStats
@@ -201,9 +186,9 @@ def test_reduce_adds_in_the_stated_order():
         member = np.ones(E, bool) if r == nl else lidx == r
         assert irow[r, 0] == w["w_n"][member].sum() and irow[r, 1] == w["w_has"][member].sum()
         assert irow[r, 2] == w["w_alive"][member].sum()
-        assert hu.bits(frow[r, 3]) == hu.bits(_reduce_reference(w["w_avg"], member)), r
-        assert hu.bits(frow[r, 4]) == hu.bits(_reduce_reference(w["w_min"], member)), r
-        assert frow[r, 5] == w["w_lo"][member].min() == _reduce_reference(w["w_lo"], member, op=min), r
+        assert hu.bits(frow[r, 3]) == hu.bits(span_sum(w["w_avg"], member)), r
+        assert hu.bits(frow[r, 4]) == hu.bits(span_sum(w["w_min"], member)), r
+        assert frow[r, 5] == w["w_lo"][member].min() == span_min(w["w_lo"], member), r
     assert s["episodes"] == int(w["w_n"].sum()) and len(s["per_layout"]) == nl
     assert sum(p["episodes"] for p in s["per_layout"]) == s["episodes"]
     assert s["avg_health"] == frow[nl, 3] / irow[nl, 1] and s["min_health_mean"] == frow[nl, 4] / irow[nl, 0]
