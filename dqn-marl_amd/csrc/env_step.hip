@@ -3696,26 +3696,31 @@ int evx_env_orders_push_sample(const evx_layout* l, const evx_state* s, int32_t*
                                const double* r_env, const uint8_t* done_env, int32_t n, int32_t agents_per_env,
                                int64_t pos, int32_t B, int64_t size, uint64_t seed, uint64_t offset, evx_obs* out_s,
                                evx_obs* out_s2, int32_t* out_a, float* out_r, uint8_t* out_done, void* stream) {
-    if (B > 0) {
-        if (!rp || size <= 0 || size > rp->capacity) return fail(-22, "env_orders_push_sample: bad ring size");
-        if (B > size) return fail(-22, "env_orders_push_sample: sample larger than population (random.sample)");
-        if (!out_s || !out_s2 || !out_a || !out_r || !out_done) return fail(-22, "env_orders_push_sample: NULL output");
-        if (pos < 0 || n > rp->capacity) return fail(-22, "env_orders_push_sample: bad push window");
-    }
     int rc = check_layout(l);
     if (rc) return rc;
     if (!s || !s->order || !s->perm_ws) return fail(-22, "env_orders_push: state.order / state.perm_ws is NULL");
     if (!rp || rp->capacity <= 0 || (rp->capacity & (rp->capacity - 1)))
         return fail(-22, "env_orders_push: replay capacity must be a power of two");
-    if (n < 0 || agents_per_env <= 0 || (n > 0 && (!s_obs || !s2 || !a || !r_env || !done_env)))
-        return fail(-22, "env_orders_push: bad push arguments");
+    // the push: what evx_replay_push_term refuses, whether or not a batch is drawn
+    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done) return fail(-22, "env_orders_push: NULL ring array");
+    if (n < 0) return fail(-22, "env_orders_push: n must be >= 0");
+    if (n > rp->capacity) return fail(-22, "env_orders_push: the capacity does not hold n rows");
+    if (pos < 0 || pos >= rp->capacity) return fail(-22, "env_orders_push: pos outside [0, capacity)");
+    if (agents_per_env < 1 || n % agents_per_env)
+        return fail(-22, "env_orders_push: n must be a multiple of agents_per_env >= 1");
+    if (n > 0 && (!s_obs || !s2 || !a || !r_env || !done_env)) return fail(-22, "env_orders_push: NULL argument");
+    if (B > 0) {
+        if (size <= 0 || size > rp->capacity) return fail(-22, "env_orders_push_sample: bad ring size");
+        if (B > size) return fail(-22, "env_orders_push_sample: sample larger than population (random.sample)");
+        if (!out_s || !out_s2 || !out_a || !out_r || !out_done) return fail(-22, "env_orders_push_sample: NULL output");
+    }
     int hmin = 0;
     const int hcap = heavy_cap(*l, &hmin);
     const int nord = s->E > 0 ? (s->E + 1023) / 1024 : 0;
     const int nsmp = B > 0 ? (B + 255) / 256 : 0;
     const unsigned nblk = (unsigned)(nord + nsmp + (n + 1023) / 1024);
     if (nblk == 0) return 0;
-    evx::PushArgs pa{*rp, s_obs, s2, s2_term, a, r_env, done_env, n, agents_per_env, pos & (rp->capacity - 1)};
+    evx::PushArgs pa{*rp, s_obs, s2, s2_term, a, r_env, done_env, n, agents_per_env, pos};
     evx::SampleArgs sa{size, B, seed, offset, out_s, out_s2, out_a, out_r, out_done};
     if (((uintptr_t)s->perm_ws & 15) == 0)
         hipLaunchKernelGGL(evx::env_orders_push_kernel<true>, dim3(nblk), dim3(1024), 0, (hipStream_t)stream,

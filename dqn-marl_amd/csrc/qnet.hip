@@ -1195,6 +1195,7 @@ __global__ __launch_bounds__(256) void relu_grad_kernel(float* __restrict__ dy, 
 // ===================================================================== C-ABI
 namespace {
 using evxh::fail;
+using evxh::failf;
 using evxh::hip_status;
 unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
@@ -2019,10 +2020,25 @@ int evx_act(const float* Q, int32_t n, int32_t A, float epsilon, uint64_t seed, 
     return hip_status("act");
 }
 
+// What a push of n rows at pos must satisfy before anything is launched (as evx_replay_push_blocks):
+// n > capacity would let two threads write one slot, a pos outside the ring a slot outside it, and
+// agents_per_env < 1 divides by zero on the device. 0: launch; 1: nothing to push; -22: refused.
+static int push_check(const char* who, const evx_replay* rp, const evx_obs* s, const evx_obs* s2, const int32_t* a,
+                      const double* r_env, const uint8_t* done_env, int32_t n, int32_t agents_per_env, int64_t pos) {
+    if (!rp || rp->capacity <= 0) return failf(-22, "%s: bad ring (NULL, or capacity < 1)", who);
+    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done) return failf(-22, "%s: NULL ring array", who);
+    if (n < 0) return failf(-22, "%s: n must be >= 0", who);
+    if (n > rp->capacity) return failf(-22, "%s: the capacity does not hold n rows", who);
+    if (pos < 0 || pos >= rp->capacity) return failf(-22, "%s: pos outside [0, capacity)", who);
+    if (agents_per_env < 1 || n % agents_per_env) return failf(-22, "%s: n must be a multiple of agents_per_env >= 1", who);
+    if (n == 0) return 1;
+    if (!s || !s2 || !a || !r_env || !done_env) return failf(-22, "%s: NULL argument", who);
+    return 0;
+}
+
 int evx_replay_push(const evx_replay* rp, const evx_obs* s, const evx_obs* s2, const int32_t* a, const double* r_env,
                     const uint8_t* done_env, int32_t n, int32_t agents_per_env, int64_t pos, void* stream) {
-    if (!rp || rp->capacity <= 0) return fail(-22, "replay: bad ring");
-    if (n <= 0) return 0;
+    if (int rc = push_check("replay_push", rp, s, s2, a, r_env, done_env, n, agents_per_env, pos)) return rc < 0 ? rc : 0;
     hipLaunchKernelGGL(evxq::replay_push_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, *rp, s, s2,
                        (const evx_obs*)nullptr, a, r_env, done_env, n, agents_per_env, pos);
     return hip_status("replay_push");
@@ -2031,8 +2047,8 @@ int evx_replay_push(const evx_replay* rp, const evx_obs* s, const evx_obs* s2, c
 int evx_replay_push_term(const evx_replay* rp, const evx_obs* s, const evx_obs* s2, const evx_obs* s2_term,
                          const int32_t* a, const double* r_env, const uint8_t* done_env, int32_t n,
                          int32_t agents_per_env, int64_t pos, void* stream) {
-    if (!rp || rp->capacity <= 0) return fail(-22, "replay: bad ring");
-    if (n <= 0) return 0;
+    if (int rc = push_check("replay_push_term", rp, s, s2, a, r_env, done_env, n, agents_per_env, pos))
+        return rc < 0 ? rc : 0;
     hipLaunchKernelGGL(evxq::replay_push_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, *rp, s, s2, s2_term,
                        a, r_env, done_env, n, agents_per_env, pos);
     return hip_status("replay_push_term");
@@ -2044,6 +2060,8 @@ int evx_replay_sample(const evx_replay* rp, int64_t size, int32_t B, uint64_t se
     if (B <= 0) return 0;
     if (size > rp->capacity) return fail(-22, "replay: size > capacity");
     if (B > size) return fail(-22, "replay: sample larger than population (random.sample)");
+    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done) return fail(-22, "replay_sample: NULL ring array");
+    if (!s || !s2 || !a || !r || !done) return fail(-22, "replay_sample: NULL argument");
     hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, (int64_t)0,
                        size, B, seed, offset, s, s2, a, r, done, idx_out);
     return hip_status("replay_sample");
@@ -2086,6 +2104,8 @@ int evx_replay_sample_window(const evx_replay* rp, int64_t base, int64_t count, 
     if (count > rp->capacity || base < 0 || base >= rp->capacity) return fail(-22, "replay: bad window");
     if (B <= 0) return 0;
     if (B > count) return fail(-22, "replay: sample larger than the window (random.sample)");
+    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done) return fail(-22, "replay_sample_window: NULL ring array");
+    if (!s || !s2 || !a || !r || !done) return fail(-22, "replay_sample_window: NULL argument");
     hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, base, count,
                        B, seed, offset, s, s2, a, r, done, idx_out);
     return hip_status("replay_sample_window");

@@ -209,6 +209,14 @@ class VecTrainer:
         self.last_range = None  # n_step > 1: the (base, count) the last learn step's chains ran over
         if precision not in ("f32", "bf16", "exact"):
             raise ValueError(f"precision must be 'f32', 'bf16' or 'exact', not {precision!r}")
+        # a ring smaller than one push: two rows of the push would share a slot (the winner undefined)
+        # and window() would count a negative number of entries. Groups push their own rows one after
+        # the other; the lagged schedule's window sets a whole step's rows aside
+        n_groups = groups if isinstance(groups, int) and groups > 1 and not lagged_learn else 1
+        push_rows = -(-E // n_groups) * layout.R
+        if replay_capacity < push_rows:
+            raise ValueError(f"replay_capacity = {replay_capacity} is smaller than one push of {push_rows} rows "
+                             f"(E * R / groups = {E} * {layout.R} / {n_groups})")
         self.lay, self.E, self.R = layout, E, layout.R
         self.device = layout.device
         # the push reads env.obs_prev: no copy per step

@@ -371,12 +371,19 @@ int evx_dropout_mask(uint8_t *mask, int64_t n, float p, uint64_t seed, uint64_t 
 /* DQNAgent.act (agents/dqn_agent.py:101-124): epsilon-greedy over argmax_a Q[i][a] */
 int evx_act(const float *Q, int32_t n, int32_t A, float epsilon, uint64_t seed, uint64_t offset,
             int32_t *actions, void *stream);
+/* DQNAgent.remember for n rows (agents/dqn_agent.py:97-99): row i goes to ring slot
+ * (pos + i) mod capacity with a[i], s[i], s2[i] and the team reward (f64 -> f32, round to nearest
+ * even) and done flag of env i / agents_per_env. The caller keeps pos and size: pos advances by n
+ * mod capacity, size grows to at most capacity.
+ * -22 before any launch (evx_q_last_error names the entry): a NULL rp or capacity < 1; a NULL ring
+ * array; n < 0; n > capacity (two rows of one push would share a slot, the winner undefined); pos
+ * outside [0, capacity); agents_per_env < 1; n no multiple of agents_per_env. Then n == 0: 0,
+ * nothing done (s .. done_env may be NULL). -22: a NULL s, s2, a, r_env or done_env. */
 int evx_replay_push(const evx_replay *rp, const evx_obs *s, const evx_obs *s2, const int32_t *a,
                     const double *r_env, const uint8_t *done_env, int32_t n, int32_t agents_per_env, int64_t pos,
                     void *stream);
-/* random.sample replacement for the vectorised learner: B uniform indices < size */
 /* evx_replay_push with s2 = done_env[e] ? s2_term : s2 (the terminal observations of
- * envs that evx_env_step auto-reset) */
+ * envs that evx_env_step auto-reset); s2_term may be NULL (evx_replay_push). The same refusals. */
 int evx_replay_push_term(const evx_replay *rp, const evx_obs *s, const evx_obs *s2, const evx_obs *s2_term,
                          const int32_t *a, const double *r_env, const uint8_t *done_env, int32_t n,
                          int32_t agents_per_env, int64_t pos, void *stream);
@@ -389,17 +396,35 @@ int evx_env_orders_push(const evx_layout *l, const evx_state *s, int32_t *perm, 
                         const double *r_env, const uint8_t *done_env, int32_t n, int32_t agents_per_env,
                         int64_t pos, void *stream);
 /* ... and the learn step's batch (evx_replay_sample over the ring as it stands after the push:
- * size = the ring size after it; B = 0 draws nothing) in the same launch. */
+ * size = the ring size after it; B = 0 draws nothing) in the same launch; a drawn slot inside the
+ * push window is read from the push's sources.
+ * -22 before any launch, whether or not B > 0: a bad layout or state; a capacity that is no power
+ * of two; and what evx_replay_push_term refuses (a NULL ring array, n < 0, n > capacity, pos outside
+ * [0, capacity), agents_per_env < 1, n no multiple of it, a NULL source array with n > 0). With
+ * B > 0 also: size outside [1, capacity], B > size, a NULL output. */
 int evx_env_orders_push_sample(const evx_layout *l, const evx_state *s, int32_t *perm, const evx_replay *rp,
                                const evx_obs *s_obs, const evx_obs *s2, const evx_obs *s2_term, const int32_t *a,
                                const double *r_env, const uint8_t *done_env, int32_t n, int32_t agents_per_env,
                                int64_t pos, int32_t B, int64_t size, uint64_t seed, uint64_t offset, evx_obs *out_s,
                                evx_obs *out_s2, int32_t *out_a, float *out_r, uint8_t *out_done, void *stream);
+/* random.sample replacement for the vectorised learner (agents/dqn_agent.py:132): row i of the
+ * outputs is the ring's row at slot perm(i), for a keyed pseudo-random permutation perm of
+ * [0, size) (a 6-round Feistel network, cycle-walked; the key is all 128 bits of (seed, offset));
+ * idx_out (may be NULL) gets the slots. Without replacement: B = size draws visit every slot once.
+ * Documented limit: the first draw is uniform and the joint distribution of the draws close to
+ * uniform only from a few dozen entries on -- below 32 entries the pairs of draws are measurably
+ * non-uniform, and at some sizes below 15 a slot's frequency as first draw is off 1/size by up to
+ * 3 % (DESIGN.md section 5.0 has the measurements). Trainers sample rings no smaller than a batch.
+ * -22 before any launch: a NULL rp or size < 1. Then B <= 0: 0, nothing done (the outputs may be
+ * NULL). -22: size > capacity; B > size (as random.sample raises); a NULL ring array; a NULL s, s2,
+ * a, r or done. */
 int evx_replay_sample(const evx_replay *rp, int64_t size, int32_t B, uint64_t seed, uint64_t offset, evx_obs *s,
                       evx_obs *s2, int32_t *a, float *r, uint8_t *done, int64_t *idx_out, void *stream);
 /* B uniform indices over the ring window [base, base+count) mod capacity (same draws as
  * evx_replay_sample with base 0): lets a learn step sample the transitions already pushed
- * while the next push overwrites the slots outside the window (lagged-replay schedule) */
+ * while the next push overwrites the slots outside the window (lagged-replay schedule).
+ * -22 before any launch: a NULL rp or count < 1; count > capacity or base outside [0, capacity).
+ * Then B <= 0: 0. -22: B > count; a NULL ring array; a NULL s, s2, a, r or done. */
 int evx_replay_sample_window(const evx_replay *rp, int64_t base, int64_t count, int32_t B, uint64_t seed,
                              uint64_t offset, evx_obs *s, evx_obs *s2, int32_t *a, float *r, uint8_t *done,
                              int64_t *idx_out, void *stream);
@@ -430,8 +455,9 @@ int evx_replay_sample_joint(const evx_replay *rp, int64_t size, int32_t B, int32
  * so y = R + gamma_row * Q_target(s2, .) * !done (evx_td_opts.gamma_row). The chain stops at a
  * terminal slot (never across an auto-reset) and at the end of the range; a row with d0 >= count
  * keeps its own slot (L = 1); n_step = 1 copies the slot's r, done, s2 and gamma_row = gamma.
- * -22 before any launch: a NULL required pointer, n_step outside [1, EVX_NSTEP_MAX], stride < 1,
- * count outside [0, capacity], base outside [0, capacity), gamma not finite (evx_q_last_error). */
+ * -22 before any launch: a NULL rp, idx, s2, r, done or gamma_row (len may be NULL), n_step outside
+ * [1, EVX_NSTEP_MAX], stride < 1, count outside [0, capacity], base outside [0, capacity), gamma
+ * not finite (evx_q_last_error). Then B <= 0: 0. -22: a ring without its s2, r or done array. */
 #define EVX_NSTEP_MAX 32
 int evx_replay_nstep(const evx_replay *rp, const int64_t *idx, int32_t B, int64_t base, int64_t count,
                      int64_t stride, int32_t n_step, float gamma, evx_obs *s2, float *r, uint8_t *done,

@@ -97,6 +97,14 @@ void orc_replay_indices(int64_t base, int64_t size, int64_t capacity, int B, uin
     }
 }
 
+/* orc_replay_indices under T consecutive offsets offset0, offset0 + 1, ..: idx [T][B] (the draw
+ * statistics of tests/test_replay_cpu.py, one call instead of T) */
+void orc_replay_indices_offsets(int64_t base, int64_t size, int64_t capacity, int B, uint64_t seed, uint64_t offset0,
+                                int64_t T, uint32_t stream, int64_t *idx) {
+    for (int64_t t = 0; t < T; t++)
+        orc_replay_indices(base, size, capacity, B, seed, offset0 + (uint64_t)t, stream, idx + t * B);
+}
+
 /* keep[r][c] of the fused MLP's dropout: one fmix32 hash per (row pair, column), low 16 bits
  * for the even row, high 16 for the odd; keep iff the 16-bit value >= floor(p * 65536) */
 void orc_dropout_keep(uint32_t seed, uint32_t stream, float p, int rows, int cols, uint8_t *keep) {

@@ -289,6 +289,17 @@ def replay_indices(base, size, capacity, B, seed, offset, stream=0):
     return idx
 
 
+def replay_indices_offsets(base, size, capacity, B, seed, offset0, T, stream=0):
+    """replay_indices under the T consecutive offsets offset0, offset0 + 1, ..: int64 [T][B]."""
+    idx = np.zeros((T, B), np.int64)
+    L = lib()
+    L.orc_replay_indices_offsets.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_uint64,
+                                             C.c_int64, C.c_uint32, C.c_void_p]
+    L.orc_replay_indices_offsets(int(base), int(size), int(capacity), int(B), int(seed) & (2**64 - 1),
+                                 int(offset0) & (2**64 - 1), int(T), int(stream) & 0xFFFFFFFF, _p(idx))
+    return idx
+
+
 def dropout_keep(seed, stream, p, rows, cols=512):
     """The fused MLP kernels' dropout keep mask restated: uint8 [rows][cols]."""
     keep = np.zeros((rows, cols), np.uint8)

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+from order_util import want_classes, want_order, want_perm
+
 pytestmark = pytest.mark.gpu
 
 
@@ -56,23 +58,13 @@ def test_act_perm_and_env_order_match_numpy(E):
     env.compute_orders(perm2)  # both in one launch
     torch.cuda.synchronize()
     assert torch.equal(perm, perm2) and torch.equal(order1, env.order)
-    sel = scal[:, 0] >= t_max
-    want = np.concatenate([np.nonzero(sel)[0], np.nonzero(~sel)[0]]).astype(np.int32)
     got = perm.cpu().numpy()
-    assert np.array_equal(got[:E], want)
+    assert np.array_equal(got[:E], want_perm(scal, t_max))
     assert np.all(got[E:] == -7)
-    rem = P - ev - dead
-    bucket = 15 - np.minimum(15, np.maximum(0, rem) * 16 // (P + 1))
-    want_order = np.argsort(bucket, kind="stable").astype(np.int32)
+    want, want_heavy = want_order(scal, P)
     order = env.order.cpu().numpy()
-    assert np.array_equal(order[:E], want_order)
-    assert order[E] == min(176, int(np.sum(rem >= max(1, P // 4))))
-
-
-def _want_classes(scal, P, t_max):
-    rem = P - scal[:, 2] - scal[:, 3]
-    b = 15 - np.minimum(15, np.maximum(0, rem) * 16 // (P + 1))
-    return (b | np.where(scal[:, 0] >= t_max, 0x10, 0) | np.where(rem >= max(1, P // 4), 0x20, 0)).astype(np.uint8)
+    assert np.array_equal(order[:E], want)
+    assert order[E] == want_heavy
 
 
 def test_step_and_reset_write_class_bytes():
@@ -99,7 +91,7 @@ def test_step_and_reset_write_class_bytes():
         if t % 37 == 0 or t == 101:
             torch.cuda.synchronize()
             scal = env.scal.view(E, 4).cpu().numpy()
-            assert np.array_equal(env.perm_ws[:E].cpu().numpy(), _want_classes(scal, P, t_max)), t
+            assert np.array_equal(env.perm_ws[:E].cpu().numpy(), want_classes(scal, P, t_max)), t
     assert n_done > 0
 
 
