@@ -6,7 +6,9 @@ training over several seeds and hyperparameters, ranked by death rate, then evac
 Reads the env and agent sections of ``configs/dqn.yaml`` as train_vec does; ``--lr``, ``--gamma``,
 ``--epsilon-decay``, ``--target-every`` and ``--seeds`` take one value for every member or K
 comma-separated values (default: the config's agent keys; seeds: ``--seed`` + k). ``--envs`` is the
-total over members (a multiple of K). Every ``--log-every`` steps one ``episode_summary()``:
+total over members (a multiple of K). ``--loss``, ``--huber-delta``, ``--target-tau`` and ``--n-step``
+are comma lists in the same way (defaults: the optional ``agent:`` keys train_vec reads);
+``--double-q`` holds for every member. The ring is sized for the deepest member's n_step pushes. Every ``--log-every`` steps one ``episode_summary()``:
 
   member<k>/training_log.csv   train_vec's columns, member k's envs
   population_summary.csv       per log line the mean, std, min and max over members of return,
@@ -52,6 +54,13 @@ def parse_args(argv=None):
     for flag, what in (("--lr", "learning rate"), ("--gamma", "discount"), ("--epsilon-decay", "epsilon decay"),
                        ("--target-every", "learn steps between target copies"), ("--seeds", "initial-weight seed")):
         ap.add_argument(flag, default=None, metavar="a,b,..", help=f"{what}: one value, or one per member")
+    ap.add_argument("--double-q", action="store_true", default=None,
+                    help="Double-Q targets for every member (config: agent.double_dqn)")
+    for flag, what in (("--loss", "TD loss, mse or huber (config: agent.loss; mse)"),
+                       ("--huber-delta", "Huber delta (config: agent.huber_delta; 1.0)"),
+                       ("--target-tau", "soft target rate per learn step, 0: the hard copy (config: agent.target_tau)"),
+                       ("--n-step", "n-step returns from the member's ring, 1..32 (config: agent.n_step; 1)")):
+        ap.add_argument(flag, default=None, metavar="a,b,..", help=f"{what}: one value, or one per member")
     ap.add_argument("--eval-episodes", type=int, default=0, help="episodes per env of a final greedy evaluation")
     ap.add_argument("--eval-envs", type=int, default=None, help="envs of that evaluation (default: a member's envs)")
     return ap.parse_args(argv)
@@ -85,6 +94,22 @@ def member_hparams(args, agent_cfg) -> dict:
                                        int(agent_cfg.get("target_update_freq", 200))),
                 init_seeds=[args.seed + k for k in range(K)] if args.seeds is None else
                 broadcast("seeds", args.seeds, K, int, 0))
+
+
+def member_options(args, agent_cfg) -> dict:
+    """The learner options the trainer takes: double_q (one bool), and loss, huber_delta, target_tau
+    and n_step as per-member lists, from the flags and the optional agent keys train_vec reads
+    (double_dqn, loss, huber_delta, target_tau, n_step). The values are checked as the trainer's."""
+    from evacx.population import per_member
+    K = args.members
+    o = dict(loss=broadcast("loss", args.loss, K, str, str(agent_cfg.get("loss", "mse"))),
+             huber_delta=broadcast("huber-delta", args.huber_delta, K, float, float(agent_cfg.get("huber_delta", 1.0))),
+             target_tau=broadcast("target-tau", args.target_tau, K, float, float(agent_cfg.get("target_tau", 0.0))),
+             n_step=broadcast("n-step", args.n_step, K, int, agent_cfg.get("n_step", 1)))
+    for name, v in o.items():
+        per_member(name, v, K)
+    o["double_q"] = bool(args.double_q if args.double_q is not None else agent_cfg.get("double_dqn", False))
+    return o
 
 
 def rank_key(row):
@@ -124,6 +149,7 @@ def train_pop(args):
         config = yaml.safe_load(f)
     ec, ac = config["env"], config["agent"]
     hp = member_hparams(args, ac)
+    opts = member_options(args, ac)
     if not torch.cuda.is_available():
         raise RuntimeError("train_pop needs an MI355X (HIP) device; no CPU fallback exists")
     out_dir = args.out or os.path.join(project_root, config.get("save_path", "dqn_results"))
@@ -133,16 +159,19 @@ def train_pop(args):
     lay = DeviceLayout(build_tables(spec), int(ec["num_people"]), device=device)
     batch = args.batch or max(256, int(ac.get("batch_size", 32)))
     n = (args.envs // max(K, 1)) * lay.R  # a member's rows per push
-    capacity = max(int(ac.get("memory_size", 50000)), 4 * batch, 2 * n)
+    # at least two pushes in the ring, and a whole chain of the deepest member's n_step of them
+    capacity = max(int(ac.get("memory_size", 50000)), 4 * batch, max(2, max(opts["n_step"])) * n)
     tr = PopulationTrainer(lay, args.envs, members=K, seed=args.seed, batch=batch, replay_capacity=capacity,
                            epsilon=float(ac.get("epsilon", 1.0)), epsilon_min=float(ac.get("epsilon_min", 0.02)),
-                           episode_stats=True, **hp)
+                           episode_stats=True, **hp, **opts)
     dirs = [os.path.join(out_dir, f"member{k}") for k in range(K)]
     for d in dirs:
         os.makedirs(d, exist_ok=True)
     print(f"env {spec.L}x{spec.W}, {lay.P} people; {K} members x {args.envs // K} envs, batch {batch} and replay "
           f"{capacity} per member on {device}; lr {hp['lr']}, gamma {hp['gamma']}, epsilon decay "
-          f"{hp['epsilon_decay']}, target every {hp['target_every']}, seeds {hp['init_seeds']}")
+          f"{hp['epsilon_decay']}, target every {hp['target_every']}, seeds {hp['init_seeds']}; "
+          f"{'double-Q' if opts['double_q'] else 'max'} target, loss {opts['loss']}, huber delta {opts['huber_delta']}, "
+          f"target tau {opts['target_tau']}, n_step {opts['n_step']}")
     files = [open(os.path.join(d, "training_log.csv"), "w", newline="") for d in dirs]
     rows = None
     try:

@@ -2801,7 +2801,8 @@ __device__ __forceinline__ float polyak_one(const AdamPack& a, int i, float tau,
     a.p[i] = tn;
     return tn;
 }
-__global__ __launch_bounds__(256) void polyak_pack3_kernel(AdamPack a, float tau, float omt) {
+// the body of polyak_pack3_kernel and polyak_pack3_g_kernel: one net's blend and repack
+__device__ __forceinline__ void polyak_pack3_body(AdamPack a, float tau, float omt) {
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (i >= NPAR) return;
     if (i < OB1) {
@@ -2846,6 +2847,27 @@ __global__ __launch_bounds__(256) void polyak_pack3_kernel(AdamPack a, float tau
     } else {
         polyak_one(a, i, tau, omt);
     }
+}
+__global__ __launch_bounds__(256) void polyak_pack3_kernel(AdamPack a, float tau, float omt) {
+    polyak_pack3_body(a, tau, omt);
+}
+// evx_qmlp_polyak_pack3_g: net blockIdx.y of the [nets][...] buffers with its own rate; a net whose
+// tau is 0 (a member with a hard target copy) writes nothing
+struct PolyakNets {
+    float tau[64], omt[64];
+};
+__global__ __launch_bounds__(256) void polyak_pack3_g_kernel(AdamPack a0, PolyakNets c) {
+    const size_t G = blockIdx.y;
+    const float tau = c.tau[G];
+    if (tau == 0.f) return;
+    AdamPack a = a0;
+    a.p += G * NPAR; a.g += G * NPAR;
+    a.w1b += G * HID * K1X; a.w1l += G * HID * K1P;
+    a.w2b += G * HID2 * HID; a.w2l += G * HID2 * HID;
+    a.w2t = adv(a.w2t, G * HID2 * HID); a.w2tl = adv(a.w2tl, G * HID2 * HID);
+    a.w1o = adv(a.w1o, G * HID * 128); a.w1ol = adv(a.w1ol, G * HID * 128);
+    a.b1c += G * HID;
+    polyak_pack3_body(a, tau, c.omt[G]);
 }
 
 // squared-norm partials of the flat gradient buffer (one per workgroup) for adam_pack3_kernel
@@ -3771,6 +3793,34 @@ int evx_qmlp_polyak_pack3(const float* p, float* t, float tau, float one_minus_t
     hipLaunchKernelGGL(evxm::polyak_pack3_kernel, dim3((unsigned)((evxm::NPAR + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, a, tau, one_minus_tau);
     return hip_status("qmlp_polyak_pack3");
+}
+
+int evx_qmlp_polyak_pack3_g(const float* p, float* t, const float* tau, const float* one_minus_tau, uint16_t* w1b,
+                            uint16_t* w1l, float* b1c, uint16_t* w2b, uint16_t* w2l, uint16_t* w2t, uint16_t* w2tl,
+                            uint16_t* w1o, uint16_t* w1ol, int32_t nets, void* stream) {
+    if (!p || !t || !tau || !one_minus_tau || !w1b || !w1l || !b1c || !w2b || !w2l)
+        return fail(-22, "qmlp_polyak_pack3_g: NULL argument");
+    if (nets < 1 || nets > 64) return fail(-22, "qmlp_polyak_pack3_g: nets must be 1..64");
+    if ((w1o == nullptr) != (w1ol == nullptr)) return fail(-22, "qmlp_polyak_pack3_g: w1o and w1ol go together");
+    if ((w2t == nullptr) != (w2tl == nullptr)) return fail(-22, "qmlp_polyak_pack3_g: w2t and w2tl go together");
+    evxm::PolyakNets c{};
+    for (int g = 0; g < nets; g++) {
+        if (!(tau[g] >= 0.f && tau[g] <= 1.f)) return fail(-22, "qmlp_polyak_pack3_g: tau must lie in [0, 1]");
+        if (!std::isfinite(one_minus_tau[g])) return fail(-22, "qmlp_polyak_pack3_g: one_minus_tau must be finite");
+        c.tau[g] = tau[g];
+        c.omt[g] = one_minus_tau[g];
+    }
+    evxm::AdamPack a = {};
+    a.p = t;
+    a.g = const_cast<float*>(p);  // read only (polyak_one)
+    a.w1b = reinterpret_cast<__bf16*>(w1b); a.w1l = reinterpret_cast<__bf16*>(w1l);
+    a.w2b = reinterpret_cast<__bf16*>(w2b); a.w2l = reinterpret_cast<__bf16*>(w2l);
+    a.w2t = reinterpret_cast<__bf16*>(w2t); a.w2tl = reinterpret_cast<__bf16*>(w2tl);
+    a.w1o = reinterpret_cast<__bf16*>(w1o); a.w1ol = reinterpret_cast<__bf16*>(w1ol);
+    a.b1c = b1c;
+    hipLaunchKernelGGL(evxm::polyak_pack3_g_kernel, dim3((unsigned)((evxm::NPAR + 255) / 256), (unsigned)nets),
+                       dim3(256), 0, (hipStream_t)stream, a, c);
+    return hip_status("qmlp_polyak_pack3_g");
 }
 
 int evx_qmlp_backward(const evx_qmlp_params* p, int32_t B, const float* dq, const uint16_t* x, const uint16_t* h1,

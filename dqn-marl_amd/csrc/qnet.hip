@@ -787,15 +787,15 @@ __global__ __launch_bounds__(256) void colsum_finish(const float* __restrict__ p
 // launches on different streams with their own workspaces never meet).
 // sel / delta / gamma_row (evx_td_opts; not the reference's): the bootstrap action given instead
 // of the target's maximum, the Huber loss instead of the squared error, a discount per row.
-__global__ __launch_bounds__(256) void td_loss_kernel(const float* __restrict__ Q, const float* __restrict__ Qt,
-                                                      int A, const int32_t* __restrict__ act,
-                                                      const float* __restrict__ rew, const uint8_t* __restrict__ done,
-                                                      float gamma, int B, const float* __restrict__ w,
-                                                      float* __restrict__ dQ, float* __restrict__ part,
-                                                      float* __restrict__ td_abs, int ntd = 0,
-                                                      float* __restrict__ zero = nullptr, int64_t nzero = 0,
-                                                      const int32_t* __restrict__ sel = nullptr, float delta = 0.f,
-                                                      const float* __restrict__ gamma_row = nullptr) {
+// (the body of td_loss_kernel and td_loss_nets_kernel)
+__device__ __forceinline__ void td_loss_body(const float* __restrict__ Q, const float* __restrict__ Qt, int A,
+                                             const int32_t* __restrict__ act, const float* __restrict__ rew,
+                                             const uint8_t* __restrict__ done, float gamma, int B,
+                                             const float* __restrict__ w, float* __restrict__ dQ,
+                                             float* __restrict__ part, float* __restrict__ td_abs, int ntd,
+                                             float* __restrict__ zero, int64_t nzero,
+                                             const int32_t* __restrict__ sel, float delta,
+                                             const float* __restrict__ gamma_row) {
     __shared__ float red[256];
     if (zero && (int)blockIdx.x >= ntd) {  // the extra workgroups clear the gradient buffer for the backward
         if (blockIdx.y) return;
@@ -854,6 +854,33 @@ __global__ __launch_bounds__(256) void td_loss_kernel(const float* __restrict__ 
         __syncthreads();
     }
     if (threadIdx.x == 0) part[gy * nb + blockIdx.x] = red[0];
+}
+__global__ __launch_bounds__(256) void td_loss_kernel(const float* __restrict__ Q, const float* __restrict__ Qt,
+                                                      int A, const int32_t* __restrict__ act,
+                                                      const float* __restrict__ rew, const uint8_t* __restrict__ done,
+                                                      float gamma, int B, const float* __restrict__ w,
+                                                      float* __restrict__ dQ, float* __restrict__ part,
+                                                      float* __restrict__ td_abs, int ntd = 0,
+                                                      float* __restrict__ zero = nullptr, int64_t nzero = 0,
+                                                      const int32_t* __restrict__ sel = nullptr, float delta = 0.f,
+                                                      const float* __restrict__ gamma_row = nullptr) {
+    td_loss_body(Q, Qt, A, act, rew, done, gamma, B, w, dQ, part, td_abs, ntd, zero, nzero, sel, delta, gamma_row);
+}
+// evx_td_loss_opt_nets: a Huber delta per net (0: that net's squared error), by value
+struct TdDeltas {
+    float v[64];
+};
+__global__ __launch_bounds__(256) void td_loss_nets_kernel(const float* __restrict__ Q, const float* __restrict__ Qt,
+                                                           int A, const int32_t* __restrict__ act,
+                                                           const float* __restrict__ rew,
+                                                           const uint8_t* __restrict__ done, float gamma, int B,
+                                                           const float* __restrict__ w, float* __restrict__ dQ,
+                                                           float* __restrict__ part, float* __restrict__ td_abs,
+                                                           int ntd, float* __restrict__ zero, int64_t nzero,
+                                                           const int32_t* __restrict__ sel, TdDeltas deltas,
+                                                           const float* __restrict__ gamma_row) {
+    td_loss_body(Q, Qt, A, act, rew, done, gamma, B, w, dQ, part, td_abs, ntd, zero, nzero, sel,
+                 deltas.v[blockIdx.y], gamma_row);
 }
 // loss[y] = (sum of net y's nb block partials) / B: strided partial sums, then a fixed LDS tree
 __global__ __launch_bounds__(256) void td_finish_kernel(const float* __restrict__ part, int nb, int B,
@@ -1909,9 +1936,9 @@ int64_t evx_td_loss_ws_floats(int32_t B, int32_t nets) {
 static int td_launch(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew,
                      const uint8_t* done, float gamma, int32_t B, int32_t nets, const float* w, float* dQ, float* loss,
                      float* td_abs, float* zero, int64_t nzero, float* ws, int64_t ws_floats, void* stream,
-                     const char* what, const evx_td_opts* opt = nullptr) {
+                     const char* what, const evx_td_opts* opt = nullptr, const float* deltas = nullptr) {
     const int32_t* sel = opt ? opt->sel : nullptr;
-    const float delta = opt ? opt->huber_delta : 0.f;
+    const float delta = opt && !deltas ? opt->huber_delta : 0.f;
     const float* gamma_row = opt ? opt->gamma_row : nullptr;
     if (!(delta >= 0.f) || !std::isfinite(delta)) return fail(-22, "td_loss: huber_delta must be finite and >= 0");
     if (B <= 0) return 0;
@@ -1921,8 +1948,15 @@ static int td_launch(const float* Q, const float* Qt, int32_t A, const int32_t* 
     if (!ws || ws_floats < (int64_t)ntd * nets) return fail(-22, "td_loss: workspace smaller than evx_td_loss_ws_floats");
     const int nz = zero && nzero > 0 ? (int)std::min<int64_t>((nzero + 256 * 16 - 1) / (256 * 16), 512) : 0;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(evxq::td_loss_kernel, dim3(ntd + nz, nets), dim3(256), 0, st, Q, Qt, A, act, rew, done, gamma, B,
-                       w, dQ, ws, td_abs, ntd, nz ? zero : nullptr, nzero, sel, delta, gamma_row);
+    if (deltas) {  // evx_td_loss_opt_nets (nets <= 64 and every delta checked there)
+        evxq::TdDeltas dl{};
+        for (int k = 0; k < nets; k++) dl.v[k] = deltas[k];
+        hipLaunchKernelGGL(evxq::td_loss_nets_kernel, dim3(ntd + nz, nets), dim3(256), 0, st, Q, Qt, A, act, rew, done,
+                           gamma, B, w, dQ, ws, td_abs, ntd, nz ? zero : nullptr, nzero, sel, dl, gamma_row);
+    } else {
+        hipLaunchKernelGGL(evxq::td_loss_kernel, dim3(ntd + nz, nets), dim3(256), 0, st, Q, Qt, A, act, rew, done,
+                           gamma, B, w, dQ, ws, td_abs, ntd, nz ? zero : nullptr, nzero, sel, delta, gamma_row);
+    }
     hipLaunchKernelGGL(evxq::td_finish_kernel, dim3(nets), dim3(256), 0, st, (const float*)ws, ntd, B, loss);
     return hip_status(what);
 }
@@ -1954,6 +1988,20 @@ int evx_td_loss_opt(const float* Q, const float* Qt, int32_t A, const int32_t* a
                     void* stream) {
     return td_launch(Q, Qt, A, act, rew, done, gamma, B, nets, w, dQ, loss, td_abs, zero, nzero, ws, ws_floats, stream,
                      "td_loss_opt", opt);
+}
+
+int evx_td_loss_opt_nets(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew,
+                         const uint8_t* done, float gamma, int32_t B, int32_t nets, const float* w, float* dQ,
+                         float* loss, float* td_abs, float* zero, int64_t nzero, float* ws, int64_t ws_floats,
+                         const evx_td_opts* opt, const float* huber_delta, void* stream) {
+    if (!huber_delta) return fail(-22, "td_loss_opt_nets: NULL huber_delta");
+    if (nets < 1 || nets > 64) return fail(-22, "td_loss_opt_nets: nets must be 1..64");
+    for (int k = 0; k < nets; k++)
+        if (!(huber_delta[k] >= 0.f) || !std::isfinite(huber_delta[k]))
+            return fail(-22, "td_loss_opt_nets: huber_delta must be finite and >= 0");
+    if (!Q || !Qt || !act || !rew || !done || !dQ || !loss) return fail(-22, "td_loss_opt_nets: NULL argument");
+    return td_launch(Q, Qt, A, act, rew, done, gamma, B, nets, w, dQ, loss, td_abs, zero, nzero, ws, ws_floats, stream,
+                     "td_loss_opt_nets", opt, huber_delta);
 }
 
 int evx_polyak(const float* p, float* t, int64_t n, float tau, float one_minus_tau, void* stream) {

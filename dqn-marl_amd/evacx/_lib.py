@@ -302,6 +302,10 @@ SIGNATURES = {
     "evx_qmlp_act_gb_plan_query": (C.c_int, [_LAY, _vp, _i32, _i32, *_NET, _vp, _P(evx_qmlp_fwd_plan)]),
     "evx_replay_push_blocks": (C.c_int, [_RING] + [_vp] * 6 + [_i32, _i32, _i32, _i64, _vp]),
     "evx_replay_sample_blocks": (C.c_int, [_RING, _i64, _i32, _i32, _u64, _u64] + [_vp] * 6),
+    "evx_replay_sample_nstep_blocks": (C.c_int, [_RING, _i64, _i32, _i32, _u64, _u64] + [_i64] * 3 + [_vp] * 11),
+    "evx_td_loss_opt_nets": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32, _i32] + [_vp] * 5 +
+                             [_i64, _vp, _i64, _OPTS, _vp, _vp]),
+    "evx_qmlp_polyak_pack3_g": (C.c_int, [_vp] * 13 + [_i32, _vp]),
     "evx_qmix_nparams": (C.c_int32, [_i32]),
     "evx_qmix_part_floats": (C.c_int64, [_i32, _i32]),
     "evx_qmix_loss": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32, _i32] + [_vp] * 7 + [_i64, _vp]),

@@ -16,6 +16,13 @@ exploration schedule and target period, and shares every launch with the others:
            GroupedLearner.learn_obs   forward pair, TD loss (gamma[k] per row: gamma_row), backward,
                                       clip + Adam with lr[k] (evx_qmlp_adam_pack3_gl): one launch per link
 
+The learner options are opt-in and per member but for Double-Q: n_step[k] > 1 anywhere turns the
+sample launch into evx_replay_sample_nstep_blocks (the draws and every member's chain in one launch);
+loss[k] = "huber" makes the TD launch evx_td_loss_opt_nets (delta[k] per net, 0 for "mse");
+target_tau[k] > 0 anywhere adds one evx_qmlp_polyak_pack3_g launch after the step (members with tau 0
+keep their hard copy every target_every[k]); double_q adds one evx_qmlp_act_gb launch on the batch's
+s2 blocks for the whole population.
+
 Member k's trajectory, batches and weights are those of a VecTrainer-style loop of its own -- one
 ``Learner``, one ``Replay``, ``MLPFast.act`` on its row block -- bit for bit (tests/pop_util.py
 ``SlowPopulation`` is that loop; DESIGN.md 5.5 holds the contract). No host syncs inside ``step()``.
@@ -29,17 +36,20 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from ._lib import OBS_WORDS, check, evx_replay, lib
+from ._lib import NSTEP_MAX, OBS_WORDS, check, evx_replay, lib
 from .env import _ptr, _stream
 
 MAX_MEMBERS = 64
 _HP = ("lr", "gamma", "epsilon", "epsilon_min", "epsilon_decay", "target_every")
+_OPT = ("loss", "huber_delta", "target_tau", "n_step")  # the learner options a member may set for itself
 
 
 def per_member(name: str, v, K: int) -> list:
     """A hyperparameter as a list of K values: a scalar is broadcast, a sequence must hold K.
     target_every: integers >= 1; epsilon / epsilon_min: finite, in [0, 1]; lr: finite, >= 0;
-    gamma / epsilon_decay: finite, in [0, 1]. ValueError naming the value otherwise."""
+    gamma / epsilon_decay: finite, in [0, 1]; loss: "mse" or "huber"; huber_delta: finite, > 0;
+    target_tau: finite, in [0, 1]; n_step: integers in 1..NSTEP_MAX (32). ValueError naming the value
+    otherwise."""
     vals = list(v) if isinstance(v, (list, tuple)) else [v] * K
     if len(vals) != K:
         raise ValueError(f"{name} must be a scalar or a sequence of members = {K} values, not {len(vals)}: {v!r}")
@@ -50,17 +60,33 @@ def per_member(name: str, v, K: int) -> list:
                 raise ValueError(f"target_every must be an integer >= 1, not {x!r}")
             out.append(x)
             continue
+        if name == "n_step":
+            if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= NSTEP_MAX:
+                raise ValueError(f"n_step must be an integer in 1..{NSTEP_MAX}, not {x!r}")
+            out.append(x)
+            continue
+        if name == "loss":
+            if x not in ("mse", "huber"):
+                raise ValueError(f"loss must be 'mse' or 'huber', not {x!r}")
+            out.append(x)
+            continue
         if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
             raise ValueError(f"{name} must be a finite number, not {x!r}")
+        if name == "huber_delta":
+            if x <= 0:
+                raise ValueError(f"huber_delta must be > 0, not {x!r}")
+            out.append(float(x))
+            continue
         if x < 0 or (name != "lr" and x > 1):
             raise ValueError(f"{name} must lie in " + ("[0, inf)" if name == "lr" else "[0, 1]") + f", not {x!r}")
         out.append(float(x))
     return out
 
 
-def validate_population(layout, E, members, batch, replay_capacity, learn_every=1) -> int:
+def validate_population(layout, E, members, batch, replay_capacity, learn_every=1, n_step=1) -> int:
     """The constructor's refusals that need no device (ValueError naming the value); returns
-    N = (E / members) * R, the rows a member owns."""
+    N = (E / members) * R, the rows a member owns. n_step (a scalar or members values): a member's
+    ring must hold n_step[k] pushes of N rows, or no chain of its could reach that depth."""
     from .env import LayoutSet
     if isinstance(layout, LayoutSet):
         raise ValueError("PopulationTrainer: one DeviceLayout, not a LayoutSet")
@@ -79,6 +105,10 @@ def validate_population(layout, E, members, batch, replay_capacity, learn_every=
         raise ValueError(f"replay_capacity must hold a member's push of {N} rows and a batch of {batch}, not {C_!r}")
     if isinstance(learn_every, bool) or not isinstance(learn_every, int) or learn_every < 1:
         raise ValueError(f"learn_every must be an integer >= 1, not {learn_every!r}")
+    for n in per_member("n_step", n_step, K):
+        if n * N > C_:
+            raise ValueError(f"n_step = {n} needs a replay_capacity of at least n_step * N = {n * N} slots "
+                             f"({n} pushes of {N} rows), not {C_!r}")
     return N
 
 
@@ -124,27 +154,70 @@ class BlockReplay:
                                              out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
                                              out["done"].data_ptr(), _stream()), "replay_sample_blocks")
 
+    def live_range(self):
+        """(base, count) of every ring in push order, oldest first: ((pos - size) mod C, size)."""
+        return (self.pos - self.size) % self.capacity, self.size
+
+    def sample_nstep(self, B, seed, offset, n_step, gamma, stride, out):
+        """sample()'s draws, each followed by ring k's n-step chain of depth n_step[k] under gamma[k]
+        over the live range, stride rows pushed per env step (evx_replay_sample_nstep_blocks, one
+        launch): out["s"] / out["a"] the drawn slot's, out["r"] the discounted return, out["s2"] /
+        out["done"] the chain's last slot's, out["gamma_row"] = gamma[k]^L; out["nlen"] (int32, L) and
+        out["idx"] (int64, the drawn ring-local slot) are optional. Trainer.Replay.sample + .nstep
+        of every ring, bit for bit."""
+        if len(n_step) != self.K or len(gamma) != self.K:
+            raise ValueError(f"BlockReplay.sample_nstep: n_step and gamma must hold {self.K} values")
+        for name, per in (("s", OBS_WORDS), ("s2", OBS_WORDS), ("a", 1), ("r", 1), ("done", 1), ("gamma_row", 1),
+                          ("nlen", 1), ("idx", 1)):
+            t = out.get(name)
+            if t is None and name in ("nlen", "idx"):
+                continue
+            if t.numel() < self.K * B * per:
+                raise ValueError(f"BlockReplay.sample_nstep: out[{name!r}] holds {t.numel() // per} rows, "
+                                 f"needs {self.K * B}")
+        base, count = self.live_range()
+        ns = (C.c_int32 * self.K)(*[int(n) for n in n_step])
+        gm = (C.c_float * self.K)(*[float(g) for g in gamma])
+        check(lib().evx_replay_sample_nstep_blocks(C.byref(self.c), self.size, B, self.K, seed, offset, base, count,
+                                                   stride, ns, gm, out["s"].data_ptr(), out["s2"].data_ptr(),
+                                                   out["a"].data_ptr(), out["r"].data_ptr(), out["done"].data_ptr(),
+                                                   out["gamma_row"].data_ptr(), _ptr(out.get("nlen")),
+                                                   _ptr(out.get("idx")), _stream()), "replay_sample_nstep_blocks")
+
 
 class PopulationTrainer:
     def __init__(self, layout, E: int, members: int, seed_base: int = 1234, seed: int = 0,
                  init_seeds: Optional[Sequence[int]] = None, batch: int = 4096, replay_capacity: int = 1 << 18,
                  lr=1e-4, gamma=0.99, epsilon=1.0, epsilon_min=0.02, epsilon_decay=0.9995, target_every=1000,
-                 learn_every: int = 1, episode_stats: bool = False, learn_stats: bool = False):
+                 learn_every: int = 1, episode_stats: bool = False, learn_stats: bool = False,
+                 double_q: bool = False, loss="mse", huber_delta=1.0, target_tau=0.0, n_step=1):
         """members = K learners over E envs of one DeviceLayout (E / K each); batch = B rows per member
         and learn step; replay_capacity = C slots per member. lr, gamma, epsilon, epsilon_min,
         epsilon_decay and target_every: a scalar, or a sequence of K values (per_member).
+        loss ("mse" / "huber"), huber_delta, target_tau and n_step: the learner options of
+        evacx.qnet.Learner and VecTrainer, each a scalar or a sequence of K values (per_member). A
+        member with target_tau[k] > 0 blends its target after every learn step and takes no hard copy;
+        a member with n_step[k] > 1 learns on returns of up to n_step[k] rewards along its own ring
+        (the ring must hold n_step[k] pushes). double_q is one bool for the whole population: the
+        selection forward is one launch for all members and LearnStats reads one sel buffer, and it
+        fixes the dropout stream numbering (3 per learn step instead of 2), so it cannot change
+        later either (per-member Double-Q: not built). With every option at its default nothing
+        more is allocated or launched than without them.
         init_seeds[k] (default seed + k): member k starts from Learner(seed=init_seeds[k])'s weights.
         seed keys the dropout hash, the epsilon draws (seed * 7919 + 17) and the replay draws
         (seed * 7919 + 18); env e is seeded seed_base + e. episode_stats / learn_stats: EpisodeStats
         grouped by member / LearnStats(K) for episode_summary() / learn_summary(); off: nothing is
         allocated or launched for them. The net is the x3 MLP; one GPU, strict schedule, uniform
         replay, no act table."""
-        N = validate_population(layout, E, members, batch, replay_capacity, learn_every)
+        N = validate_population(layout, E, members, batch, replay_capacity, learn_every, n_step)
         K = members
         hp = dict(lr=lr, gamma=gamma, epsilon=epsilon, epsilon_min=epsilon_min, epsilon_decay=epsilon_decay,
-                  target_every=target_every)
-        for name in _HP:
+                  target_every=target_every, loss=loss, huber_delta=huber_delta, target_tau=target_tau, n_step=n_step)
+        for name in _HP + _OPT:
             setattr(self, name, per_member(name, hp[name], K))
+        if not isinstance(double_q, bool):
+            raise ValueError(f"double_q must be a bool (one for the whole population), not {double_q!r}")
+        self.double_q = double_q
         if init_seeds is not None and len(init_seeds) != K:
             raise ValueError(f"init_seeds must hold members = {K} seeds, not {len(init_seeds)}")
         from .env import VecEnv
@@ -199,17 +272,39 @@ class PopulationTrainer:
         if self.replay.size < self.batch:
             return None
         K, B, sp, gl = self.K, self.batch, self.samp, self.glearner
-        self.replay.sample(B, self.sample_seed, self.learn_steps * K * B, sp)
-        loss = gl.learn_obs(self.lay.c, sp["s"], sp["a"], sp["r"], sp["done"], sp["s2"], B, gamma_row=self.gamma_row,
-                            lr=self.lr)
+        grow = self.gamma_row
+        if any(n > 1 for n in self.n_step):  # the sampler follows every member's chain in its own launch
+            if "gamma_row" not in sp:
+                sp.update(gamma_row=torch.zeros(K * B, dtype=torch.float32, device=self.device),
+                          nlen=torch.zeros(K * B, dtype=torch.int32, device=self.device))
+            self.replay.sample_nstep(B, self.sample_seed, self.learn_steps * K * B, self.n_step, self.gamma, self.N, sp)
+            grow = sp["gamma_row"]
+        else:
+            self.replay.sample(B, self.sample_seed, self.learn_steps * K * B, sp)
+        opts = {}
+        if self.double_q:
+            opts["double_q"] = True
+        if any(ls == "huber" for ls in self.loss):  # a member's kernel delta is 0 for "mse"
+            opts["huber_delta"] = [d if ls == "huber" else 0.0 for ls, d in zip(self.loss, self.huber_delta)]
+        loss = gl.learn_obs(self.lay.c, sp["s"], sp["a"], sp["r"], sp["done"], sp["s2"], B, gamma_row=grow, lr=self.lr,
+                            **opts)
         self.learn_steps += 1
         for k in range(K):
             if self.epsilon[k] > self.epsilon_min[k]:  # DQNAgent.learn's schedule (agents/dqn_agent.py:163-164)
                 self.epsilon[k] *= self.epsilon_decay[k]
-        due = [k for k in range(K) if self.learn_steps % self.target_every[k] == 0]
+        # a soft member blends after every learn step and takes no hard copy (VecTrainer's target_tau)
+        due = [k for k in range(K) if self.target_tau[k] == 0 and self.learn_steps % self.target_every[k] == 0]
         if due:
             gl.sync_target(due)
+        if any(t > 0 for t in self.target_tau):
+            gl.soft_update(self.target_tau)
         return loss
+
+    @property
+    def last_nlen(self):
+        """The chain length of every row of the last n-step learn step: int32 [K B] on the device
+        (read it after a synchronize); None before the first such step."""
+        return self.samp.get("nlen")
 
     def step(self):
         """One training step of every member on the current stream: act, env.step (auto-reset),
@@ -253,13 +348,17 @@ class PopulationTrainer:
         return k
 
     def set_hparams(self, k: int, **hp):
-        """Change member k's lr, gamma, epsilon, epsilon_min, epsilon_decay or target_every from the
-        next step on (the values are checked as the constructor's)."""
+        """Change member k's lr, gamma, epsilon, epsilon_min, epsilon_decay, target_every, loss,
+        huber_delta, target_tau or n_step from the next step on (the values are checked as the
+        constructor's). double_q is fixed at construction: it fixes the dropout stream numbering."""
         k = self._member(k)
         for name in hp:
-            if name not in _HP:
-                raise ValueError(f"set_hparams: unknown hyperparameter {name!r} (one of {', '.join(_HP)})")
+            if name not in _HP + _OPT:
+                raise ValueError(f"set_hparams: unknown hyperparameter {name!r} (one of {', '.join(_HP + _OPT)})")
         new = {name: per_member(name, v, 1)[0] for name, v in hp.items()}
+        if "n_step" in new and new["n_step"] * self.N > self.replay.capacity:
+            raise ValueError(f"n_step = {new['n_step']} needs a replay_capacity of at least n_step * N = "
+                             f"{new['n_step'] * self.N} slots, not {self.replay.capacity}")
         for name, v in new.items():
             getattr(self, name)[k] = v
         if "gamma" in new:  # (a fill on the current stream, after the learn steps launched so far)
@@ -278,13 +377,16 @@ class PopulationTrainer:
         gl.fast_t.nets[dst].repack()
 
     def member_learner(self, k: int):
-        """An evacx.qnet.Learner holding member k's online and target weights, Adam moments and
-        hyperparameters (a copy: for evacx.evaluate.evaluate and checkpoints)."""
+        """An evacx.qnet.Learner holding member k's online and target weights, Adam moments,
+        hyperparameters and learner options (a copy: for evacx.evaluate.evaluate and checkpoints)."""
         from .qnet import Learner
         k = self._member(k)
         gl = self.glearner
+        tau = self.target_tau[k]
         lr = Learner(kind="mlp", device=self.device, lr=self.lr[k], gamma=self.gamma[k], precision="f32",
-                     seed=self.init_seeds[k])
+                     seed=self.init_seeds[k], double_q=self.double_q, loss=self.loss[k],
+                     huber_delta=self.huber_delta[k], target_tau=tau if tau < 1.0 else 0.0)
+        lr.target_tau = tau  # (Learner's constructor stops short of 1, the copy every step; its kernel takes it)
         lr.online.flat.copy_(gl.flat[k])
         lr.target.flat.copy_(gl.tflat[k])
         lr.m.copy_(gl.m[k])

@@ -29,7 +29,7 @@ import torch
 
 from ._lib import check, evx_adam, evx_qmlp_fwd_out, evx_qmlp_fwd_plan, evx_qmlp_grads, evx_qmlp_plan, lib
 from .env import _stream
-from .qmlp import HID, HID2, K1X, NACT, MLPFast, _need, td_opts
+from .qmlp import HID, HID2, K1X, NACT, MLPFast, _need, polyak_coeffs, td_opts
 from .qnet import DROPOUT_P, FlatParams, layer_specs, param_shapes
 
 
@@ -76,6 +76,7 @@ class GroupedLearner:
             raise ValueError(f"GroupedLearner: stats must be a LearnStats of {nets} nets and A = {NACT}")
         self.stats = stats
         self.stat_batch = None  # stats: (Q, Qt, a, r, done, sel, gamma_row, B) of the last learn_obs
+        self.last_sel = None  # learn_obs(double_q=True): the last step's bootstrap actions (int32 [G B])
         self.G, self.device = int(nets), torch.device(device)
         self.shapes = param_shapes(layer_specs("mlp"))
         self.npar = sum(int(torch.Size(s).numel()) for s in self.shapes.values())
@@ -164,17 +165,26 @@ class GroupedLearner:
         return plan
 
     # ---------------------------------------------------------------- learn
-    def learn_obs(self, lay_c, s_obs, a, r, done, s2_obs, B: int, update: bool = True, gamma_row=None, lr=None):
+    def learn_obs(self, lay_c, s_obs, a, r, done, s2_obs, B: int, update: bool = True, gamma_row=None, lr=None,
+                  double_q: bool = False, huber_delta=None):
         """One DQNAgent.learn step of every net: net g's batch is rows [g B, (g + 1) B) of s_obs /
         a / r / done / s2_obs. Returns the per-net losses [G] (device, no host sync).
         gamma_row: device f32 [G B], the discount of every row in place of gamma (evx_td_loss_opt;
         evacx.population: gamma[g] on every row of block g); lr: step_optimizer's. None: the
-        entries and the bits of a call without them."""
+        entries and the bits of a call without them.
+        double_q: the target bootstraps from the target net's value of the online net's greedy action
+        at s2 -- one more launch, act_blocks on s2_obs with every epsilon 0 on dropout stream
+        drop_stream + 2 (rows g B + i), before the forward pair; the actions stay in last_sel (int32
+        [G B]) and drop_stream advances by 3 instead of 2, as evacx.qnet.Learner(double_q=True)'s.
+        huber_delta: a sequence of G values, net g's Huber delta (0: its squared error;
+        evx_td_loss_opt_nets). Both off: the launches, stream numbers and bits of a call without them."""
         G = self.G
         if B <= 0 or B % 2:
             raise ValueError("learn_obs: B must be even and > 0")
         if gamma_row is not None and (gamma_row.dtype != torch.float32 or gamma_row.numel() < G * B):
             raise ValueError(f"learn_obs: gamma_row must be a float32 tensor of at least G B = {G * B} elements")
+        if huber_delta is not None and len(huber_delta) != G:
+            raise ValueError(f"learn_obs: huber_delta must hold {G} values, not {len(huber_delta)}")
         for name, t, w in (("s_obs", s_obs, 8), ("s2_obs", s2_obs, 8), ("a", a, 1), ("r", r, 1), ("done", done, 1)):
             _need("learn_obs " + name, t, G * B, w)
         X = self._buf("x", G * B * K1X, torch.int16)
@@ -183,7 +193,13 @@ class GroupedLearner:
         Q = self._buf("q", G * B * NACT, torch.float32)
         H1t = self._buf("h1t", G * 2 * B * HID, torch.int16)
         Qt = self._buf("qt", G * B * NACT, torch.float32)
-        self.drop_stream += 2
+        self.drop_stream += 3 if double_q else 2
+        sel = None
+        if double_q:  # the online nets' greedy actions at s2 (train mode, as every forward of learn)
+            sel = self._buf("sel", G * B, torch.int32)
+            self.act_blocks(lay_c, s2_obs, B, [0.0] * G, actions=sel, drop_p=self.drop_p,
+                            drop_stream=self.drop_stream + 2)
+            self.last_sel = sel
         d_on = MLPFast._drop((self.seed, self.drop_stream, self.drop_p))
         d_tg = MLPFast._drop((self.seed, self.drop_stream + 1, self.drop_p))
         o_on = MLPFast._out(H1, X, H2, Q)
@@ -193,7 +209,21 @@ class GroupedLearner:
                                         C.byref(o_tg), _stream()), "qmlp_forward2_g")
         dQ = self._buf("dq", G * B * NACT, torch.float32)
         tw = self._buf("td_ws", max(1, int(lib().evx_td_loss_ws_floats(B, G))), torch.float32)
-        if gamma_row is None:
+        if huber_delta is not None:
+            o = td_opts(sel=sel, gamma_row=gamma_row)
+            deltas = (C.c_float * G)(*[float(x) for x in huber_delta])
+            check(lib().evx_td_loss_opt_nets(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(),
+                                             done.data_ptr(), self.gamma, B, G, None, dQ.data_ptr(),
+                                             self.loss.data_ptr(), None, self.gflat.data_ptr(), self.gflat.numel(),
+                                             tw.data_ptr(), tw.numel(), C.byref(o), deltas, _stream()),
+                  "td_loss_opt_nets")
+        elif sel is not None:
+            o = td_opts(sel=sel, gamma_row=gamma_row)
+            check(lib().evx_td_loss_opt(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(), done.data_ptr(),
+                                        self.gamma, B, G, None, dQ.data_ptr(), self.loss.data_ptr(), None,
+                                        self.gflat.data_ptr(), self.gflat.numel(), tw.data_ptr(), tw.numel(),
+                                        C.byref(o), _stream()), "td_loss_opt")
+        elif gamma_row is None:
             check(lib().evx_td_loss_zero_g(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(),
                                            done.data_ptr(), self.gamma, B, G, None, dQ.data_ptr(),
                                            self.loss.data_ptr(), None, self.gflat.data_ptr(), self.gflat.numel(),
@@ -205,7 +235,7 @@ class GroupedLearner:
                                         self.gflat.data_ptr(), self.gflat.numel(), tw.data_ptr(), tw.numel(),
                                         C.byref(o), _stream()), "td_loss_opt")
         if self.stats is not None:
-            self.stat_batch = (Q, Qt, a, r, done, None, gamma_row, B)
+            self.stat_batch = (Q, Qt, a, r, done, sel, gamma_row, B)
         self._backward(B, dQ, X, H1, H2)
         if update:
             self.step_optimizer(lr=lr)
@@ -254,6 +284,22 @@ class GroupedLearner:
         for g in (range(self.G) if nets is None else nets):
             self.tflat[g].copy_(self.flat[g])
             self.fast_t.nets[g].repack()
+
+    def soft_update(self, taus):
+        """Polyak target update of every net in one launch (evx_qmlp_polyak_pack3_g): net g's target =
+        taus[g] * online + (1 - taus[g]) * target with its operand repack, as
+        evacx.qnet.Learner.soft_update; a net with taus[g] = 0 keeps its target bit for bit."""
+        if len(taus) != self.G:
+            raise ValueError(f"soft_update: taus must hold {self.G} values, not {len(taus)}")
+        co = [polyak_coeffs(t) for t in taus]
+        tau = (C.c_float * self.G)(*[c[0] for c in co])
+        omt = (C.c_float * self.G)(*[c[1] for c in co])
+        b = self.fast_t.bufs
+        check(lib().evx_qmlp_polyak_pack3_g(self.flat.data_ptr(), self.tflat.data_ptr(), tau, omt, b["w1b"].data_ptr(),
+                                            b["w1l"].data_ptr(), b["b1c"].data_ptr(), b["w2b"].data_ptr(),
+                                            b["w2l"].data_ptr(), b["w2t"].data_ptr(), b["w2tl"].data_ptr(),
+                                            b["w1o"].data_ptr(), b["w1ol"].data_ptr(), self.G, _stream()),
+              "qmlp_polyak_pack3_g")
 
     def state_dict(self, g: int):
         """Net g's parameters in DQNNetwork's state_dict order (evacx.qnet.FlatParams)."""

@@ -875,6 +875,42 @@ int evx_replay_push_blocks(const evx_replay *rp, const evx_obs *s, const evx_obs
 int evx_replay_sample_blocks(const evx_replay *rp, int64_t size, int32_t B, int32_t nets, uint64_t seed,
                              uint64_t offset, evx_obs *s, evx_obs *s2, int32_t *a, float *r, uint8_t *done,
                              void *stream);
+/* The population's learner options: each member its own n-step depth, Huber delta and Polyak rate
+ * (host arrays [nets], passed to the kernels by value as evx_qmlp_act_gb's epsilons are).
+ * evx_replay_sample_nstep_blocks: evx_replay_sample_blocks and evx_replay_nstep in one launch. Row
+ * k B + i draws ring k's slot j0 as evx_replay_sample_blocks does, takes s and a from it and follows
+ * evx_replay_nstep's chain on ring k with n_step[k] and gamma[k] over the live range [base, base +
+ * count) mod capacity (common to the rings; successor of slot j: (j + stride) mod capacity): r = the
+ * discounted return, s2 / done = the chain's last slot's, gamma_row = gamma[k]^L, len = L (int32
+ * [nets][B], may be NULL), idx_out = j0 (int64 [nets][B], ring-local, may be NULL). All f32, R + g r
+ * a multiply and an add. Every n_step = 1: evx_replay_sample_blocks bit for bit, gamma_row = gamma[k],
+ * len = 1. A stride beyond the ring is taken as the capacity (no successor lies inside the range).
+ * -22 before any launch: a NULL required pointer, nets outside 1..64, B odd, size outside
+ * [1, capacity], B > size, count outside [0, capacity], base outside [0, capacity), stride < 1, an
+ * n_step outside 1..EVX_NSTEP_MAX, a gamma that is not finite. */
+int evx_replay_sample_nstep_blocks(const evx_replay *rp, int64_t size, int32_t B, int32_t nets, uint64_t seed,
+                                   uint64_t offset, int64_t base, int64_t count, int64_t stride,
+                                   const int32_t *n_step, const float *gamma, evx_obs *s, evx_obs *s2, int32_t *a,
+                                   float *r, uint8_t *done, float *gamma_row, int32_t *len, int64_t *idx_out,
+                                   void *stream);
+/* evx_td_loss_opt with a Huber delta per net: huber_delta [nets] on the host (0: that net's squared
+ * error) in place of opt->huber_delta, which is not read; opt may be NULL (no sel, no gamma_row).
+ * Equal deltas give evx_td_loss_opt bit for bit. -22 before any launch: a NULL required pointer,
+ * nets outside 1..64, a delta that is negative or not finite, and what evx_td_loss_opt refuses. */
+int evx_td_loss_opt_nets(const float *Q, const float *Qt, int32_t A, const int32_t *act, const float *rew,
+                         const uint8_t *done, float gamma, int32_t B, int32_t nets, const float *w, float *dQ,
+                         float *loss, float *td_abs, float *zero, int64_t nzero, float *ws, int64_t ws_floats,
+                         const evx_td_opts *opt, const float *huber_delta, void *stream);
+/* evx_qmlp_polyak_pack3 of every net in one launch: p / t [nets][evx_qmlp_nparams()], the operand
+ * buffers in the [nets] layout above; tau / one_minus_tau [nets] on the host (one_minus_tau[g] =
+ * (float)(1.0 - (double)tau[g])). Net g with tau[g] = 0 is skipped: its target parameters and
+ * operand buffers keep their bits, so members with a hard target copy and members with a soft one
+ * share the launch. Per net evx_qmlp_polyak_pack3 bit for bit. -22 before any launch: a NULL
+ * required pointer, nets outside 1..64, a tau outside [0, 1], a one_minus_tau that is not finite,
+ * w1o / w1ol or w2t / w2tl given singly. */
+int evx_qmlp_polyak_pack3_g(const float *p, float *t, const float *tau, const float *one_minus_tau, uint16_t *w1b,
+                            uint16_t *w1l, float *b1c, uint16_t *w2b, uint16_t *w2l, uint16_t *w2t, uint16_t *w2tl,
+                            uint16_t *w1o, uint16_t *w1ol, int32_t nets, void *stream);
 
 /* ---- QMIX mixer (runners/train_qmix.py:39-54 MixingNetwork, loss :78-104) for n <= 16 agents:
  * Q / Qt [n][B][A] (evx_qmlp_forward2_g), act [n][B], rew / done [B]; mix / mix_t the online /

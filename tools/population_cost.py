@@ -15,6 +15,8 @@ per shape: ms per step of each variant per block, the means, the block min-max, 
 
   python3 tools/population_cost.py                      # cfg2: 8 x 4096 envs, B = 4096
   python3 tools/population_cost.py --members 4 --steps 200 --rounds 6
+  python3 tools/population_cost.py --variants options   # the learner options' price list
+  python3 tools/population_cost.py --variants population  # (a) alone: one build or commit against another
 """
 import argparse
 import json
@@ -84,21 +86,31 @@ def child(args, name):
     cap = capacity_for(E, R)
     lrs = [LRS[k % len(LRS)] for k in range(K)]
     gammas = [GAMMAS[(k // len(LRS)) % len(GAMMAS)] for k in range(K)]
-    trs = {
-        "population": [age(PopulationTrainer(lay, K * E, members=K, batch=E, replay_capacity=cap, lr=lrs, gamma=gammas),
-                           K * E, R, args.age_steps, args.stagger)],
-        "separate": [age(VecTrainer(lay, E, batch=E, replay_capacity=cap, act_table=False, lr=lrs[k], gamma=gammas[k],
-                                    learner_seed=k, seed_base=1234 + k * E), E, R, args.age_steps, args.stagger)
-                     for k in range(K)],
-        "one": [age(VecTrainer(lay, K * E, batch=E, replay_capacity=capacity_for(K * E, R)), K * E, R, args.age_steps,
-                    args.stagger)],
-    }
+    def pop(**opts):
+        return [age(PopulationTrainer(lay, K * E, members=K, batch=E, replay_capacity=cap, lr=lrs, gamma=gammas, **opts),
+                    K * E, R, args.age_steps, args.stagger)]
+    if args.variants == "options":  # the price list of the learner options: four populations of one shape
+        soft = dict(double_q=True, loss="huber", huber_delta=1.0, target_tau=0.005)
+        trs = {"population": pop(), "double_q": pop(double_q=True), "double_q_huber_tau": pop(**soft),
+               "double_q_huber_tau_nstep3": pop(n_step=3, **soft)}
+    elif args.variants == "population":  # variant (a) alone (two builds or two commits against each other)
+        trs = {"population": pop()}
+    else:
+        trs = {
+            "population": pop(),
+            "separate": [age(VecTrainer(lay, E, batch=E, replay_capacity=cap, act_table=False, lr=lrs[k],
+                                        gamma=gammas[k], learner_seed=k, seed_base=1234 + k * E), E, R, args.age_steps,
+                             args.stagger) for k in range(K)],
+            "one": [age(VecTrainer(lay, K * E, batch=E, replay_capacity=capacity_for(K * E, R)), K * E, R,
+                        args.age_steps, args.stagger)],
+        }
     names = list(trs)
     for k in names:
         block(trs[k], args.warmup)
     ms = {k: [] for k in names}
     for r in range(args.rounds):  # alternate, and rotate who goes first
-        for k in names[r % 3:] + names[:r % 3]:
+        o = r % len(names)
+        for k in names[o:] + names[:o]:
             ms[k].append(block(trs[k], args.steps))
     for group in trs.values():
         for tr in group:
@@ -110,9 +122,13 @@ def child(args, name):
                ms_per_step={k: [round(x, 4) for x in v] for k, v in ms.items()},
                mean={k: round(v, 4) for k, v in mean.items()},
                min={k: round(min(v), 4) for k, v in ms.items()}, max={k: round(max(v), 4) for k, v in ms.items()},
-               population_over_separate=round(mean["population"] / mean["separate"], 4),
                env_steps_per_s={k: round(K * E / (mean[k] * 1e-3)) for k in names},
-               device=torch.cuda.get_device_name(0))
+               variants=args.variants, device=torch.cuda.get_device_name(0))
+    if "separate" in mean:
+        out["population_over_separate"] = round(mean["population"] / mean["separate"], 4)
+    if args.variants == "options":  # per round: what each option set adds to the population's step
+        out["over_population_ms"] = {k: [round(x - y, 4) for x, y in zip(ms[k], ms["population"])]
+                                     for k in names if k != "population"}
     print(json.dumps(out), flush=True)
 
 
@@ -126,6 +142,9 @@ def main():
     ap.add_argument("--age-steps", type=int, default=1300)
     ap.add_argument("--stagger", type=int, default=1200)
     ap.add_argument("--limit", type=float, default=600.0, help="seconds a shape's child process may take")
+    ap.add_argument("--variants", choices=["base", "options", "population"], default="base",
+                    help="base: (a) / (b) / (c) above; options: the population with its learner options off, with "
+                         "double_q, + Huber + target_tau 0.005 on every member, + n_step 3; population: (a) alone")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
@@ -140,7 +159,8 @@ def main():
         # time ends the tool: nothing more is started on the device
         cmd = [sys.executable, os.path.abspath(__file__), "--child", name] + \
               [a for k, v in (("--members", args.members), ("--steps", args.steps), ("--rounds", args.rounds),
-                              ("--warmup", args.warmup), ("--age-steps", args.age_steps), ("--stagger", args.stagger))
+                              ("--warmup", args.warmup), ("--age-steps", args.age_steps), ("--stagger", args.stagger),
+                              ("--variants", args.variants))
                for a in (k, str(v))]
         try:
             rc = subprocess.call(cmd, timeout=args.limit)
