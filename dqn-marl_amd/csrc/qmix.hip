@@ -16,11 +16,18 @@
 // (state_dict order: fc1_weight [n][32], fc1_bias [32], fc2_weight [32][1], fc2_bias [1]) and
 // the loss. Extra workgroups of the rows launch clear the agents' gradient buffer, as
 // td_loss_zero does for one net.
+//
+// evx_qmix_loss_opt: the same rows kernel with the TD options compiled in (qmix_rows_kernel<true>):
+// the bootstrap action of every agent given (sel, Double-Q: the online nets' greedy actions at s2)
+// in place of the target nets' maximum, a discount per joint row (gamma_row: n-step rows), the Huber
+// loss on q_tot - y, and |q_tot - y| per row (td_abs). qmix_rows_kernel<false> is evx_qmix_loss's
+// instantiation; the staging layout, the parameter sums and the reduce are common to both.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "evacx.h"
 #include "evx_host.h"
@@ -32,13 +39,22 @@ constexpr int NMAX = 16;  // agents per launch
 constexpr int ROWS = 256;
 __host__ __device__ constexpr int mix_params(int n) { return n * EMB + EMB + EMB + 1; }
 
+// evx_qmix_loss_opt's options, by value (all NULL / 0: the plain loss)
+struct MixOpts {
+    const int32_t* sel;      // [n][B] or NULL
+    const float* gamma_row;  // [B] or NULL
+    float delta;             // Huber delta, 0: squared error
+    float* td_abs;           // [B] or NULL
+};
+
 // per-row factors staged for the parameter sums: q_i (n), dh_j (32), hid_j (32), dqt
+template <bool OPT>
 __global__ __launch_bounds__(ROWS) void qmix_rows_kernel(const float* __restrict__ Q, const float* __restrict__ Qt, int A,
                                                          const int32_t* __restrict__ act, const float* __restrict__ rew,
                                                          const uint8_t* __restrict__ done, float gamma, int B, int n,
                                                          const float* __restrict__ mix, const float* __restrict__ mix_t,
                                                          float* __restrict__ dQ, float* __restrict__ part, int nrow_blocks,
-                                                         float* __restrict__ zero, int64_t nzero) {
+                                                         float* __restrict__ zero, int64_t nzero, MixOpts mo) {
     if ((int)blockIdx.x >= nrow_blocks) {  // clear the agents' gradients for the grouped backward
         const int64_t z0 = ((int64_t)blockIdx.x - nrow_blocks) * ROWS + threadIdx.x;
         const int64_t zs = ((int64_t)gridDim.x - nrow_blocks) * ROWS;
@@ -66,6 +82,10 @@ __global__ __launch_bounds__(ROWS) void qmix_rows_kernel(const float* __restrict
             const size_t r = (size_t)i * B + b;
             a[i] = act[r];
             q[i] = Q[r * A + a[i]];  // q_network(s).gather(1, a)
+            if (OPT && mo.sel) {  // Double-Q: the target's value of the given action (clamped into the row)
+                qt[i] = Qt[r * A + min(max(mo.sel[r], 0), A - 1)];
+                continue;
+            }
             float mx = Qt[r * A];
             for (int j = 1; j < A; j++) mx = fmaxf(mx, Qt[r * A + j]);  // target_network(s').max(1)[0]
             qt[i] = mx;
@@ -79,7 +99,9 @@ __global__ __launch_bounds__(ROWS) void qmix_rows_kernel(const float* __restrict
             tot_t += (pre > 0.f ? pre : 0.f) * fabsf(tw2[j]);
         }
         tot_t += tb2;
-        const float y = rew[b] + gamma * tot_t * (done[b] ? 0.f : 1.f);
+        // gamma_row (n-step rows): the joint row's own discount gamma^L
+        const float gm = (OPT && mo.gamma_row) ? mo.gamma_row[b] : gamma;
+        const float y = rew[b] + gm * tot_t * (done[b] ? 0.f : 1.f);
         // online mixer
         float hid[EMB];
         float tot = 0.f;
@@ -93,7 +115,15 @@ __global__ __launch_bounds__(ROWS) void qmix_rows_kernel(const float* __restrict
         tot += b2;
         const float d = tot - y;
         lossv = d * d;
-        const float dqt = 2.f * d / (float)B;  // mse_loss(mean) backward
+        float dqt = 2.f * d / (float)B;  // mse_loss(mean) backward
+        if (OPT) {
+            if (mo.delta > 0.f) {  // Huber: quadratic within delta, linear beyond; the gradient clamped
+                const float ad = fabsf(d), delta = mo.delta;
+                lossv = ad <= delta ? 0.5f * (d * d) : delta * (ad - 0.5f * delta);
+                dqt = fminf(fmaxf(d, -delta), delta) / (float)B;
+            }
+            if (mo.td_abs) mo.td_abs[b] = fabsf(d);
+        }
         float dq[NMAX];
         for (int i = 0; i < n; i++) dq[i] = 0.f;
         for (int j = 0; j < EMB; j++) {
@@ -159,7 +189,36 @@ __global__ __launch_bounds__(256) void qmix_reduce_kernel(const float* __restric
 }  // namespace evxx
 
 namespace {
-using evxh::fail;
+using evxh::failf;
+
+// the checks and the two launches of evx_qmix_loss / evx_qmix_loss_opt
+template <bool OPT>
+int qmix_launch(const char* who, const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew,
+                const uint8_t* done, float gamma, int32_t B, int32_t n, const float* mix, const float* mix_t,
+                float* dQ, float* mix_grad, float* loss, float* part, float* zero, int64_t nzero, evxx::MixOpts mo,
+                void* stream) {
+    if (B <= 0) return 0;
+    if (n < 1 || n > evxx::NMAX) return failf(-22, "%s: 1..16 agents", who);
+    if (A < 1 || A > 64) return failf(-22, "%s: 1..64 actions", who);
+    if (!Q || !Qt || !act || !rew || !done || !mix || !mix_t || !dQ || !mix_grad || !loss || !part)
+        return failf(-22, "%s: NULL argument", who);
+    if (OPT && !(std::isfinite(mo.delta) && mo.delta >= 0.f))
+        return failf(-22, "%s: huber_delta must be finite and >= 0", who);
+    if (OPT && !std::isfinite(gamma)) return failf(-22, "%s: gamma must be finite", who);
+    const int nrb = (B + evxx::ROWS - 1) / evxx::ROWS;
+    const int nz = zero && nzero > 0 ? (int)std::min<int64_t>((nzero + 256 * 16 - 1) / (256 * 16), 512) : 0;
+    const size_t lds = (size_t)evxx::ROWS * (n + 2 * evxx::EMB + 2) * 4;
+    {
+        static std::atomic<uint64_t> attr_done;
+        const void* ks[1] = {(const void*)evxx::qmix_rows_kernel<OPT>};
+        evxh::max_lds_once(attr_done, ks, 1, 160 * 1024);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(evxx::qmix_rows_kernel<OPT>, dim3(nrb + nz), dim3(evxx::ROWS), lds, st, Q, Qt, A, act, rew, done,
+                       gamma, B, n, mix, mix_t, dQ, part, nrb, nz ? zero : nullptr, nzero, mo);
+    hipLaunchKernelGGL(evxx::qmix_reduce_kernel, dim3(1), dim3(256), 0, st, part, nrb, n, B, mix, mix_grad, loss);
+    return evxh::hip_status(who);
+}
 }  // namespace
 
 extern "C" {
@@ -176,24 +235,23 @@ int64_t evx_qmix_part_floats(int32_t B, int32_t n) {
 int evx_qmix_loss(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew, const uint8_t* done,
                   float gamma, int32_t B, int32_t n, const float* mix, const float* mix_t, float* dQ, float* mix_grad,
                   float* loss, float* part, float* zero, int64_t nzero, void* stream) {
-    if (B <= 0) return 0;
-    if (n < 1 || n > evxx::NMAX) return fail(-22, "qmix_loss: 1..16 agents");
-    if (A < 1 || A > 64) return fail(-22, "qmix_loss: 1..64 actions");
-    if (!Q || !Qt || !act || !rew || !done || !mix || !mix_t || !dQ || !mix_grad || !loss || !part)
-        return fail(-22, "qmix_loss: NULL argument");
-    const int nrb = (B + evxx::ROWS - 1) / evxx::ROWS;
-    const int nz = zero && nzero > 0 ? (int)std::min<int64_t>((nzero + 256 * 16 - 1) / (256 * 16), 512) : 0;
-    const size_t lds = (size_t)evxx::ROWS * (n + 2 * evxx::EMB + 2) * 4;
-    {
-        static std::atomic<uint64_t> attr_done;
-        const void* ks[1] = {(const void*)evxx::qmix_rows_kernel};
-        evxh::max_lds_once(attr_done, ks, 1, 160 * 1024);
+    return qmix_launch<false>("qmix_loss", Q, Qt, A, act, rew, done, gamma, B, n, mix, mix_t, dQ, mix_grad, loss, part,
+                              zero, nzero, evxx::MixOpts{}, stream);
+}
+
+int evx_qmix_loss_opt(const float* Q, const float* Qt, int32_t A, const int32_t* act, const float* rew,
+                      const uint8_t* done, float gamma, int32_t B, int32_t n, const float* mix, const float* mix_t,
+                      float* dQ, float* mix_grad, float* loss, float* part, float* zero, int64_t nzero,
+                      const evx_td_opts* opt, float* td_abs, void* stream) {
+    evxx::MixOpts mo{};
+    if (opt) {
+        mo.sel = opt->sel;
+        mo.gamma_row = opt->gamma_row;
+        mo.delta = opt->huber_delta;
     }
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(evxx::qmix_rows_kernel, dim3(nrb + nz), dim3(evxx::ROWS), lds, st, Q, Qt, A, act, rew, done, gamma,
-                       B, n, mix, mix_t, dQ, part, nrb, nz ? zero : nullptr, nzero);
-    hipLaunchKernelGGL(evxx::qmix_reduce_kernel, dim3(1), dim3(256), 0, st, part, nrb, n, B, mix, mix_grad, loss);
-    return evxh::hip_status("qmix_loss");
+    mo.td_abs = td_abs;
+    return qmix_launch<true>("qmix_loss_opt", Q, Qt, A, act, rew, done, gamma, B, n, mix, mix_t, dQ, mix_grad, loss,
+                             part, zero, nzero, mo, stream);
 }
 
 }  // extern "C"

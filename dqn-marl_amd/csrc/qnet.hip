@@ -1087,6 +1087,48 @@ __global__ __launch_bounds__(256) void replay_nstep_kernel(evx_replay rp, const 
     if (len) len[i] = L;
 }
 
+// evx_replay_sample_nstep_agents: replay_sample_kernel's draw j0 of agent blockIdx.y (its own
+// permutation, or the shared one with joint), s and a from it, then replay_nstep_kernel's chain
+// from j0 in the same launch. The stride is a multiple of nets for whole-env pushes, so every slot
+// of a chain is the same agent's; in joint mode the agents of a draw share the env-steps, the push
+// gave them the env's team reward and done flag, and so their chains have one length. j0 < size <=
+// capacity, every later slot is taken mod capacity: nothing is read outside the ring.
+__global__ __launch_bounds__(256) void replay_sample_nstep_agents_kernel(
+    evx_replay rp, int64_t size, int B, int nets, int joint, uint64_t seed, uint64_t offset, int64_t base,
+    int64_t count, int64_t stride, int n_step, float gamma, evx_obs* __restrict__ s, evx_obs* __restrict__ s2,
+    int32_t* __restrict__ a, float* __restrict__ r, uint8_t* __restrict__ done, float* __restrict__ gamma_row,
+    int32_t* __restrict__ len, int64_t* __restrict__ idx_out) {
+    const int i0 = blockIdx.x * 256 + threadIdx.x;
+    if (i0 >= B) return;
+    const int g = (int)blockIdx.y;
+    const int64_t i = (int64_t)g * B + i0;
+    const uint64_t n = (uint64_t)(size / nets);
+    const perm_key pk = make_perm_key(n, seed, offset, joint ? 0u : (uint32_t)g);
+    const int64_t C = rp.capacity;
+    const int64_t j0 = (int64_t)perm_apply(pk, (uint64_t)i0, n) * nets + g;
+    s[i] = rp.s[j0];
+    a[i] = rp.a[j0];
+    int64_t d0 = j0 - base;
+    if (d0 < 0) d0 += C;
+    int64_t j = j0;
+    float R = rp.r[j0], gm = gamma;
+    uint8_t dn = rp.done[j0];
+    int L = 1;
+    while (L < n_step && !dn && d0 + (int64_t)L * stride < count) {
+        j = (j0 + (int64_t)L * stride) % C;
+        R = R + gm * rp.r[j];
+        gm = gm * gamma;
+        dn = rp.done[j];
+        L++;
+    }
+    r[i] = R;
+    gamma_row[i] = gm;
+    done[i] = dn;
+    s2[i] = rp.s2[j];
+    if (len) len[i] = L;
+    if (idx_out) idx_out[i] = j0;
+}
+
 __global__ __launch_bounds__(256) void gather_rows_kernel(const evx_obs* __restrict__ src,
                                                           const int64_t* __restrict__ idx, int n,
                                                           evx_obs* __restrict__ dst) {
@@ -2177,6 +2219,40 @@ int evx_replay_nstep(const evx_replay* rp, const int64_t* idx, int32_t B, int64_
                        base, count, std::min<int64_t>(stride, rp->capacity), (int)n_step, gamma, s2, r, done,
                        gamma_row, len);
     return hip_status("replay_nstep");
+}
+
+int evx_replay_sample_nstep_agents(const evx_replay* rp, int64_t size, int32_t B, int32_t nets, int32_t joint,
+                                   uint64_t seed, uint64_t offset, int64_t base, int64_t count, int64_t stride,
+                                   int32_t n_step, float gamma, evx_obs* s, evx_obs* s2, int32_t* a, float* r,
+                                   uint8_t* done, float* gamma_row, int32_t* len, int64_t* idx_out, void* stream) {
+    if (!rp || !s || !s2 || !a || !r || !done || !gamma_row)
+        return fail(-22, "replay_sample_nstep_agents: NULL argument");
+    if (rp->capacity <= 0) return fail(-22, "replay_sample_nstep_agents: bad ring");
+    if (n_step < 1 || n_step > EVX_NSTEP_MAX)
+        return fail(-22, "replay_sample_nstep_agents: n_step must be 1..EVX_NSTEP_MAX (32)");
+    if (stride < 1) return fail(-22, "replay_sample_nstep_agents: stride must be >= 1");
+    if (count < 0 || count > rp->capacity)
+        return fail(-22, "replay_sample_nstep_agents: count must lie in [0, capacity]");
+    if (base < 0 || base >= rp->capacity)
+        return fail(-22, "replay_sample_nstep_agents: base must lie in [0, capacity)");
+    if (!std::isfinite(gamma)) return fail(-22, "replay_sample_nstep_agents: gamma must be finite");
+    if (B <= 0) return 0;
+    if (nets < 1 || nets > 65535) return fail(-22, "replay_sample_nstep_agents: nets must be 1..65535");
+    if (rp->capacity % nets) return fail(-22, "replay_sample_nstep_agents: capacity must be a multiple of nets");
+    if (size < nets || size > rp->capacity || size % nets)
+        return fail(-22, "replay_sample_nstep_agents: size must be a positive multiple of nets within the capacity");
+    if (B > size / nets)
+        return fail(-22, joint ? "replay_sample_nstep_agents: sample larger than the population"
+                               : "replay_sample_nstep_agents: sample larger than an agent's population");
+    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done)
+        return fail(-22, "replay_sample_nstep_agents: NULL ring array");
+    // a stride beyond the ring never finds a successor inside the range (count <= capacity): the
+    // capacity stands for it, so L * stride cannot overflow
+    hipLaunchKernelGGL(evxq::replay_sample_nstep_agents_kernel, dim3(nblk(B), nets), dim3(256), 0, (hipStream_t)stream,
+                       *rp, size, (int)B, (int)nets, joint ? 1 : 0, seed, offset, base, count,
+                       std::min<int64_t>(stride, rp->capacity), (int)n_step, gamma, s, s2, a, r, done, gamma_row, len,
+                       idx_out);
+    return hip_status("replay_sample_nstep_agents");
 }
 
 int evx_gather_obs(const evx_obs* src, const int64_t* idx, int32_t n, evx_obs* dst, void* stream) {

@@ -247,6 +247,8 @@ SIGNATURES = {
     "evx_replay_sample_agents": (C.c_int, [_RING, _i64, _i32, _i32, _u64, _u64] + [_vp] * 6),
     "evx_replay_sample_joint": (C.c_int, [_RING, _i64, _i32, _i32, _u64, _u64] + [_vp] * 6),
     "evx_replay_nstep": (C.c_int, [_RING, _vp, _i32] + [_i64] * 3 + [_i32, _f32] + [_vp] * 6),
+    "evx_replay_sample_nstep_agents": (C.c_int, [_RING, _i64, _i32, _i32, _i32, _u64, _u64] + [_i64] * 3 +
+                                       [_i32, _f32] + [_vp] * 9),
     "evx_prio_init": (C.c_int, [_P(evx_prio), _vp]),
     "evx_prio_set_range": (C.c_int, [_P(evx_prio)] + [_i64] * 3 + [_vp]),
     "evx_prio_update": (C.c_int, [_P(evx_prio), _vp, _vp, _i32, _f64, _f64, _vp]),
@@ -309,6 +311,8 @@ SIGNATURES = {
     "evx_qmix_nparams": (C.c_int32, [_i32]),
     "evx_qmix_part_floats": (C.c_int64, [_i32, _i32]),
     "evx_qmix_loss": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32, _i32] + [_vp] * 7 + [_i64, _vp]),
+    "evx_qmix_loss_opt": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32, _i32] + [_vp] * 7 +
+                          [_i64, _OPTS, _vp, _vp]),
     "evx_qmix_last_error": (C.c_char_p, []),
     "evx_episode_init": (C.c_int, [_P(evx_episodes), _vp]),
     "evx_episode_update": (C.c_int, [_P(evx_episodes)] + [_vp] * 3 + [_i64, _vp]),

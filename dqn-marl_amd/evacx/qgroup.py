@@ -18,11 +18,14 @@ Adam moments, MFMA operand copies, activations -- is one slice of a [G][...] arr
   net's TD step (inside its backward's first kernel) per 16- to 128-row block in row order.
 * ``GroupedQMix``: the QMIX learn step -- the agents' forwards, the mixer's loss and backward
   in one kernel (evx_qmix_loss: dQ of every agent at its taken action), the agents' grouped
-  backward and per-agent clip + Adam, the mixer's clip_grad_norm_ + Adam.
+  backward and per-agent clip + Adam, the mixer's clip_grad_norm_ + Adam. Opt-in: Double-Q
+  selection, the Huber loss and a discount per joint row (evx_qmix_loss_opt), soft target updates
+  of the agents and the mixer.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional
 
 import torch
@@ -356,10 +359,22 @@ class GroupedQMix:
         self.mix_norm = torch.zeros(1, **f32)
         self._scratch = torch.zeros(2048, **f32)
 
-    def __call__(self, lay_c, s_obs, a, r, done, s2_obs, B: int):
+    def __call__(self, lay_c, s_obs, a, r, done, s2_obs, B: int, double_q: bool = False, huber_delta: float = 0.0,
+                 gamma_row=None):
         """s_obs / s2_obs [n][B] compact observations, a [n][B] int32 (agent-major), r / done [B] (the
-        joint reward and done flag). Returns the loss tensor [1] (device)."""
+        joint reward and done flag). Returns the loss tensor [1] (device).
+        double_q: every agent's target value is its target net's at the online net's greedy action at
+        s2 -- one more launch, as GroupedLearner.learn_obs makes it: act_blocks on s2_obs with every
+        epsilon 0 on dropout stream drop_stream + 2, before the forward pair; the actions stay in
+        A.last_sel (int32 [n B]) and drop_stream advances by 3 instead of 2.
+        huber_delta > 0: the Huber loss on the mixed TD error (0: its square). gamma_row: device f32
+        [B], the discount of every joint row in place of gamma (n-step rows). Any of them:
+        evx_qmix_loss_opt; all off: evx_qmix_loss and the stream numbers of a call without them."""
         A, n = self.A, self.A.G
+        if not (isinstance(huber_delta, (int, float)) and math.isfinite(huber_delta) and huber_delta >= 0):
+            raise ValueError(f"qmix: huber_delta must be a finite number >= 0, not {huber_delta!r}")
+        if gamma_row is not None and (gamma_row.dtype != torch.float32 or gamma_row.numel() < B):
+            raise ValueError(f"qmix: gamma_row must be a float32 tensor of at least B = {B} elements")
         X = A._buf("x", n * B * K1X, torch.int16)
         H1 = A._buf("h1", n * 2 * B * HID, torch.int16)
         H2 = A._buf("h2", n * B * HID2, torch.float32)
@@ -370,7 +385,12 @@ class GroupedQMix:
             _need("qmix " + name, t, n * B, w)
         _need("qmix r", r, B, 1)
         _need("qmix done", done, B, 1)
-        A.drop_stream += 2
+        A.drop_stream += 3 if double_q else 2
+        sel = None
+        if double_q:  # the online nets' greedy actions at s2 (train mode, as every forward of learn)
+            sel = A._buf("sel", n * B, torch.int32)
+            A.act_blocks(lay_c, s2_obs, B, [0.0] * n, actions=sel, drop_p=A.drop_p, drop_stream=A.drop_stream + 2)
+            A.last_sel = sel
         d_on = MLPFast._drop((A.seed, A.drop_stream, A.drop_p))
         d_tg = MLPFast._drop((A.seed, A.drop_stream + 1, A.drop_p))
         o_on = MLPFast._out(H1, X, H2, Q)
@@ -380,10 +400,18 @@ class GroupedQMix:
                                         C.byref(o_tg), _stream()), "qmlp_forward2_g")
         dQ = A._buf("dq", n * B * NACT, torch.float32)
         part = A._buf("mixpart", int(lib().evx_qmix_part_floats(B, n)), torch.float32)
-        check(lib().evx_qmix_loss(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(), done.data_ptr(),
-                                  A.gamma, B, n, self.mix.data_ptr(), self.mix_t.data_ptr(), dQ.data_ptr(),
-                                  self.mix_g.data_ptr(), self.loss.data_ptr(), part.data_ptr(), A.gflat.data_ptr(),
-                                  A.gflat.numel(), _stream()), "qmix_loss")
+        if sel is None and huber_delta == 0 and gamma_row is None:
+            check(lib().evx_qmix_loss(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(), done.data_ptr(),
+                                      A.gamma, B, n, self.mix.data_ptr(), self.mix_t.data_ptr(), dQ.data_ptr(),
+                                      self.mix_g.data_ptr(), self.loss.data_ptr(), part.data_ptr(), A.gflat.data_ptr(),
+                                      A.gflat.numel(), _stream()), "qmix_loss")
+        else:
+            o = td_opts(sel=sel, huber_delta=huber_delta, gamma_row=gamma_row)
+            check(lib().evx_qmix_loss_opt(Q.data_ptr(), Qt.data_ptr(), NACT, a.data_ptr(), r.data_ptr(),
+                                          done.data_ptr(), A.gamma, B, n, self.mix.data_ptr(), self.mix_t.data_ptr(),
+                                          dQ.data_ptr(), self.mix_g.data_ptr(), self.loss.data_ptr(), part.data_ptr(),
+                                          A.gflat.data_ptr(), A.gflat.numel(), C.byref(o), None, _stream()),
+                  "qmix_loss_opt")
         A._backward(B, dQ, X, H1, H2)
         A.step_optimizer()  # clip_grad_norm_(agent_i, 1.0) + agent_i.optimizer.step()
         L = lib()
@@ -400,3 +428,10 @@ class GroupedQMix:
         """agent.update_target_network() for every agent + target_mixing <- mixing (:116-118)."""
         self.A.sync_target()
         self.mix_t.copy_(self.mix)
+
+    def soft_update(self, tau: float):
+        """Polyak update of every agent's target net (GroupedLearner.soft_update, one launch) and of
+        the target mixer (evx_polyak): target = tau * online + (1 - tau) * target."""
+        self.A.soft_update([tau] * self.A.G)
+        t, omt = polyak_coeffs(tau)
+        check(lib().evx_polyak(self.mix.data_ptr(), self.mix_t.data_ptr(), self.nmix, t, omt, _stream()), "polyak")

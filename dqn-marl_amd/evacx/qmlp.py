@@ -17,7 +17,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import (check, evx_qmlp_dropout, evx_qmlp_fwd_out, evx_qmlp_fwd_plan, evx_qmlp_grads,  # noqa: F401
+from ._lib import (NSTEP_MAX, check, evx_qmlp_dropout, evx_qmlp_fwd_out, evx_qmlp_fwd_plan, evx_qmlp_grads,  # noqa: F401
                    evx_qmlp_params, evx_td_opts, lib)
 from .env import _stream
 
@@ -44,6 +44,46 @@ def validate_td_options(loss: str = "mse", huber_delta: float = 1.0, target_tau:
         raise ValueError(f"huber_delta must be a finite number > 0, not {huber_delta!r}")
     if not (isinstance(target_tau, (int, float)) and 0.0 <= target_tau < 1.0):
         raise ValueError(f"target_tau must lie in [0, 1), not {target_tau!r}")
+
+
+def validate_nets_options(nets: str = "shared", R: int = 1, E: int = 1, batch: int = 4096,
+                          replay_capacity: int = 1 << 20, n_step: int = 1, groups: int = 1, kind: str = "mlp",
+                          precision: str = "f32", lagged_learn: bool = False, replay: str = "uniform",
+                          per_env_layouts: bool = False, grad_hook: bool = False,
+                          td_options: bool = False, agent_options: bool = False) -> None:
+    """ValueError for a combination of VecTrainer's nets mode and learner options that no path
+    runs: an unknown nets; an n_step outside [1, NSTEP_MAX], or n_step > 1
+    with groups != 1 or a ring that holds no whole chain (n_step * E * R > replay_capacity);
+    "per_robot" / "qmix" nets with anything but the MLP in f32, one group, the strict schedule,
+    uniform replay, one layout and one GPU, or with a batch that is no multiple of 2 R or a
+    capacity that is no multiple of R. td_options: one of double_q, loss, huber_delta, target_tau is
+    off its default. agent_options: the caller is evacx.trainer.MultiAgentTrainer, which takes those
+    and n_step > 1 for "per_robot" / "qmix" nets; VecTrainer itself keeps refusing them there.
+    Needs no device."""
+    if nets not in ("shared", "per_robot", "qmix"):
+        raise ValueError(f"nets must be 'shared', 'per_robot' or 'qmix', not {nets!r}")
+    if isinstance(n_step, bool) or not (isinstance(n_step, int) and 1 <= n_step <= NSTEP_MAX):
+        raise ValueError(f"n_step must be an integer in [1, {NSTEP_MAX}], not {n_step!r}")
+    if nets != "shared" and td_options and not agent_options:
+        raise ValueError(f"double_q / loss / huber_delta / target_tau need nets='shared' with VecTrainer: for "
+                         f"nets={nets!r} use evacx.trainer.MultiAgentTrainer")
+    if n_step > 1:
+        if nets != "shared" and not agent_options:
+            raise ValueError(f"n_step > 1 needs nets='shared' with VecTrainer: for nets={nets!r} use "
+                             "evacx.trainer.MultiAgentTrainer")
+        if groups != 1:
+            raise ValueError("n_step > 1 needs groups=1: the successor rule rests on one push of E * R rows "
+                             "per step")
+        if n_step * E * R > replay_capacity:
+            raise ValueError(f"n_step * E * R = {n_step * E * R} exceeds replay_capacity = "
+                             f"{replay_capacity}: no n_step chain could ever complete")
+    if nets != "shared":
+        if kind != "mlp" or precision != "f32" or groups != 1 or lagged_learn or replay != "uniform" or \
+                per_env_layouts or grad_hook:
+            raise ValueError("per_robot nets: MLP, f32, one group, strict schedule, uniform replay, one layout, "
+                             "one GPU")
+        if batch % (2 * R) or replay_capacity % R:
+            raise ValueError("per_robot nets: batch a multiple of 2 R, replay capacity a multiple of R")
 
 
 def td_opts(sel=None, huber_delta: float = 0.0, gamma_row=None) -> evx_td_opts:

@@ -24,7 +24,8 @@ import torch
 from ._lib import (ACCUM, CONV_DW, CONV_DX, CONV_FWD, OUT_SPLIT, PREC, RELU, SPLIT_AB, check,  # noqa: F401
                    evx_adam, evx_gemm_desc, evx_gemm_plan, lib)
 from .env import _stream
-from .qmlp import evx_td_opts, polyak_coeffs, td_opts, validate_td_options  # noqa: F401 (re-exported)
+from .qmlp import (evx_td_opts, polyak_coeffs, td_opts, validate_nets_options,  # noqa: F401 (re-exported)
+                   validate_td_options)
 
 DROPOUT_P = 0.2
 # the loader's and the check's earlier names here, kept for callers written against them

@@ -26,10 +26,10 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from ._lib import NSTEP_MAX, OBS_WORDS, check, evx_replay, lib
+from ._lib import OBS_WORDS, check, evx_replay, lib
 from .env import DeviceLayout, VecEnv, _ptr, _stream, n_layout_rows
 from .qmlp import act_ws_ints
-from .qnet import DROPOUT_P, Learner, validate_td_options
+from .qnet import DROPOUT_P, Learner, validate_nets_options, validate_td_options
 
 
 class Replay:
@@ -144,6 +144,9 @@ class _Group:
 
 
 class VecTrainer:
+    # per-robot / QMIX nets with double_q / loss / huber_delta / target_tau / n_step: MultiAgentTrainer
+    agent_options = False
+
     def __init__(self, layout: DeviceLayout, E: int, seed_base: int = 1234, env_offset: int = 0,
                  kind: str = "mlp", precision: str = "f32", batch: int = 4096, replay_capacity: int = 1 << 20,
                  lr: float = 1e-4, gamma: float = 0.99, epsilon: float = 1.0, epsilon_min: float = 0.02,
@@ -175,12 +178,18 @@ class VecTrainer:
         Off: nothing is allocated or launched for it.
         double_q / loss ("mse", "huber") / huber_delta / target_tau: the learner's TD options
         (evacx.qnet.Learner); target_tau > 0 replaces the hard copy every target_every learn steps
-        by Learner.soft_update() after every learn step. nets="shared" only.
+        by Learner.soft_update() after every learn step. nets="shared" here; the subclass
+        MultiAgentTrainer takes them for the other two: with nets="per_robot" every robot's net
+        takes them (GroupedLearner.learn_obs / soft_update); with "qmix" Double-Q selects every
+        agent's bootstrap action, the Huber loss acts on the mixed TD error and the soft update
+        covers the agents and the target mixer (GroupedQMix).
         n_step > 1: the learn step turns its sampled slots into n-step rows (Replay.nstep, one more
         launch after the sampler's, on its stream: r = the discounted return of up to n_step
         rewards of the same env and robot, s2 / done the chain's last slot's, the discount per row
         in samp["gamma_row"], the chain lengths in samp["nlen"]); under every sampler and both
-        schedules. nets="shared", groups=1 and no step(extra_reset=...). 1: nothing of it runs.
+        schedules. nets="per_robot" / "qmix" (MultiAgentTrainer only): the sampler and the chains in one launch
+        (evx_replay_sample_nstep_agents over the whole ring), gamma_row [R][batch / R]; QMIX reads
+        agent 0's rows, the joint rows'. groups=1 and no step(extra_reset=...). 1: nothing of it runs.
         learn_stats: the learner folds every learn step's batch into an evacx.lstats.LearnStats (two
         launches after clip + Adam, on its stream) for learn_summary(); nets="shared" (1 net) or
         "per_robot" (R nets), not "qmix" (the target there is the mixer's).
@@ -189,26 +198,19 @@ class VecTrainer:
         more launch per group and step, where the episode statistics' runs) for value_summary();
         every nets mode. Both off: nothing is allocated or launched for them; on, the training
         itself is the same bit for bit."""
-        if learn_stats and nets == "qmix":
+        if learn_stats and nets == "qmix":  # (before anything reads the layout)
             raise ValueError("learn_stats needs nets='shared' or 'per_robot': the QMIX target is the mixer's")
         validate_td_options(loss, huber_delta, target_tau)
         self.target_tau = float(target_tau)
-        if not (isinstance(n_step, int) and 1 <= n_step <= NSTEP_MAX):
-            raise ValueError(f"n_step must be an integer in [1, {NSTEP_MAX}], not {n_step!r}")
-        if n_step > 1:
-            if nets != "shared":
-                raise ValueError(f"n_step > 1 needs nets='shared': the samplers of nets={nets!r} return no slot "
-                                 "indices")
-            if groups != 1:
-                raise ValueError("n_step > 1 needs groups=1: the successor rule rests on one push of E * R rows "
-                                 "per step")
-            if n_step * E * layout.R > replay_capacity:
-                raise ValueError(f"n_step * E * R = {n_step * E * layout.R} exceeds replay_capacity = "
-                                 f"{replay_capacity}: no n_step chain could ever complete")
-        self.n_step = n_step
-        self.last_range = None  # n_step > 1: the (base, count) the last learn step's chains ran over
         if precision not in ("f32", "bf16", "exact"):
             raise ValueError(f"precision must be 'f32', 'bf16' or 'exact', not {precision!r}")
+        validate_nets_options(nets, R=layout.R, E=E, batch=batch, replay_capacity=replay_capacity, n_step=n_step,
+                              groups=groups, kind=kind, precision=precision, lagged_learn=lagged_learn, replay=replay,
+                              per_env_layouts=layout_of is not None, grad_hook=grad_hook is not None,
+                              td_options=bool(double_q or loss != "mse" or huber_delta != 1.0 or target_tau != 0.0),
+                              agent_options=self.agent_options)
+        self.n_step = n_step
+        self.last_range = None  # n_step > 1: the (base, count) the last learn step's chains ran over
         # a ring smaller than one push: two rows of the push would share a slot (the winner undefined)
         # and window() would count a negative number of entries. Groups push their own rows one after
         # the other; the lagged schedule's window sets a whole step's rows aside
@@ -225,18 +227,11 @@ class VecTrainer:
         self.env.reset()
         parts = self.env.split(groups) if groups > 1 else [self.env]
         self.per_robot = nets in ("per_robot", "qmix")
-        if nets not in ("shared", "per_robot", "qmix"):
-            raise ValueError(f"nets must be 'shared', 'per_robot' or 'qmix', not {nets!r}")
-        if self.per_robot and (double_q or loss != "mse" or huber_delta != 1.0 or target_tau != 0.0):
-            raise ValueError("double_q / loss / huber_delta / target_tau need nets='shared': the grouped learner has "
-                             "no grouped selection forward and the QMIX loss has its own kernel")
+        # per-robot / QMIX nets: the options as the grouped learn steps take them (None / 0: off, and
+        # then the entries and launches of a trainer without them)
+        self.double_q = bool(double_q)
+        self.huber = float(huber_delta) if loss == "huber" else 0.0
         if self.per_robot:
-            if kind != "mlp" or precision != "f32" or groups != 1 or lagged_learn or replay != "uniform" or \
-                    layout_of is not None or grad_hook is not None:
-                raise ValueError("per_robot nets: MLP, f32, one group, strict schedule, uniform replay, one layout, "
-                                 "one GPU")
-            if batch % (2 * self.R) or replay_capacity % self.R:
-                raise ValueError("per_robot nets: batch a multiple of 2 R, replay capacity a multiple of R")
             from .qgroup import GroupedLearner, GroupedQMix
             self.learn_stats = None
             if learn_stats:
@@ -431,18 +426,39 @@ class VecTrainer:
             if self.replay.size < self.batch:
                 return None
             sp = self.samp
-            fn = lib().evx_replay_sample_joint if self.qmix is not None else lib().evx_replay_sample_agents
-            check(fn(C.byref(self.replay.c), self.replay.size, Bn, self.R, self.seed + 1, self.learn_steps * self.batch,
-                     sp["s"].data_ptr(), sp["s2"].data_ptr(), sp["a"].data_ptr(), sp["r"].data_ptr(),
-                     sp["done"].data_ptr(), _stream()), "replay_sample_agents/joint")
-            if self.qmix is not None:  # agent 0's rows carry the team reward / done of the sampled env-steps
-                loss = self.qmix(self.lay.c, sp["s"], sp["a"], sp["r"], sp["done"], sp["s2"], Bn)
+            grow = None
+            if self.n_step > 1:
+                # the draws of the sampler below, each followed along its robot's chain over the whole
+                # ring in the same launch (evx_replay_sample_nstep_agents; one push is E * R rows)
+                self.last_range = self.replay.live_range()
+                check(lib().evx_replay_sample_nstep_agents(
+                    C.byref(self.replay.c), self.replay.size, Bn, self.R, int(self.qmix is not None), self.seed + 1,
+                    self.learn_steps * self.batch, self.last_range[0], self.last_range[1], self.n_agents, self.n_step,
+                    float(self.glearner.gamma), sp["s"].data_ptr(), sp["s2"].data_ptr(), sp["a"].data_ptr(),
+                    sp["r"].data_ptr(), sp["done"].data_ptr(), sp["gamma_row"].data_ptr(), sp["nlen"].data_ptr(),
+                    sp["idx"].data_ptr(), _stream()), "replay_sample_nstep_agents")
+                grow = sp["gamma_row"]  # [R][Bn]; QMIX reads agent 0's rows [0, Bn): the joint rows'
             else:
-                loss = self.glearner.learn_obs(self.lay.c, sp["s"], sp["a"], sp["r"], sp["done"], sp["s2"], Bn)
+                fn = lib().evx_replay_sample_joint if self.qmix is not None else lib().evx_replay_sample_agents
+                check(fn(C.byref(self.replay.c), self.replay.size, Bn, self.R, self.seed + 1,
+                         self.learn_steps * self.batch, sp["s"].data_ptr(), sp["s2"].data_ptr(), sp["a"].data_ptr(),
+                         sp["r"].data_ptr(), sp["done"].data_ptr(), _stream()), "replay_sample_agents/joint")
+            if self.qmix is not None:  # agent 0's rows carry the team reward / done of the sampled env-steps
+                loss = self.qmix(self.lay.c, sp["s"], sp["a"], sp["r"], sp["done"], sp["s2"], Bn,
+                                 double_q=self.double_q, huber_delta=self.huber, gamma_row=grow)
+            else:
+                loss = self.glearner.learn_obs(self.lay.c, sp["s"], sp["a"], sp["r"], sp["done"], sp["s2"], Bn,
+                                               gamma_row=grow, double_q=self.double_q,
+                                               huber_delta=[self.huber] * self.R if self.huber else None)
             self.learn_steps += 1
             if self.epsilon > self.epsilon_min:
                 self.epsilon *= self.epsilon_decay
-            if self.learn_steps % self.target_every == 0:
+            if self.target_tau > 0:  # Polyak targets after every learn step, no periodic hard copy
+                if self.qmix is not None:
+                    self.qmix.soft_update(self.target_tau)
+                else:
+                    self.glearner.soft_update([self.target_tau] * self.R)
+            elif self.learn_steps % self.target_every == 0:
                 if self.qmix is not None:
                     self.qmix.sync_targets()
                 else:
@@ -697,6 +713,20 @@ class VecTrainer:
         cur.wait_event(self.ev_learned)
         cur.wait_event(self.ev_prio)
         self.join_caller = True
+
+
+class MultiAgentTrainer(VecTrainer):
+    """VecTrainer for nets="per_robot" or "qmix" with the learner's options: double_q, loss,
+    huber_delta, target_tau and n_step as VecTrainer's docstring states them for these modes.
+    VecTrainer itself refuses them there, as it always has; everything else -- arguments, step(),
+    learn(), the summaries -- is VecTrainer's, and with every option at its default the two classes
+    train bit for bit alike."""
+    agent_options = True
+
+    def __init__(self, layout, E: int, nets: str = "qmix", **kw):
+        if nets not in ("per_robot", "qmix"):
+            raise ValueError(f"MultiAgentTrainer: nets must be 'per_robot' or 'qmix', not {nets!r}")
+        super().__init__(layout, E, nets=nets, **kw)
 
 
 def make_allreduce_hook(dist, world: int):

@@ -462,6 +462,27 @@ int evx_replay_sample_joint(const evx_replay *rp, int64_t size, int32_t B, int32
 int evx_replay_nstep(const evx_replay *rp, const int64_t *idx, int32_t B, int64_t base, int64_t count,
                      int64_t stride, int32_t n_step, float gamma, evx_obs *s2, float *r, uint8_t *done,
                      float *gamma_row, int32_t *len, void *stream);
+/* evx_replay_sample_agents (joint = 0) or evx_replay_sample_joint (joint != 0) and evx_replay_nstep
+ * in one launch, for per-robot and QMIX nets. Row g B + i draws slot j0 as that sampler does with
+ * the same (size, B, nets, seed, offset), takes s and a from it and follows evx_replay_nstep's chain
+ * from j0 over the live range [base, base + count) mod capacity (successor of slot j: (j + stride)
+ * mod capacity; stride = the rows of one push, a multiple of nets, so a chain stays with its agent;
+ * it stops at n_step, at a terminal slot or at the end of the range): r = the discounted return,
+ * s2 / done = the chain's last slot's, gamma_row = gamma^L, len = L (int32 [nets][B], may be NULL),
+ * idx_out = j0 (int64 [nets][B], may be NULL). All f32, R + g r a multiply and an add. n_step = 1:
+ * the sampler's s / s2 / a / r / done bit for bit, gamma_row = gamma, len = 1. A stride beyond the
+ * ring is taken as the capacity.
+ * Joint mode: the push writes the env's team reward and done flag into every robot's row, so the
+ * nets chains of one draw have the same length, return and done flag: agent 0's r / done /
+ * gamma_row, rows [0, B), are the joint row's (what evx_qmix_loss_opt takes).
+ * -22 before any launch: a NULL rp, s, s2, a, r, done or gamma_row, a capacity < 1, n_step outside
+ * [1, EVX_NSTEP_MAX], stride < 1, count outside [0, capacity], base outside [0, capacity), gamma not
+ * finite (evx_q_last_error). Then B <= 0: 0. -22: nets outside 1..65535, a capacity or size that is
+ * no multiple of nets, size outside [nets, capacity], B > size / nets, a NULL ring array. */
+int evx_replay_sample_nstep_agents(const evx_replay *rp, int64_t size, int32_t B, int32_t nets, int32_t joint,
+                                   uint64_t seed, uint64_t offset, int64_t base, int64_t count, int64_t stride,
+                                   int32_t n_step, float gamma, evx_obs *s, evx_obs *s2, int32_t *a, float *r,
+                                   uint8_t *done, float *gamma_row, int32_t *len, int64_t *idx_out, void *stream);
 /* ------------------------------------------- prioritized replay
  * Proportional prioritized replay (Schaul et al. 2016) over the slots of an evx_replay
  * ring; the reference samples uniformly (random.sample, agents/dqn_agent.py:132), so
@@ -923,6 +944,30 @@ int64_t evx_qmix_part_floats(int32_t B, int32_t n);
 int evx_qmix_loss(const float *Q, const float *Qt, int32_t A, const int32_t *act, const float *rew,
                   const uint8_t *done, float gamma, int32_t B, int32_t n, const float *mix, const float *mix_t,
                   float *dQ, float *mix_grad, float *loss, float *part, float *zero, int64_t nzero, void *stream);
+/* evx_qmix_loss with the TD options (evx_td_opts, layout unchanged) applied to the mixed value: sel
+ * [n][B] (agent-major like act), gamma_row [B] (one discount per joint row), huber_delta one value;
+ * opt may be NULL. td_abs [B] (may be NULL) gets |d|. Per joint row b, all f32, in the order of
+ * evx_qmix_loss:
+ *   q_i   = Q[i][b][act[i][b]]
+ *   j*_i  = sel ? clamp(sel[i][b], 0, A - 1) : the maximum of Qt[i][b][.];   qt_i = Qt[i][b][j*_i]
+ *   tot_t = target mixer(qt),  tot = online mixer(q)
+ *   y     = rew[b] + (gamma_row ? gamma_row[b] : gamma) * tot_t * (done[b] ? 0 : 1)
+ *   d     = tot - y;  td_abs[b] = |d|
+ *   huber_delta = 0:  l = d * d,  dqt = 2 d / B
+ *   huber_delta > 0:  l = |d| <= delta ? 0.5 (d * d) : delta (|d| - 0.5 delta),  dqt = min(max(d, -delta), delta) / B
+ *   loss = mean(l); the backward through the online mixer from dqt, the mixer's gradient and the
+ *   clear of zero as in evx_qmix_loss. With Double-Q every agent bootstraps from its own greedy
+ *   action and the monotone target mixer combines those values; the Huber loss and its clamp act
+ *   on the team's TD error d, not per agent.
+ * opt = NULL and td_abs = NULL: evx_qmix_loss bit for bit (the same kernel, the options compiled
+ * out there). part, its summation order and the LDS footprint are evx_qmix_loss's.
+ * B <= 0: 0, nothing written. -22 before any launch (evx_qmix_last_error): what evx_qmix_loss
+ * refuses (n outside 1..16, A outside 1..64, a NULL required pointer), a huber_delta that is
+ * negative or not finite, a gamma that is not finite. */
+int evx_qmix_loss_opt(const float *Q, const float *Qt, int32_t A, const int32_t *act, const float *rew,
+                      const uint8_t *done, float gamma, int32_t B, int32_t n, const float *mix, const float *mix_t,
+                      float *dQ, float *mix_grad, float *loss, float *part, float *zero, int64_t nzero,
+                      const evx_td_opts *opt, float *td_abs, void *stream);
 const char *evx_qmix_last_error(void);
 
 /* ---- Episode statistics (csrc/episode.hip). The reference's training loop adds each step's
