@@ -39,8 +39,8 @@
 
 #include "evacx.h"
 #include "evx_device.h"
-#include "evx_draws.h"
 #include "evx_host.h"
+#include "evx_ring.h"
 
 namespace evx {
 
@@ -3271,7 +3271,7 @@ __global__ __launch_bounds__(1024) void env_orders_kernel(const uint8_t* __restr
                                                           int32_t* __restrict__ order, int32_t* __restrict__ perm) {
     orders_body<V16, 16>(cls, E, hcap, order, perm, (int)blockIdx.x);
 }
-// DQNAgent.remember for every robot of the step (the replay push: evxq::replay_push_kernel's body)
+// DQNAgent.remember for every robot of the step (the replay push: evx_ring.h's ring_put)
 // and the next step's orders in one launch: workgroups [0, nord) the orders (1024 envs each), the
 // rest one transition per thread -- the orders then need no launch or cross-stream event of their
 // own, and run beside the push's memory traffic. (256-env order workgroups of 4 waves, each
@@ -3306,22 +3306,14 @@ __global__ __launch_bounds__(1024) void env_orders_push_kernel(const uint8_t* __
         if (threadIdx.x >= 256) return;
         const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
         if (i >= sa.B) return;
-        const evxd::perm_key pk = evxd::make_perm_key((uint64_t)sa.size, sa.seed, sa.offset, 0u);
-        const int64_t j = (int64_t)evxd::perm_apply(pk, (uint64_t)i, (uint64_t)sa.size);  // base 0: the whole ring
+        const evxr::rows out{sa.s, sa.s2, sa.a, sa.r, sa.done};
+        const int64_t j = evxr::perm_draw((uint64_t)sa.size, sa.seed, sa.offset, 0u, i);  // base 0: the whole ring
         const int64_t off = (j - pa.pos) & cm;
         if (off < pa.n) {  // written by this launch's push: its source
-            const int k = (int)off, e = k / pa.agents_per_env;
-            sa.s[i] = pa.s[k];
-            sa.s2[i] = (pa.s2_term && pa.done_env[e]) ? pa.s2_term[k] : pa.s2[k];
-            sa.a[i] = pa.a[k];
-            sa.r[i] = (float)pa.r_env[e];
-            sa.done[i] = pa.done_env[e];
+            const int k = (int)off;
+            evxr::push_row({pa.s, pa.s2, pa.s2_term, pa.a, pa.r_env, pa.done_env}, k, k / pa.agents_per_env, out, i);
         } else {
-            sa.s[i] = pa.rp.s[j];
-            sa.s2[i] = pa.rp.s2[j];
-            sa.a[i] = pa.rp.a[j];
-            sa.r[i] = pa.rp.r[j];
-            sa.done[i] = pa.rp.done[j];
+            evxr::ring_take(pa.rp, j, out, i);
         }
         return;
     }
@@ -3331,13 +3323,8 @@ __global__ __launch_bounds__(1024) void env_orders_push_kernel(const uint8_t* __
     }
     const int i = ((int)blockIdx.x - nord - nsmp) * 1024 + (int)threadIdx.x;
     if (i >= pa.n) return;
-    const int64_t slot = (pa.pos + i) & cm;
-    const int e = i / pa.agents_per_env;
-    pa.rp.s[slot] = pa.s[i];
-    pa.rp.s2[slot] = (pa.s2_term && pa.done_env[e]) ? pa.s2_term[i] : pa.s2[i];
-    pa.rp.a[slot] = pa.a[i];
-    pa.rp.r[slot] = (float)pa.r_env[e];
-    pa.rp.done[slot] = pa.done_env[e];
+    evxr::ring_put(pa.rp, (pa.pos + i) & cm, {pa.s, pa.s2, pa.s2_term, pa.a, pa.r_env, pa.done_env}, i,
+                   i / pa.agents_per_env);
 }
 
 // ---------------------------------------------------- observation expand
@@ -3702,7 +3689,7 @@ int evx_env_orders_push_sample(const evx_layout* l, const evx_state* s, int32_t*
     if (!rp || rp->capacity <= 0 || (rp->capacity & (rp->capacity - 1)))
         return fail(-22, "env_orders_push: replay capacity must be a power of two");
     // the push: what evx_replay_push_term refuses, whether or not a batch is drawn
-    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done) return fail(-22, "env_orders_push: NULL ring array");
+    if ((rc = evxr::ring_arrays_ok("env_orders_push", rp))) return rc;
     if (n < 0) return fail(-22, "env_orders_push: n must be >= 0");
     if (n > rp->capacity) return fail(-22, "env_orders_push: the capacity does not hold n rows");
     if (pos < 0 || pos >= rp->capacity) return fail(-22, "env_orders_push: pos outside [0, capacity)");

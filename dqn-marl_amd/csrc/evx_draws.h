@@ -1,7 +1,8 @@
-// Counter-based draws shared by the learner's kernels (csrc/qnet.hip) and the fused replay push
-// (csrc/env_step.hip): Philox4x32-10 (Salmon et al. 2011) and the keyed Feistel permutation the
+// Counter-based draws: Philox4x32-10 (Salmon et al. 2011) and the keyed Feistel permutation the
 // replay samples without replacement with (DQNAgent.learn's random.sample, agents/dqn_agent.py:132;
-// restated on the CPU by oracle/draw_oracle.c).
+// restated on the CPU by oracle/draw_oracle.c). Users: csrc/qnet.hip (Philox: dropout masks and the
+// epsilon-greedy act) and csrc/evx_ring.h (the permutation: perm_draw, through which csrc/replay.hip
+// and the fused orders + push + sample launch of csrc/env_step.hip draw).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -20,6 +20,7 @@
 
 #include "evacx.h"
 #include "evx_host.h"
+#include "evx_ring.h"
 
 namespace evxp {
 
@@ -181,11 +182,7 @@ __global__ __launch_bounds__(NT) void prio_sample_kernel(evx_replay rp, evx_prio
     }
     const int64_t j = node - C;
     const double p = t.sum[node];
-    s[k] = rp.s[j];
-    s2[k] = rp.s2[j];
-    a[k] = rp.a[j];
-    r[k] = rp.r[j];
-    done[k] = rp.done[j];
+    evxr::ring_take(rp, j, evxr::rows{s, s2, a, r, done}, k);
     if (idx_out) idx_out[k] = j;
     if (w_out) w_out[k] = total > 0.0 ? (float)pow(p / t.mn[1], -beta) : 0.f;
 }

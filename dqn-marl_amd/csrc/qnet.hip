@@ -7,7 +7,7 @@
 //   DQNAgent.learn (:126-168)  -> evx_td_loss (gather, max, TD target, MSE, dQ),
 //                                 evx_gemm backward, evx_colsum (bias grads),
 //                                 evx_sumsq + evx_clip_adam (clip_grad_norm_ + Adam)
-//   DQNAgent.memory (:88-99)   -> evx_replay_push / evx_replay_sample
+//   DQNAgent.memory (:88-99)   -> the replay ring, csrc/replay.hip
 // GEMMs take fp32 operands in HBM and compute either exact f32 (v_mfma_f32_32x32x2_f32:
 // a k-ordered fmaf chain, used where parity with torch fp32 matters) or bf16 inputs
 // with f32 accumulation (v_mfma_f32_32x32x16_bf16, the throughput path).
@@ -30,13 +30,9 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 32;  // K tile of the 128 x 128 GEMM kernels
 
-// Philox4x32-10, the replay permutation (evx_draws.h)
+// Philox4x32-10 (evx_draws.h)
 using evxd::u4;
 using evxd::philox;
-using evxd::perm_key;
-using evxd::fmix32;
-using evxd::make_perm_key;
-using evxd::perm_apply;
 __device__ __forceinline__ float u01(uint32_t v) { return (float)(v >> 8) * (1.0f / 16777216.0f); }
 
 // ------------------------------------------------------------------------ GEMM
@@ -830,7 +826,7 @@ __device__ __forceinline__ void td_loss_body(const float* __restrict__ Q, const 
             mx = Qt[(int64_t)i * A];
             for (int j = 1; j < A; j++) mx = fmaxf(mx, Qt[(int64_t)i * A + j]);
         }
-        // gamma_row (n-step rows, evx_replay_nstep): the row's own discount gamma^L
+        // gamma_row (the replay ring's n-step rows): the row's own discount gamma^L
         const float y = rew[i] + (gamma_row ? gamma_row[i] : gamma) * mx * (done[i] ? 0.f : 1.f);
         const int a = act[i];
         const float d = Q[(int64_t)i * A + a] - y;
@@ -990,150 +986,6 @@ __global__ __launch_bounds__(256) void act_kernel(const float* __restrict__ Q, i
         if (u01(r.x) <= epsilon) best = (int)((uint64_t)r.y * (uint64_t)A >> 32);
     }
     actions[i] = best;
-}
-
-// ---------------------------------------------------------------- replay
-// Uniform replay ring (DQNAgent.memory, agents/dqn_agent.py:88-99) with compact
-// observations; per-agent transitions share the env's team reward/done.
-__global__ __launch_bounds__(256) void replay_push_kernel(evx_replay rp, const evx_obs* __restrict__ s,
-                                                          const evx_obs* __restrict__ s2,
-                                                          const evx_obs* __restrict__ s2_term, const int32_t* __restrict__ a,
-                                                          const double* __restrict__ r_env,
-                                                          const uint8_t* __restrict__ done_env, int n, int agents_per_env,
-                                                          int64_t pos) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t slot = (pos + i) % rp.capacity;
-    const int e = i / agents_per_env;
-    rp.s[slot] = s[i];
-    rp.s2[slot] = (s2_term && done_env[e]) ? s2_term[i] : s2[i];
-    rp.a[slot] = a[i];
-    rp.r[slot] = (float)r_env[e];
-    rp.done[slot] = done_env[e];
-}
-
-// Sampling WITHOUT replacement, as DQNAgent.learn's random.sample(memory, B)
-// (agents/dqn_agent.py:132): draw i of a batch is perm(i) for a keyed pseudo-random permutation
-// perm of [0, n) -- a 6-round balanced Feistel network on the smallest even-width domain 2^w >= n,
-// cycle-walked back into [0, n) (terminates: i's cycle under the domain permutation contains i
-// itself; expected < 4 rounds of walking since 2^w < 4n). Round keys from Philox4x32-10 of the
-// draw's (offset, stream) under the seed, so each learn step's batch is a fresh permutation and
-// the B draws are distinct (B <= n). oracle/draw_oracle.c orc_replay_indices restates it.
-__global__ __launch_bounds__(256) void replay_sample_kernel(evx_replay rp, int64_t base, int64_t size, int B, uint64_t seed,
-                                                            uint64_t offset, evx_obs* __restrict__ s,
-                                                            evx_obs* __restrict__ s2, int32_t* __restrict__ a,
-                                                            float* __restrict__ r, uint8_t* __restrict__ done,
-                                                            int64_t* __restrict__ idx_out, int nets = 1,
-                                                            int joint = 0) {
-    const int i0 = blockIdx.x * 256 + threadIdx.x;
-    if (i0 >= B) return;
-    // nets > 1 (evx_replay_sample_agents): agent blockIdx.y's own transitions -- the ring slots
-    // == agent (mod nets) -- into rows [agent B, (agent + 1) B), a permutation keyed by the agent;
-    // joint (evx_replay_sample_joint): draw i is shared by every agent (the same env-steps)
-    const int g = (int)blockIdx.y;
-    const int i = g * B + i0;
-    const uint64_t n = nets > 1 ? (uint64_t)(size / nets) : (uint64_t)size;
-    const perm_key pk = make_perm_key(n, seed, offset, joint ? 0u : (uint32_t)g);
-    const uint64_t d = perm_apply(pk, (uint64_t)i0, n);
-    int64_t j;
-    if (nets > 1) {
-        j = (int64_t)d * nets + g;
-    } else {
-        j = base + (int64_t)d;
-        if (j >= rp.capacity) j -= rp.capacity;
-    }
-    s[i] = rp.s[j];
-    s2[i] = rp.s2[j];
-    a[i] = rp.a[j];
-    r[i] = rp.r[j];
-    done[i] = rp.done[j];
-    if (idx_out) idx_out[i] = j;
-}
-
-// n-step rows of sampled slots (evx_replay_nstep; not the reference's, whose target is one step
-// deep). Every training step pushes `stride` rows in the same order, so the successor of slot j
-// (same env, same robot, next env step) is slot (j + stride) mod capacity while that slot lies in
-// the live range [base, base + count) mod capacity (push order, oldest first): no link array.
-// One row per thread; the chain stops at n_step links, at a terminal slot (so never across an
-// auto-reset: that slot's s2 is the terminal observation) or at the end of the range. All f32;
-// R + g * r stays a multiply and an add (-ffp-contract=off). A slot index outside the ring is
-// clamped into it (never read out of bounds); one outside the range keeps its own row (L = 1).
-__global__ __launch_bounds__(256) void replay_nstep_kernel(evx_replay rp, const int64_t* __restrict__ idx, int B,
-                                                           int64_t base, int64_t count, int64_t stride, int n_step,
-                                                           float gamma, evx_obs* __restrict__ s2,
-                                                           float* __restrict__ r, uint8_t* __restrict__ done,
-                                                           float* __restrict__ gamma_row, int32_t* __restrict__ len) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B) return;
-    const int64_t C = rp.capacity;
-    const int64_t j0 = min(max(idx[i], (int64_t)0), C - 1);
-    int64_t d0 = j0 - base;
-    if (d0 < 0) d0 += C;
-    int64_t j = j0;
-    float R = rp.r[j0], g = gamma;
-    uint8_t dn = rp.done[j0];
-    int L = 1;
-    while (L < n_step && !dn && d0 + (int64_t)L * stride < count) {
-        j = (j0 + (int64_t)L * stride) % C;
-        R = R + g * rp.r[j];
-        g = g * gamma;
-        dn = rp.done[j];
-        L++;
-    }
-    r[i] = R;
-    gamma_row[i] = g;
-    done[i] = dn;
-    s2[i] = rp.s2[j];
-    if (len) len[i] = L;
-}
-
-// evx_replay_sample_nstep_agents: replay_sample_kernel's draw j0 of agent blockIdx.y (its own
-// permutation, or the shared one with joint), s and a from it, then replay_nstep_kernel's chain
-// from j0 in the same launch. The stride is a multiple of nets for whole-env pushes, so every slot
-// of a chain is the same agent's; in joint mode the agents of a draw share the env-steps, the push
-// gave them the env's team reward and done flag, and so their chains have one length. j0 < size <=
-// capacity, every later slot is taken mod capacity: nothing is read outside the ring.
-__global__ __launch_bounds__(256) void replay_sample_nstep_agents_kernel(
-    evx_replay rp, int64_t size, int B, int nets, int joint, uint64_t seed, uint64_t offset, int64_t base,
-    int64_t count, int64_t stride, int n_step, float gamma, evx_obs* __restrict__ s, evx_obs* __restrict__ s2,
-    int32_t* __restrict__ a, float* __restrict__ r, uint8_t* __restrict__ done, float* __restrict__ gamma_row,
-    int32_t* __restrict__ len, int64_t* __restrict__ idx_out) {
-    const int i0 = blockIdx.x * 256 + threadIdx.x;
-    if (i0 >= B) return;
-    const int g = (int)blockIdx.y;
-    const int64_t i = (int64_t)g * B + i0;
-    const uint64_t n = (uint64_t)(size / nets);
-    const perm_key pk = make_perm_key(n, seed, offset, joint ? 0u : (uint32_t)g);
-    const int64_t C = rp.capacity;
-    const int64_t j0 = (int64_t)perm_apply(pk, (uint64_t)i0, n) * nets + g;
-    s[i] = rp.s[j0];
-    a[i] = rp.a[j0];
-    int64_t d0 = j0 - base;
-    if (d0 < 0) d0 += C;
-    int64_t j = j0;
-    float R = rp.r[j0], gm = gamma;
-    uint8_t dn = rp.done[j0];
-    int L = 1;
-    while (L < n_step && !dn && d0 + (int64_t)L * stride < count) {
-        j = (j0 + (int64_t)L * stride) % C;
-        R = R + gm * rp.r[j];
-        gm = gm * gamma;
-        dn = rp.done[j];
-        L++;
-    }
-    r[i] = R;
-    gamma_row[i] = gm;
-    done[i] = dn;
-    s2[i] = rp.s2[j];
-    if (len) len[i] = L;
-    if (idx_out) idx_out[i] = j0;
-}
-
-__global__ __launch_bounds__(256) void gather_rows_kernel(const evx_obs* __restrict__ src,
-                                                          const int64_t* __restrict__ idx, int n,
-                                                          evx_obs* __restrict__ dst) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
 }
 
 // ------------------------------------------------------------ conv helpers
@@ -2108,158 +1960,6 @@ int evx_act(const float* Q, int32_t n, int32_t A, float epsilon, uint64_t seed, 
     hipLaunchKernelGGL(evxq::act_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, Q, n, A, epsilon, seed,
                        offset, actions);
     return hip_status("act");
-}
-
-// What a push of n rows at pos must satisfy before anything is launched (as evx_replay_push_blocks):
-// n > capacity would let two threads write one slot, a pos outside the ring a slot outside it, and
-// agents_per_env < 1 divides by zero on the device. 0: launch; 1: nothing to push; -22: refused.
-static int push_check(const char* who, const evx_replay* rp, const evx_obs* s, const evx_obs* s2, const int32_t* a,
-                      const double* r_env, const uint8_t* done_env, int32_t n, int32_t agents_per_env, int64_t pos) {
-    if (!rp || rp->capacity <= 0) return failf(-22, "%s: bad ring (NULL, or capacity < 1)", who);
-    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done) return failf(-22, "%s: NULL ring array", who);
-    if (n < 0) return failf(-22, "%s: n must be >= 0", who);
-    if (n > rp->capacity) return failf(-22, "%s: the capacity does not hold n rows", who);
-    if (pos < 0 || pos >= rp->capacity) return failf(-22, "%s: pos outside [0, capacity)", who);
-    if (agents_per_env < 1 || n % agents_per_env) return failf(-22, "%s: n must be a multiple of agents_per_env >= 1", who);
-    if (n == 0) return 1;
-    if (!s || !s2 || !a || !r_env || !done_env) return failf(-22, "%s: NULL argument", who);
-    return 0;
-}
-
-int evx_replay_push(const evx_replay* rp, const evx_obs* s, const evx_obs* s2, const int32_t* a, const double* r_env,
-                    const uint8_t* done_env, int32_t n, int32_t agents_per_env, int64_t pos, void* stream) {
-    if (int rc = push_check("replay_push", rp, s, s2, a, r_env, done_env, n, agents_per_env, pos)) return rc < 0 ? rc : 0;
-    hipLaunchKernelGGL(evxq::replay_push_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, *rp, s, s2,
-                       (const evx_obs*)nullptr, a, r_env, done_env, n, agents_per_env, pos);
-    return hip_status("replay_push");
-}
-
-int evx_replay_push_term(const evx_replay* rp, const evx_obs* s, const evx_obs* s2, const evx_obs* s2_term,
-                         const int32_t* a, const double* r_env, const uint8_t* done_env, int32_t n,
-                         int32_t agents_per_env, int64_t pos, void* stream) {
-    if (int rc = push_check("replay_push_term", rp, s, s2, a, r_env, done_env, n, agents_per_env, pos))
-        return rc < 0 ? rc : 0;
-    hipLaunchKernelGGL(evxq::replay_push_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, *rp, s, s2, s2_term,
-                       a, r_env, done_env, n, agents_per_env, pos);
-    return hip_status("replay_push_term");
-}
-
-int evx_replay_sample(const evx_replay* rp, int64_t size, int32_t B, uint64_t seed, uint64_t offset, evx_obs* s,
-                      evx_obs* s2, int32_t* a, float* r, uint8_t* done, int64_t* idx_out, void* stream) {
-    if (!rp || size <= 0) return fail(-22, "replay: empty");
-    if (B <= 0) return 0;
-    if (size > rp->capacity) return fail(-22, "replay: size > capacity");
-    if (B > size) return fail(-22, "replay: sample larger than population (random.sample)");
-    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done) return fail(-22, "replay_sample: NULL ring array");
-    if (!s || !s2 || !a || !r || !done) return fail(-22, "replay_sample: NULL argument");
-    hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, (int64_t)0,
-                       size, B, seed, offset, s, s2, a, r, done, idx_out);
-    return hip_status("replay_sample");
-}
-
-int evx_replay_sample_agents(const evx_replay* rp, int64_t size, int32_t B, int32_t nets, uint64_t seed,
-                             uint64_t offset, evx_obs* s, evx_obs* s2, int32_t* a, float* r, uint8_t* done,
-                             void* stream) {
-    if (!rp || !s || !s2 || !a || !r || !done) return fail(-22, "replay_sample_agents: NULL argument");
-    if (B <= 0) return 0;
-    if (nets < 1 || nets > 65535) return fail(-22, "replay_sample_agents: nets must be 1..65535");
-    if (rp->capacity % nets) return fail(-22, "replay_sample_agents: capacity must be a multiple of nets");
-    if (size < nets || size > rp->capacity || size % nets)
-        return fail(-22, "replay_sample_agents: size must be a positive multiple of nets within the capacity");
-    if (B > size / nets) return fail(-22, "replay_sample_agents: sample larger than an agent's population");
-    hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B), nets), dim3(256), 0, (hipStream_t)stream, *rp, (int64_t)0,
-                       size, B, seed, offset, s, s2, a, r, done, nullptr, (int)nets);
-    return hip_status("replay_sample_agents");
-}
-
-int evx_replay_sample_joint(const evx_replay* rp, int64_t size, int32_t B, int32_t nets, uint64_t seed,
-                            uint64_t offset, evx_obs* s, evx_obs* s2, int32_t* a, float* r, uint8_t* done,
-                            void* stream) {
-    if (!rp || !s || !s2 || !a || !r || !done) return fail(-22, "replay_sample_joint: NULL argument");
-    if (B <= 0) return 0;
-    if (nets < 1 || nets > 65535) return fail(-22, "replay_sample_joint: nets must be 1..65535");
-    if (rp->capacity % nets) return fail(-22, "replay_sample_joint: capacity must be a multiple of nets");
-    if (size < nets || size > rp->capacity || size % nets)
-        return fail(-22, "replay_sample_joint: size must be a positive multiple of nets within the capacity");
-    if (B > size / nets) return fail(-22, "replay_sample_joint: sample larger than the population");
-    hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B), nets), dim3(256), 0, (hipStream_t)stream, *rp, (int64_t)0,
-                       size, B, seed, offset, s, s2, a, r, done, nullptr, (int)nets, 1);
-    return hip_status("replay_sample_joint");
-}
-
-int evx_replay_sample_window(const evx_replay* rp, int64_t base, int64_t count, int32_t B, uint64_t seed,
-                             uint64_t offset, evx_obs* s, evx_obs* s2, int32_t* a, float* r, uint8_t* done,
-                             int64_t* idx_out, void* stream) {
-    if (!rp || count <= 0) return fail(-22, "replay: empty window");
-    if (count > rp->capacity || base < 0 || base >= rp->capacity) return fail(-22, "replay: bad window");
-    if (B <= 0) return 0;
-    if (B > count) return fail(-22, "replay: sample larger than the window (random.sample)");
-    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done) return fail(-22, "replay_sample_window: NULL ring array");
-    if (!s || !s2 || !a || !r || !done) return fail(-22, "replay_sample_window: NULL argument");
-    hipLaunchKernelGGL(evxq::replay_sample_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, base, count,
-                       B, seed, offset, s, s2, a, r, done, idx_out);
-    return hip_status("replay_sample_window");
-}
-
-int evx_replay_nstep(const evx_replay* rp, const int64_t* idx, int32_t B, int64_t base, int64_t count, int64_t stride,
-                     int32_t n_step, float gamma, evx_obs* s2, float* r, uint8_t* done, float* gamma_row, int32_t* len,
-                     void* stream) {
-    if (!rp || rp->capacity <= 0) return fail(-22, "replay_nstep: bad ring");
-    if (!idx || !s2 || !r || !done || !gamma_row) return fail(-22, "replay_nstep: NULL argument");
-    if (n_step < 1 || n_step > EVX_NSTEP_MAX) return fail(-22, "replay_nstep: n_step must be 1..EVX_NSTEP_MAX (32)");
-    if (stride < 1) return fail(-22, "replay_nstep: stride must be >= 1");
-    if (count < 0 || count > rp->capacity) return fail(-22, "replay_nstep: count must lie in [0, capacity]");
-    if (base < 0 || base >= rp->capacity) return fail(-22, "replay_nstep: base must lie in [0, capacity)");
-    if (!std::isfinite(gamma)) return fail(-22, "replay_nstep: gamma must be finite");
-    if (B <= 0) return 0;
-    if (!rp->s2 || !rp->r || !rp->done) return fail(-22, "replay_nstep: ring without s2 / r / done");
-    // a stride beyond the ring never finds a successor inside the range (count <= capacity): the
-    // capacity stands for it, so L * stride cannot overflow
-    hipLaunchKernelGGL(evxq::replay_nstep_kernel, dim3(nblk(B)), dim3(256), 0, (hipStream_t)stream, *rp, idx, (int)B,
-                       base, count, std::min<int64_t>(stride, rp->capacity), (int)n_step, gamma, s2, r, done,
-                       gamma_row, len);
-    return hip_status("replay_nstep");
-}
-
-int evx_replay_sample_nstep_agents(const evx_replay* rp, int64_t size, int32_t B, int32_t nets, int32_t joint,
-                                   uint64_t seed, uint64_t offset, int64_t base, int64_t count, int64_t stride,
-                                   int32_t n_step, float gamma, evx_obs* s, evx_obs* s2, int32_t* a, float* r,
-                                   uint8_t* done, float* gamma_row, int32_t* len, int64_t* idx_out, void* stream) {
-    if (!rp || !s || !s2 || !a || !r || !done || !gamma_row)
-        return fail(-22, "replay_sample_nstep_agents: NULL argument");
-    if (rp->capacity <= 0) return fail(-22, "replay_sample_nstep_agents: bad ring");
-    if (n_step < 1 || n_step > EVX_NSTEP_MAX)
-        return fail(-22, "replay_sample_nstep_agents: n_step must be 1..EVX_NSTEP_MAX (32)");
-    if (stride < 1) return fail(-22, "replay_sample_nstep_agents: stride must be >= 1");
-    if (count < 0 || count > rp->capacity)
-        return fail(-22, "replay_sample_nstep_agents: count must lie in [0, capacity]");
-    if (base < 0 || base >= rp->capacity)
-        return fail(-22, "replay_sample_nstep_agents: base must lie in [0, capacity)");
-    if (!std::isfinite(gamma)) return fail(-22, "replay_sample_nstep_agents: gamma must be finite");
-    if (B <= 0) return 0;
-    if (nets < 1 || nets > 65535) return fail(-22, "replay_sample_nstep_agents: nets must be 1..65535");
-    if (rp->capacity % nets) return fail(-22, "replay_sample_nstep_agents: capacity must be a multiple of nets");
-    if (size < nets || size > rp->capacity || size % nets)
-        return fail(-22, "replay_sample_nstep_agents: size must be a positive multiple of nets within the capacity");
-    if (B > size / nets)
-        return fail(-22, joint ? "replay_sample_nstep_agents: sample larger than the population"
-                               : "replay_sample_nstep_agents: sample larger than an agent's population");
-    if (!rp->s || !rp->s2 || !rp->a || !rp->r || !rp->done)
-        return fail(-22, "replay_sample_nstep_agents: NULL ring array");
-    // a stride beyond the ring never finds a successor inside the range (count <= capacity): the
-    // capacity stands for it, so L * stride cannot overflow
-    hipLaunchKernelGGL(evxq::replay_sample_nstep_agents_kernel, dim3(nblk(B), nets), dim3(256), 0, (hipStream_t)stream,
-                       *rp, size, (int)B, (int)nets, joint ? 1 : 0, seed, offset, base, count,
-                       std::min<int64_t>(stride, rp->capacity), (int)n_step, gamma, s, s2, a, r, done, gamma_row, len,
-                       idx_out);
-    return hip_status("replay_sample_nstep_agents");
-}
-
-int evx_gather_obs(const evx_obs* src, const int64_t* idx, int32_t n, evx_obs* dst, void* stream) {
-    if (n <= 0) return 0;
-    if (!src || !idx || !dst) return fail(-22, "gather_obs: NULL argument");
-    hipLaunchKernelGGL(evxq::gather_rows_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, src, idx, n, dst);
-    return hip_status("gather_obs");
 }
 
 int evx_im2col3x3(const float* x, int32_t B, int32_t C, int32_t nhwc, float* cols, void* stream) {

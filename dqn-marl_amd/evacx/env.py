@@ -38,6 +38,15 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _check_out_rows(who, out, names, rows, tail, optional=()):
+    """ValueError unless out[k] holds `rows` rows, every k of names and of optional where out has it."""
+    for k in (*names, *optional):
+        t = out.get(k) if k in optional else out[k]
+        per = OBS_WORDS if k in ("s", "s2") else 1
+        if t is not None and t.numel() < rows * per:
+            raise ValueError(f"{who}: out[{k!r}] holds {t.numel() // per} rows, {tail}")
+
+
 def pack_xy(x, y) -> np.ndarray:
     x = np.asarray(x, np.int64) & 0xFFFF
     y = np.asarray(y, np.int64) & 0xFFFF

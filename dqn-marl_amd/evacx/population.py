@@ -37,7 +37,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from ._lib import NSTEP_MAX, OBS_WORDS, check, evx_replay, lib
-from .env import _ptr, _stream
+from .env import _check_out_rows, _ptr, _stream
 
 MAX_MEMBERS = 64
 _HP = ("lr", "gamma", "epsilon", "epsilon_min", "epsilon_decay", "target_every")
@@ -146,10 +146,7 @@ class BlockReplay:
 
     def sample(self, B, seed, offset, out):
         """Ring k's B draws under (seed, offset + k B) into rows [k B, (k + 1) B) of out, every k."""
-        for name, per in (("s", OBS_WORDS), ("s2", OBS_WORDS), ("a", 1), ("r", 1), ("done", 1)):
-            if out[name].numel() < self.K * B * per:
-                raise ValueError(f"BlockReplay.sample: out[{name!r}] holds {out[name].numel() // per} rows, "
-                                 f"needs {self.K * B}")
+        _check_out_rows("BlockReplay.sample", out, ("s", "s2", "a", "r", "done"), self.K * B, f"needs {self.K * B}")
         check(lib().evx_replay_sample_blocks(C.byref(self.c), self.size, B, self.K, seed, offset, out["s"].data_ptr(),
                                              out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
                                              out["done"].data_ptr(), _stream()), "replay_sample_blocks")
@@ -167,14 +164,8 @@ class BlockReplay:
         of every ring, bit for bit."""
         if len(n_step) != self.K or len(gamma) != self.K:
             raise ValueError(f"BlockReplay.sample_nstep: n_step and gamma must hold {self.K} values")
-        for name, per in (("s", OBS_WORDS), ("s2", OBS_WORDS), ("a", 1), ("r", 1), ("done", 1), ("gamma_row", 1),
-                          ("nlen", 1), ("idx", 1)):
-            t = out.get(name)
-            if t is None and name in ("nlen", "idx"):
-                continue
-            if t.numel() < self.K * B * per:
-                raise ValueError(f"BlockReplay.sample_nstep: out[{name!r}] holds {t.numel() // per} rows, "
-                                 f"needs {self.K * B}")
+        _check_out_rows("BlockReplay.sample_nstep", out, ("s", "s2", "a", "r", "done", "gamma_row"), self.K * B,
+                       f"needs {self.K * B}", optional=("nlen", "idx"))
         base, count = self.live_range()
         ns = (C.c_int32 * self.K)(*[int(n) for n in n_step])
         gm = (C.c_float * self.K)(*[float(g) for g in gamma])

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from ._lib import OBS_WORDS, check, evx_replay, lib
-from .env import DeviceLayout, VecEnv, _ptr, _stream, n_layout_rows
+from .env import DeviceLayout, VecEnv, _check_out_rows, _ptr, _stream, n_layout_rows
 from .qmlp import act_ws_ints
 from .qnet import DROPOUT_P, Learner, validate_nets_options, validate_td_options
 
@@ -91,9 +91,28 @@ class Replay:
                                       out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
                                       out["done"].data_ptr(), _ptr(out.get("idx")), _stream()), "replay_sample")
 
+    def sample_agents(self, B, nets, seed, offset, out, joint=False):
+        """Agent g's B draws from its own transitions, or (joint) the env-steps of one permutation for
+        every agent, into rows [g B, (g + 1) B) of out (evx_replay_sample_agents / _sample_joint)."""
+        fn = lib().evx_replay_sample_joint if joint else lib().evx_replay_sample_agents
+        check(fn(C.byref(self.c), self.size, B, nets, seed, offset, out["s"].data_ptr(), out["s2"].data_ptr(),
+                 out["a"].data_ptr(), out["r"].data_ptr(), out["done"].data_ptr(), _stream()),
+              "replay_sample_agents/joint")
+
     def live_range(self):
         """(base, count) of the whole ring in push order, oldest first."""
         return (self.pos - self.size) % self.capacity, self.size
+
+    def sample_nstep_agents(self, B, nets, seed, offset, base, count, stride, n_step, gamma, out, joint=False):
+        """sample_agents' draws, each followed along its agent's chain as nstep does, in one launch
+        (evx_replay_sample_nstep_agents); out["nlen"] (int32, L) and out["idx"] (int64, j0) are optional."""
+        _check_out_rows("sample_nstep_agents", out, ("s", "s2", "a", "r", "done", "gamma_row"), nets * B,
+                       f"needs {nets * B}", optional=("nlen", "idx"))
+        check(lib().evx_replay_sample_nstep_agents(
+            C.byref(self.c), self.size, B, nets, int(joint), seed, offset, base, count, stride, n_step, float(gamma),
+            out["s"].data_ptr(), out["s2"].data_ptr(), out["a"].data_ptr(), out["r"].data_ptr(),
+            out["done"].data_ptr(), out["gamma_row"].data_ptr(), _ptr(out.get("nlen")), _ptr(out.get("idx")),
+            _stream()), "replay_sample_nstep_agents")
 
     def nstep(self, idx, B, base, count, stride, n_step, gamma, out):
         """n-step rows of the sampled slots idx (int64 [B], the samplers' idx_out) over the live
@@ -102,14 +121,11 @@ class Replay:
         out["done"] = the chain's last slot's, out["gamma_row"] = gamma^L (f32 products),
         out["nlen"] (optional, int32) = L. The chain stops at a terminal slot and at the end of
         the range."""
-        for k, per in (("r", 1), ("done", 1), ("gamma_row", 1), ("s2", OBS_WORDS)):
-            if out[k].numel() < B * per:
-                raise ValueError(f"nstep: out[{k!r}] holds {out[k].numel() // per} rows, B = {B}")
+        _check_out_rows("nstep", out, ("r", "done", "gamma_row", "s2"), B, f"B = {B}")
         if idx.dtype != torch.int64 or idx.numel() < B:
             raise ValueError(f"nstep: idx must be an int64 tensor of at least B = {B} elements")
+        _check_out_rows("nstep", out, (), B, f"B = {B}", optional=("nlen",))  # (after idx, as it always was)
         nlen = out.get("nlen")
-        if nlen is not None and nlen.numel() < B:
-            raise ValueError(f"nstep: out['nlen'] holds {nlen.numel()} rows, B = {B}")
         check(lib().evx_replay_nstep(C.byref(self.c), idx.data_ptr(), B, base, count, stride, n_step,
                                      float(gamma), out["s2"].data_ptr(), out["r"].data_ptr(),
                                      out["done"].data_ptr(), out["gamma_row"].data_ptr(), _ptr(nlen),
@@ -431,18 +447,13 @@ class VecTrainer:
                 # the draws of the sampler below, each followed along its robot's chain over the whole
                 # ring in the same launch (evx_replay_sample_nstep_agents; one push is E * R rows)
                 self.last_range = self.replay.live_range()
-                check(lib().evx_replay_sample_nstep_agents(
-                    C.byref(self.replay.c), self.replay.size, Bn, self.R, int(self.qmix is not None), self.seed + 1,
-                    self.learn_steps * self.batch, self.last_range[0], self.last_range[1], self.n_agents, self.n_step,
-                    float(self.glearner.gamma), sp["s"].data_ptr(), sp["s2"].data_ptr(), sp["a"].data_ptr(),
-                    sp["r"].data_ptr(), sp["done"].data_ptr(), sp["gamma_row"].data_ptr(), sp["nlen"].data_ptr(),
-                    sp["idx"].data_ptr(), _stream()), "replay_sample_nstep_agents")
+                self.replay.sample_nstep_agents(Bn, self.R, self.seed + 1, self.learn_steps * self.batch,
+                                                self.last_range[0], self.last_range[1], self.n_agents, self.n_step,
+                                                self.glearner.gamma, sp, joint=self.qmix is not None)
                 grow = sp["gamma_row"]  # [R][Bn]; QMIX reads agent 0's rows [0, Bn): the joint rows'
             else:
-                fn = lib().evx_replay_sample_joint if self.qmix is not None else lib().evx_replay_sample_agents
-                check(fn(C.byref(self.replay.c), self.replay.size, Bn, self.R, self.seed + 1,
-                         self.learn_steps * self.batch, sp["s"].data_ptr(), sp["s2"].data_ptr(), sp["a"].data_ptr(),
-                         sp["r"].data_ptr(), sp["done"].data_ptr(), _stream()), "replay_sample_agents/joint")
+                self.replay.sample_agents(Bn, self.R, self.seed + 1, self.learn_steps * self.batch, sp,
+                                          joint=self.qmix is not None)
             if self.qmix is not None:  # agent 0's rows carry the team reward / done of the sampled env-steps
                 loss = self.qmix(self.lay.c, sp["s"], sp["a"], sp["r"], sp["done"], sp["s2"], Bn,
                                  double_q=self.double_q, huber_delta=self.huber, gamma_row=grow)
@@ -450,19 +461,7 @@ class VecTrainer:
                 loss = self.glearner.learn_obs(self.lay.c, sp["s"], sp["a"], sp["r"], sp["done"], sp["s2"], Bn,
                                                gamma_row=grow, double_q=self.double_q,
                                                huber_delta=[self.huber] * self.R if self.huber else None)
-            self.learn_steps += 1
-            if self.epsilon > self.epsilon_min:
-                self.epsilon *= self.epsilon_decay
-            if self.target_tau > 0:  # Polyak targets after every learn step, no periodic hard copy
-                if self.qmix is not None:
-                    self.qmix.soft_update(self.target_tau)
-                else:
-                    self.glearner.soft_update([self.target_tau] * self.R)
-            elif self.learn_steps % self.target_every == 0:
-                if self.qmix is not None:
-                    self.qmix.sync_targets()
-                else:
-                    self.glearner.sync_target()
+            self._learned()
             return loss
         if phase != "update":
             if (self.replay.size if window is None else window[1]) < self.batch:
@@ -517,14 +516,28 @@ class VecTrainer:
         else:
             self.learner.step_optimizer()
             loss = self.learner.loss
+        self._learned()
+        return loss
+
+    def _learned(self):
+        """After every learn step: the step count, the epsilon schedule and the target nets."""
         self.learn_steps += 1
         if self.epsilon > self.epsilon_min:  # DQNAgent.learn epsilon schedule (agents/dqn_agent.py:163-164)
             self.epsilon *= self.epsilon_decay
-        if self.target_tau > 0:  # Polyak target after every learn step, no periodic hard copy
-            self.learner.soft_update()
+        if self.target_tau > 0:  # Polyak targets after every learn step, no periodic hard copy
+            if not self.per_robot:
+                self.learner.soft_update()
+            elif self.qmix is not None:
+                self.qmix.soft_update(self.target_tau)
+            else:
+                self.glearner.soft_update([self.target_tau] * self.R)
         elif self.learn_steps % self.target_every == 0:
-            self.learner.sync_target()
-        return loss
+            if not self.per_robot:
+                self.learner.sync_target()
+            elif self.qmix is not None:
+                self.qmix.sync_targets()
+            else:
+                self.glearner.sync_target()
 
     def step(self, extra_reset: Optional[torch.Tensor] = None, ev_env=None, ev_learn=None, ev_act=None):
         """One training step. Finished envs are reset inside the env.step launch

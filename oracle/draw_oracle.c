@@ -6,7 +6,7 @@
  * Philox4x32-10 keyed by (seed, counter) -- these functions pin exactly which draws it makes.
  *   orc_epsilon_greedy : evx_act / the fused act's epsilon-greedy (csrc/qnet.hip act_kernel,
  *                        csrc/qmlp.hip fc3_act)
- *   orc_replay_indices : evx_replay_sample / _window (csrc/qnet.hip replay_sample_kernel)
+ *   orc_replay_indices : evx_replay_sample / _window (csrc/replay.hip replay_sample_kernel)
  *   orc_dropout_keep   : the fused MLP kernels' dropout hash (csrc/qmlp.hip drop_row/drop_pair)
  *   orc_dropout_mask   : evx_dropout_mask, the dense learner's keep mask (csrc/qnet.hip
  *                        dropout_mask_kernel)

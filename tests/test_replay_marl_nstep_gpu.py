@@ -1,4 +1,4 @@
-"""evx_replay_sample_nstep_agents (csrc/qnet.hip: the per-agent / joint draw and the n-step chain in
+"""evx_replay_sample_nstep_agents (csrc/replay.hip: the per-agent / joint draw and the n-step chain in
 one launch) against its numpy restatement (tests/marl_opts_util.py, checked without a device by
 tests/test_marl_opts_cpu.py) on that test's fixture, bit for bit, and against the two existing
 samplers at n_step = 1."""
