@@ -19,6 +19,16 @@ are comma lists in the same way (defaults: the optional ``agent:`` keys train_ve
 
 ``--eval-episodes N`` ends with a greedy evaluation (evacx.evaluate) of every member.
 
+``--pbt-every N`` (a multiple of ``--log-every``; 0, the default: off, the run above exactly) turns
+the grid into population-based training (evacx.pbt.PBTScheduler): every log line's summary goes to
+the scheduler, and right after the log line of every N-th step the worst ``--pbt-frac`` of the
+members (by ``--pbt-fitness`` over the episodes since the last round, ``--pbt-min-episodes`` at least)
+take the weights of the best in one launch and explore the hyperparameters of ``--pbt-space``
+(``lr:perturb:0.8,1.25:1e-6:1e-2;n_step:resample:1,3,5``):
+
+  pbt_log.csv                  one row per replaced member: round, step, dst, src, the two
+                               fitnesses and old -> new of every name of the space
+
 Usage: python -m Louvre_Evacuation.runners.train_pop --members 8 --envs 4096 --steps 2000 \\
            --lr 1e-3,3e-4,1e-4,3e-5,1e-3,3e-4,1e-4,3e-5 --gamma 0.99   (from dqn-marl_amd/)
 """
@@ -36,6 +46,7 @@ if project_root not in sys.path:
 import torch  # noqa: E402
 import yaml  # noqa: E402
 
+PBT_COLUMNS = ["round", "step", "dst", "src", "fitness_dst", "fitness_src"]  # then <name>_old, <name>_new per name
 CSV_COLUMNS = ["step", "episodes", "reward", "evac_rate", "death_rate", "length", "loss", "epsilon"]
 SUMMARY_KEYS = ("reward", "evac_rate", "death_rate")
 SUMMARY_COLUMNS = ["step"] + [f"{k}_{s}" for k in SUMMARY_KEYS for s in ("mean", "std", "min", "max")] + ["best_member"]
@@ -63,7 +74,35 @@ def parse_args(argv=None):
         ap.add_argument(flag, default=None, metavar="a,b,..", help=f"{what}: one value, or one per member")
     ap.add_argument("--eval-episodes", type=int, default=0, help="episodes per env of a final greedy evaluation")
     ap.add_argument("--eval-envs", type=int, default=None, help="envs of that evaluation (default: a member's envs)")
+    ap.add_argument("--pbt-every", type=int, default=0,
+                    help="steps between exploit / explore rounds, a multiple of --log-every (0: no rounds)")
+    ap.add_argument("--pbt-frac", type=float, default=0.25, help="share of the members replaced per round")
+    ap.add_argument("--pbt-min-episodes", type=int, default=1,
+                    help="episodes a member must have finished since the last round to take part in one")
+    ap.add_argument("--pbt-fitness", default="return_mean", choices=["return_mean", "evac_rate", "neg_death_rate"])
+    ap.add_argument("--pbt-space", default="lr:perturb:0.8,1.25:1e-6:1e-2", metavar="name:spec;..",
+                    help="what a receiver explores: name:perturb:factors:lo:hi or name:resample:values, joined by ';'")
     return ap.parse_args(argv)
+
+
+def pbt_scheduler(args, people: int):
+    """The scheduler the --pbt-* flags ask for, or None with --pbt-every 0 (ValueError naming the flag;
+    no device needed)."""
+    if args.pbt_every == 0:
+        return None
+    if args.pbt_every < 0 or args.pbt_every % args.log_every:
+        raise ValueError(f"--pbt-every must be a positive multiple of --log-every = {args.log_every}, "
+                         f"not {args.pbt_every}")
+    from evacx.pbt import PBTScheduler, parse_space
+    return PBTScheduler(args.members, parse_space(args.pbt_space), frac=args.pbt_frac,
+                        min_episodes=args.pbt_min_episodes, fitness=args.pbt_fitness, seed=args.seed, people=people)
+
+
+def pbt_rows(round_: int, step: int, decisions, names) -> list:
+    """The pbt_log.csv rows of one round's decisions."""
+    return [[round_, step, d["dst"], d["src"], repr(d["fitness_dst"]), repr(d["fitness_src"])] +
+            [x if isinstance(x, str) else repr(x) for n in names for x in (d["old"][n], d["new"][n])]
+            for d in decisions]
 
 
 def broadcast(name: str, text, K: int, conv, default):
@@ -150,6 +189,7 @@ def train_pop(args):
     ec, ac = config["env"], config["agent"]
     hp = member_hparams(args, ac)
     opts = member_options(args, ac)
+    sched = pbt_scheduler(args, int(ec["num_people"]))
     if not torch.cuda.is_available():
         raise RuntimeError("train_pop needs an MI355X (HIP) device; no CPU fallback exists")
     out_dir = args.out or os.path.join(project_root, config.get("save_path", "dqn_results"))
@@ -174,8 +214,14 @@ def train_pop(args):
           f"target tau {opts['target_tau']}, n_step {opts['n_step']}")
     files = [open(os.path.join(d, "training_log.csv"), "w", newline="") for d in dirs]
     rows = None
+    if sched is not None:
+        names = sorted(sched.space)
+        files.append(open(os.path.join(out_dir, "pbt_log.csv"), "w", newline=""))
+        plog = csv.writer(files[-1])
+        plog.writerow(PBT_COLUMNS + [f"{n}_{s}" for n in names for s in ("old", "new")])
+        files[-1].flush()
     try:
-        logs = [csv.writer(f) for f in files]
+        logs = [csv.writer(f) for f in files[:K]]  # (files[K], with a scheduler: pbt_log.csv)
         for log in logs:
             log.writerow(CSV_COLUMNS)
         with open(os.path.join(out_dir, "population_summary.csv"), "w", newline="") as sf:
@@ -185,7 +231,8 @@ def train_pop(args):
                 tr.step()
                 if step % args.log_every and step != args.steps:
                     continue
-                rows = tr.episode_summary()["per_member"]  # the only host sync of the loop
+                summary = tr.episode_summary()  # the only host sync of the loop
+                rows = summary["per_member"]
                 loss = None if tr.last_loss is None else tr.last_loss.tolist()
                 for k, (log, s) in enumerate(zip(logs, rows)):
                     log.writerow([step, s["episodes"]] + ["" if v is None else repr(v) for v in
@@ -199,6 +246,17 @@ def train_pop(args):
                 print(f"step {step:7d}: episodes={sum(s['episodes'] for s in rows):6d}, death rate "
                       f"{_fmt(min((s['death_rate'] for s in done), default=None), '.2%')} .. "
                       f"{_fmt(max((s['death_rate'] for s in done), default=None), '.2%')}, best member {srow[-1]}")
+                if sched is None:
+                    continue
+                sched.observe(summary)
+                if step % args.pbt_every == 0:
+                    rnd = sched.round
+                    decisions = sched.round_(tr)
+                    plog.writerows(pbt_rows(rnd, step, decisions, names))
+                    files[-1].flush()
+                    print(f"pbt round {rnd} at step {step}: " + (", ".join(
+                        f"{d['dst']} <- {d['src']} (" + ", ".join(f"{n} {d['old'][n]!r} -> {d['new'][n]!r}" for n in names)
+                        + ")" for d in decisions) or "no member replaced"))
     finally:
         for f in files:
             f.close()

@@ -195,6 +195,12 @@ class evx_vprobe(C.Structure):
               "w_emin", "w_emax")
 
 
+class evx_member_buf(C.Structure):
+    """One [members][...] array of evx_copy_members: member k's block is bytes [0, bytes) at
+    base + k * stride_bytes."""
+    _fields_ = [("base", C.c_void_p), ("stride_bytes", C.c_int64), ("bytes", C.c_int64)]
+
+
 # ---------------------------------------------------------------- signatures
 # symbol -> (restype, argtypes), one entry per prototype of the header, in its order. A pointer to a
 # structure mirrored above is typed; _vp is a `void *` (streams) or a plain data pointer (device and
@@ -308,6 +314,7 @@ SIGNATURES = {
     "evx_td_loss_opt_nets": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32, _i32] + [_vp] * 5 +
                              [_i64, _vp, _i64, _OPTS, _vp, _vp]),
     "evx_qmlp_polyak_pack3_g": (C.c_int, [_vp] * 13 + [_i32, _vp]),
+    "evx_copy_members": (C.c_int, [_P(evx_member_buf), _i32, _P(_i32), _i32, _vp]),
     "evx_qmix_nparams": (C.c_int32, [_i32]),
     "evx_qmix_part_floats": (C.c_int64, [_i32, _i32]),
     "evx_qmix_loss": (C.c_int, [_vp, _vp, _i32] + [_vp] * 3 + [_f32, _i32, _i32] + [_vp] * 7 + [_i64, _vp]),

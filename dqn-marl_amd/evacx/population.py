@@ -36,7 +36,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from ._lib import NSTEP_MAX, OBS_WORDS, check, evx_replay, lib
+from ._lib import NSTEP_MAX, OBS_WORDS, check, evx_member_buf, evx_replay, lib
 from .env import _check_out_rows, _ptr, _stream
 
 MAX_MEMBERS = 64
@@ -366,6 +366,43 @@ class PopulationTrainer:
             buf[dst].copy_(buf[src])
         gl.fast.nets[dst].repack()
         gl.fast_t.nets[dst].repack()
+
+    def member_map(self, src_map) -> list:
+        """src_map as copy_members takes it: K integers in 0..K - 1 whose donors keep their own block
+        (src_map[src_map[k]] == src_map[k]). ValueError naming the value otherwise (no device needed)."""
+        src = list(src_map) if isinstance(src_map, (list, tuple)) else None
+        if src is None or len(src) != self.K:
+            raise ValueError(f"src_map must be a sequence of members = {self.K} integers, not {src_map!r}")
+        for k, s in enumerate(src):
+            if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < self.K:
+                raise ValueError(f"src_map[{k}] must be an integer in 0..{self.K - 1}, not {s!r}")
+        for k, s in enumerate(src):
+            if src[s] != s:
+                raise ValueError(f"src_map[{k}] = {s}: member {s} is itself replaced (by {src[s]}); a donor must "
+                                 f"keep its own block")
+        return src
+
+    def _member_bufs(self):
+        """Every [K][...] array a member's learner state lives in, as evx_copy_members takes them:
+        flat, tflat, m, v and the nine operand buffers of both nets."""
+        gl = self.glearner
+        ts = [gl.flat, gl.tflat, gl.m, gl.v] + [fast.bufs[name] for fast in (gl.fast, gl.fast_t) for name in fast.bufs]
+        for t in ts:
+            assert t.dim() == 2 and t.shape[0] == self.K and t.is_contiguous()
+        return (evx_member_buf * len(ts))(*[
+            evx_member_buf(base=t.data_ptr(), stride_bytes=t.stride(0) * t.element_size(),
+                           bytes=t.shape[1] * t.element_size()) for t in ts])
+
+    def copy_members(self, src_map):
+        """copy_member(src_map[k], k) for every member k with src_map[k] != k, in one launch
+        (evx_copy_members): the receivers take their donors' online and target parameters, Adam
+        moments and the operand copies of both nets -- a pure function of the parameters, so the
+        copied operands are the bits a repack would write. src_map: K integers (member_map checks
+        them); no donor may itself be replaced. Hyperparameters, ring and envs stay the receiver's
+        own. The identity map launches nothing."""
+        src = self.member_map(src_map)
+        bufs = self._member_bufs()
+        check(lib().evx_copy_members(bufs, len(bufs), (C.c_int32 * self.K)(*src), self.K, _stream()), "copy_members")
 
     def member_learner(self, k: int):
         """An evacx.qnet.Learner holding member k's online and target weights, Adam moments,

@@ -932,6 +932,25 @@ int evx_td_loss_opt_nets(const float *Q, const float *Qt, int32_t A, const int32
 int evx_qmlp_polyak_pack3_g(const float *p, float *t, const float *tau, const float *one_minus_tau, uint16_t *w1b,
                             uint16_t *w1l, float *b1c, uint16_t *w2b, uint16_t *w2l, uint16_t *w2t, uint16_t *w2tl,
                             uint16_t *w1o, uint16_t *w1ol, int32_t nets, void *stream);
+/* Exploit step of population-based training: members take other members' blocks of [members][...]
+ * arrays, every array and every receiver in one launch. One evx_member_buf describes one array:
+ * member k's block is bytes [0, bytes) at base + k * stride_bytes. */
+typedef struct {
+    void *base;           /* member 0's block (device) */
+    int64_t stride_bytes; /* from one member's block to the next */
+    int64_t bytes;        /* of a block that are copied (<= stride_bytes) */
+} evx_member_buf;
+/* For every member k with src[k] != k and every buffer b: bytes [0, bytes) of base + k * stride_bytes
+ * <- the same bytes of base + src[k] * stride_bytes. bufs [nbufs] and src [members] are host arrays,
+ * passed to the kernel by value as evx_qmlp_act_gb's epsilons are. One launch, grid (chunk, receiver,
+ * buffer): 16 bytes per lane where the two blocks are congruent mod 16 (4-byte words before and
+ * after the aligned part), 4 bytes per lane otherwise; members that keep their block, the donors
+ * among them, and every byte outside the blocks are not written. The identity map returns 0 without
+ * a launch. -22 before any launch: a NULL pointer (bufs, src, a base), members outside 1..64, nbufs
+ * outside 1..32, a src[k] outside 0..members - 1, a donor that is itself replaced (src[src[k]] !=
+ * src[k]: a read / write race inside the launch), a base, stride_bytes or bytes that is no multiple
+ * of 4, bytes negative or > stride_bytes. */
+int evx_copy_members(const evx_member_buf *bufs, int32_t nbufs, const int32_t *src, int32_t members, void *stream);
 
 /* ---- QMIX mixer (runners/train_qmix.py:39-54 MixingNetwork, loss :78-104) for n <= 16 agents:
  * Q / Qt [n][B][A] (evx_qmlp_forward2_g), act [n][B], rew / done [B]; mix / mix_t the online /
